@@ -2,6 +2,13 @@
 """bench.py -- headline benchmark of the operator hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+        [--dump-outputs DIR]   after the timed steps: the Q3 result of the last one as DIR/q3_<column>.npy (float64)
+        [--full]               everything past the headline (see below)
+
+A plain run sets up Q3, warms up, times K steps and prints the headline line: `value`, `ms_per_step`, `config`, and the `roofline` and
+per-kernel figures that the timed steps' own profile yields.  `--full` adds what takes work or runs of its own: the size-independent checks
+of the results, the Q3 top-10 tail and the individually timed steps, the paged feeding, Q1, cfg2, the PCIe-inclusive line, the sub-benchmarks
+and the CPU baseline (at N > 1: the Q3 tail, the repartition plan and distributed Q1).
 
 Workload at N=1 (BASELINE.json configs[3], the one the metric is quoted on): the TPCH-SF100 Q3 operator pipeline on
 synthetic, seeded, device-resident TPCH-shaped columns --
@@ -1374,19 +1381,49 @@ def dominant(profile, steps, rows_per_step, bytes_per_row, pmc_prefix=""):
             "algorithmic_bytes_per_row": bytes_per_row[best], "rows_per_step": rows_per_step[best], "rows_per_launch": rows_per_step[best] / launches}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(pages, names, out_dir, suffix=""):
+    """the columns of `pages` (what a caller of the timed path receives) as <out_dir>/<name><suffix>.npy, float64 with nulls as NaN; past
+    DUMP_LIMIT_BYTES in all, every column keeps the same seeded sample of rows (in row order)"""
+    host = [o.to_host() for o in pages]
+    cols = []
+    for c in range(len(names)):
+        parts = []
+        for h in host:
+            blk = h.getBlock(c)
+            v = np.asarray(blk.values, dtype=np.float64)
+            if blk.nulls is not None:
+                v = np.where(blk.nulls.astype(bool), np.nan, v)
+            parts.append(v)
+        cols.append(np.concatenate(parts) if parts else np.zeros(0))
+    limit = (DUMP_LIMIT_BYTES - 4096) // (8 * len(names))      # (room for the .npy headers)
+    if len(cols[0]) > limit:
+        keep = np.sort(np.random.default_rng(SEED).choice(len(cols[0]), limit, replace=False))
+        cols = [v[keep] for v in cols]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in zip(names, cols):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sf", type=float, default=100.0, help="TPCH scale factor per GPU")
-    ap.add_argument("--only", default="", help="comma list of q3,q1,cfg2,sub,paged (default at N=1: all of them; at N>1: q3,q1 as distributed plans); paged = the same programs fed as 2^20- / 2^24-row pages and the PCIe-inclusive Q1 line (profiler passes name the other four, so that their per-kernel averages are those of the headline launches)")
+    ap.add_argument("--full", action="store_true", help="add the checks, the other workloads, the paged lines and the CPU baseline to the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's Q3 result columns to DIR as float64 .npy files")
+    ap.add_argument("--only", default="", help="with --full: comma list of q3,q1,cfg2,sub,paged (default at N=1: all of them; at N>1: q3,q1 as distributed plans); paged = the same programs fed as 2^20- / 2^24-row pages and the PCIe-inclusive Q1 line (profiler passes name the other four, so that their per-kernel averages are those of the headline launches)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-sf", type=float, default=20.0, help="scale factor of the bounded sample the CPU baseline runs (~10-25 s of CPU work)")
     args = ap.parse_args()
+    if args.only and not args.full:
+        ap.error("--only picks among the --full measurements")
     b = Bench(args)
     assert b.world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={b.world}"
-    only = set(args.only.split(",")) if args.only else ({"q3", "q1", "cfg2", "sub", "paged"} if b.world == 1 else {"q3", "q1"})
+    only = set() if not args.full else set(args.only.split(",")) if args.only else ({"q3", "q1", "cfg2", "sub", "paged"} if b.world == 1 else {"q3", "q1"})
     b.ctx.profile_enable(os.environ.get("TGPU_BENCH_NOPROFILE") is None)   # (kernel study: cost of the event timers)
     out = {}
     extra = {}
@@ -1398,7 +1435,14 @@ def main():
     step_fn = b.step_q3 if not distributed else (b.step_q3_dist_repartition if repartition else b.step_q3_dist)
     step_s, prof = b.timed(step_fn, args.steps, args.warmup)
     q3_readbacks = b.last_readbacks_per_step
-    q3_check = (b.check_q3_dist_repartition() if repartition else b.check_q3_dist()) if distributed else b.check_q3()
+    if args.dump_outputs:
+        dump_outputs(b.q3_result or [], ["q3_orderkey", "q3_orderdate", "q3_shippriority", "q3_revenue"], args.dump_outputs, f"_rank{b.rank}" if distributed else "")
+    # the rows entering the two probes (what the filters keep of orders / lineitem): input properties `value` and the roofline are quoted
+    # on.  The repartition plan's steps record the rows each rank received instead.
+    b.q3_stats.setdefault("orders_probe_rows", int((b.q3["o_orderdate"] < D_1995_03_15).sum().item()))
+    b.q3_stats.setdefault("lineitem_probe_rows", int((b.q3["l_shipdate"] > D_1995_03_15).sum().item()))
+    if args.full:
+        q3_check = (b.check_q3_dist_repartition() if repartition else b.check_q3_dist()) if distributed else b.check_q3()
     st = dict(b.q3_stats)
     probe_rows = st["lineitem_probe_rows"]
     total_probe = probe_rows
@@ -1443,9 +1487,11 @@ def main():
                                    if os.environ.get("TGPU_BENCH_PLAN") == "partial_final" else
                                    f"x{b.world}: customer replicated (RCCL all-gather), orders/lineitem and the aggregation co-partitioned on orderkey (no further exchange)"),
                    "exchange_bytes_sent_per_step": st.get("exchange_bytes_sent", 0)},
-        "roofline": roof, "checks": {"q3": q3_check},
+        "roofline": roof,
     })
-    if distributed:
+    if args.full:
+        out["checks"] = {"q3": q3_check}
+    if distributed and args.full:
         # Extras of the N-rank line (Q3's top-10 tail, the repartition plan): the headline fields above are complete; should an extra raise,
         # the line still goes out with what is there; a collective in an extra that never returns ends the process with exit code 3 after the
         # watchdog has printed the line marked `extras_timed_out` (a hang is a failure, not a result).
@@ -1511,14 +1557,15 @@ def main():
         except Exception as e:   # (every rank runs the same code on the same schedule: they fail together)
             extra["extras_error"] = repr(e)
         watchdog.cancel()
-    if not distributed and b.q3_result:
+    if args.full and not distributed and b.q3_result:
         extra["q3_top10"] = b.q3_top10(args.steps, args.warmup)
 
     if not distributed:
         for o in (b.q3_result or []):
             o.release()
         b.q3_result = None
-        extra["q3_step_stats"] = b.step_stats(b.step_q3, min(args.steps, 20))
+        if args.full:
+            extra["q3_step_stats"] = b.step_stats(b.step_q3, min(args.steps, 20))
     extra["q3_readbacks_per_step"] = q3_readbacks   # host <- device round trips (stream waits) of one Q3 step
     extra["q3_kernels_ms_per_step"] = {k: v["total_ms"] / args.steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"])}
     extra["q3_kernel_launch_min_max_ms"] = {k: [v["min_ms"], v["max_ms"], v["count"]] for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"])[:8]}
@@ -1621,7 +1668,7 @@ def main():
         torch.cuda.empty_cache()
         out["sub_benchmarks"] = sub
         out["checks"]["sub_benchmarks"] = {k: v["ok"] for k, v in sub.items()}
-    if b.rank == 0 and b.world == 1 and not args.no_cpu_baseline:
+    if args.full and b.rank == 0 and b.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(b, args.cpu_sample_sf)
     out.update(extra)
     if getattr(b, "extras_watchdog", None) is not None:

@@ -1,5 +1,5 @@
 """CPU-only checks of bench.py's contract (the driver parses ONE JSON line): the committed line of the newest round (profiles/rNN_bench.json, written by
-`python bench.py` on an MI355X) carries every key the contract names, `roofline` and `cpu_baseline` included, and its numbers are consistent
+`python bench.py --full` on an MI355X) carries every key the contract names, `roofline` and `cpu_baseline` included, and its numbers are consistent
 with each other (value = units / time, frac = achieved / peak, the committed rocprofv3 average of the dominant kernel agrees with the
 in-library timing)."""
 import csv

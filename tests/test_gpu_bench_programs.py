@@ -211,7 +211,7 @@ def test_full_size_sf100_properties(bench_mod, bench):
 
 
 def test_paged_feeding_gives_the_single_page_results_bit_for_bit(bench):
-    """bench.py's page-granularity sub-lines (`--only paged`): Q1 and Q3 fed as many small pages -- the speculative accumulate launch
+    """bench.py's page-granularity sub-lines (`--full --only paged`): Q1 and Q3 fed as many small pages -- the speculative accumulate launch
     behind the group probe, per-workgroup folded partials kept across pages, MergePages in front of the aggregation, the emit pass's
     build-channel gather -- must give exactly the rows of the one-page-per-table run (exact double sums are order independent; the
     many-group sums of Q3 are added in row order either way: pages do not change the row order)"""

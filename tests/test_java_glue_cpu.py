@@ -1,9 +1,9 @@
 """Static checks of the Java glue (java/io/trino/...) against the reference's SOURCES -- there is no JDK in the image, so nothing compiles the glue;
-these tests catch the class of mistake round 2 shipped (a glue class extending the final io.trino.spi.Page).  They read /root/reference as text and
-are skipped where it does not exist (the GPU box).  Checked: every io.trino import resolves to a reference class (nested ones included); no glue class
-extends a final class or implements a class; every @Override method is declared by a supertype (the reference's interface / class, or another glue
-class); every reference constructor the glue calls exists with that number of arguments; the methods and private fields of reference classes the glue
-relies on exist under those names; the handles GpuNative declares are the ones the glue calls."""
+these tests catch the class of mistake round 2 shipped (a glue class extending the final io.trino.spi.Page). Those that read the reference's sources
+as text (REF) are skipped where that checkout is absent; the last one needs only the glue. Checked: every io.trino import resolves to a reference
+class (nested ones included); no glue class extends a final class or implements a class; every @Override method is declared by a supertype (the
+reference's interface / class, or another glue class); every reference constructor the glue calls exists with that number of arguments; the methods
+and private fields of reference classes the glue relies on exist under those names; the handles GpuNative declares are the ones the glue calls."""
 import os
 import re
 
@@ -14,7 +14,7 @@ REF = "/root/reference"
 SRC_ROOTS = [os.path.join(REF, "core/trino-main/src/main/java"), os.path.join(REF, "core/trino-spi/src/main/java"), os.path.join(REF, "lib/trino-memory-context/src/main/java")]
 GLUE = os.path.join(ROOT, "java")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference sources are only present in the build container")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="needs a checkout of the reference sources")
 
 
 def strip_comments(text):
@@ -57,6 +57,7 @@ def resolve(name, text, package):
     return package + "." + name
 
 
+@needs_reference
 def test_every_reference_import_exists():
     for path, text in glue_files().items():
         for imp in imports_of(text):
@@ -85,6 +86,7 @@ def glue_type_sources():
     return out
 
 
+@needs_reference
 def test_no_glue_class_extends_a_final_class_or_implements_a_class():
     glue = glue_type_sources()
     checked = 0
@@ -143,6 +145,7 @@ def supertype_texts(name, glue, seen=None):
     return out
 
 
+@needs_reference
 def test_every_override_is_declared_by_a_supertype():
     glue = glue_type_sources()
     checked = 0
@@ -173,6 +176,7 @@ def test_every_override_is_declared_by_a_supertype():
     assert checked >= 20
 
 
+@needs_reference
 def test_reference_constructors_and_members_the_glue_relies_on_exist():
     S = "io.trino.spi."
     M = "io.trino."

@@ -2,8 +2,8 @@
 
     python tools/collect_profiles.py <tag> <stats_dir> [<pmc_fetch_dir> <pmc_write_dir> [<run_dir>]]
 
-  <stats_dir>      rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-  <pmc_*_dir>      rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+  <stats_dir>      rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+  <pmc_*_dir>      rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
                    (separate passes; never combined with other trace domains)
   <run_dir>        tools/final_measure.sh's output directory: its pmc_gbh_<shape>_<counter> passes (tools/exp_sub.py group_by_hash_<shape>, one
                    BenchmarkGroupByHash shape per pass) become "sub_group_by_hash_<shape>:gbh_insert"
@@ -75,7 +75,7 @@ def gbh_counter(d, name):
 
 def pmc(tag, dfetch, dwrite, run_dir=None):
     fetch, write = counter(dfetch, "FETCH_SIZE"), counter(dwrite, "WRITE_SIZE")
-    out = {"_comment": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `bench.py --steps 1 --warmup 1 "
+    out = {"_comment": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `bench.py --full --steps 1 --warmup 1 "
                        "--no-cpu-baseline` on MI355X; warm-up launches included in the per-launch lists.  Counter unit = KiB.  gfx950 correction "
                        "(MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports half of the bytes of a coalesced streaming read -> doubled; "
                        "WRITE_SIZE is used as reported.", "kernels": {}}
