@@ -681,7 +681,7 @@ void o_agg_count(const int64_t *gids, const uint8_t *nulls, const uint8_t *mask,
 
 /* Shewchuk's exact partials sum (as in CPython's math.fsum): result is the correctly rounded exact sum.
  * Not part of the reference; it is the yard-stick for the product's "exact sum" DOUBLE policy. */
-typedef struct { double *p; int32_t n, cap; double special; int has_special; } msum_t;
+typedef struct { double *p; int32_t n, cap; double special; int has_special, overflow; } msum_t;
 
 static void msum_add(msum_t *m, double x)
 {
@@ -691,6 +691,7 @@ static void msum_add(msum_t *m, double x)
         double y = m->p[j];
         if (fabs(x) < fabs(y)) { double t = x; x = y; y = t; }
         double hi = x + y;
+        if (!isfinite(hi)) m->overflow = 1;   /* a partial overflowed: the partials are lost, fx_sum redoes the group */
         double lo = y - (hi - x);
         if (lo != 0.0) m->p[i++] = lo;
         x = hi;
@@ -720,7 +721,71 @@ static double msum_result(msum_t *m)
             if (y == yr) hi = x;
         }
     }
-    return hi;
+    return hi + 0.0;   /* a zero sum is +0.0: the reference's sum starts from +0.0 */
+}
+
+/* Partials that overflow (1e308 + 1e308 - 1e308, DBL_MAX + 2^970) break Shewchuk's algorithm; such a group is summed again in fixed point:
+ * every finite double is an integer multiple of 2^-1074 below 2^2098, so a two's complement integer of FX_DIGITS 32-bit digits holds
+ * the sum of up to 2^140 of them exactly, and one rounding at the end gives the double nearest to it (ties to even). */
+#define FX_DIGITS 72
+typedef struct { uint32_t d[FX_DIGITS]; } fx_t;
+
+static void fx_add(fx_t *f, double x)
+{
+    uint64_t bits;
+    memcpy(&bits, &x, 8);
+    const int neg = (int)(bits >> 63), e = (int)((bits >> 52) & 0x7ff);
+    uint64_t m = bits & 0xfffffffffffffULL;
+    int sh = 0;                                 /* |x| = m * 2^sh * 2^-1074 */
+    if (e) { m |= 1ULL << 52; sh = e - 1; }
+    if (m == 0) return;
+    const unsigned __int128 w = (unsigned __int128)m << (sh % 32);
+    int64_t carry = 0;
+    for (int i = sh / 32; i < FX_DIGITS; i++) {
+        const int k = i - sh / 32;
+        const int64_t part = k < 3 ? (int64_t)(uint32_t)(w >> (32 * k)) : 0;
+        const int64_t t = (int64_t)f->d[i] + (neg ? -part : part) + carry;
+        f->d[i] = (uint32_t)t;
+        carry = t >> 32;                        /* -1, 0 or 1 (arithmetic shift) */
+        if (k >= 2 && carry == 0) break;
+    }
+}
+
+static int fx_bit(const fx_t *f, int i) { return (int)((f->d[i / 32] >> (i % 32)) & 1u); }
+
+static double fx_round(fx_t f)
+{
+    const int neg = (int)(f.d[FX_DIGITS - 1] >> 31);
+    if (neg) {                                  /* magnitude: two's complement */
+        uint64_t c = 1;
+        for (int i = 0; i < FX_DIGITS; i++) { const uint64_t t = (uint64_t)(uint32_t)~f.d[i] + c; f.d[i] = (uint32_t)t; c = t >> 32; }
+    }
+    int top = -1;
+    for (int i = FX_DIGITS * 32 - 1; i >= 0; i--)
+        if (fx_bit(&f, i)) { top = i; break; }
+    if (top < 0) return 0.0;
+    uint64_t out;
+    if (top <= 52) {                            /* subnormal or 2^-1022 .. 2^-1021: the integer is the bit pattern */
+        out = 0;
+        for (int i = top; i >= 0; i--) out = (out << 1) | (uint64_t)fx_bit(&f, i);
+    } else {
+        int sh = top - 52;                      /* keep bits top .. sh, round at bit sh - 1 */
+        uint64_t mant = 0;
+        for (int i = top; i >= sh; i--) mant = (mant << 1) | (uint64_t)fx_bit(&f, i);
+        const int guard = fx_bit(&f, sh - 1);
+        int sticky = 0;
+        for (int i = sh - 2; i >= 0 && !sticky; i--) sticky = fx_bit(&f, i);
+        if (guard && (sticky || (mant & 1))) {
+            mant++;
+            if (mant >> 53) { mant >>= 1; sh++; }
+        }
+        const int64_t be = (int64_t)sh + 1;     /* biased exponent of mant * 2^(sh - 1074), mant in [2^52, 2^53) */
+        out = be >= 2047 ? 0x7ff0000000000000ULL : (((uint64_t)be << 52) | (mant & 0xfffffffffffffULL));
+    }
+    if (neg) out |= 1ULL << 63;
+    double r;
+    memcpy(&r, &out, 8);
+    return r;
 }
 
 double o_exact_sum(const double *v, int64_t n)
@@ -728,6 +793,12 @@ double o_exact_sum(const double *v, int64_t n)
     msum_t m = {0};
     for (int64_t i = 0; i < n; i++) msum_add(&m, v[i]);
     double r = msum_result(&m);
+    if (!m.has_special && (m.overflow || !isfinite(r))) {
+        fx_t f;
+        memset(&f, 0, sizeof f);
+        for (int64_t i = 0; i < n; i++) fx_add(&f, v[i]);
+        r = fx_round(f);
+    }
     free(m.p);
     return r;
 }
@@ -743,7 +814,19 @@ void o_agg_double_sum_exact(const int64_t *gids, const double *v, const uint8_t 
         counts[g] += 1;
         msum_add(&ms[g], v[i]);
     }
-    for (int32_t g = 0; g < ngroups; g++) { sums[g] = msum_result(&ms[g]); free(ms[g].p); }
+    for (int32_t g = 0; g < ngroups; g++) {
+        sums[g] = msum_result(&ms[g]);
+        if (!ms[g].has_special && (ms[g].overflow || !isfinite(sums[g]))) {   /* the group again, in fixed point */
+            fx_t f;
+            memset(&f, 0, sizeof f);
+            for (int64_t i = 0; i < n; i++) {
+                if ((mask && !mask[i]) || (nulls && nulls[i]) || (gids ? gids[i] : 0) != g) continue;
+                fx_add(&f, v[i]);
+            }
+            sums[g] = fx_round(f);
+        }
+        free(ms[g].p);
+    }
     free(ms);
 }
 

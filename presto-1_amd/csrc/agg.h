@@ -5,7 +5,9 @@
 // DOUBLE sums use an order-independent exact accumulator (a Kulisch-style fixed-point "long accumulator" of 68 x 32-bit
 // limbs held in int64 words, updated with integer atomics), so the result is the correctly rounded exact sum whatever
 // the interleaving of lanes -- deterministic, and equal to the Java left-to-right sum whenever that sum is itself exact.
-// See DESIGN.md "DOUBLE aggregate policy".
+// The lane-private LDS path (few groups) keeps double-double pairs whose additions are error-free: what a pair cannot
+// hold goes exactly into the same limbs (device_agg.h TgSpill), so it yields the same bits; an addition that would
+// overflow a pair sends its addends to the limbs instead.  See DESIGN.md "DOUBLE aggregate policy".
 //
 // With MANY groups (more than the lane-private LDS path holds) that state would cost 544 bytes per group and per aggregate,
 // and neighbouring rows of one group would serialise on the same atomics.  Accumulators that allow it then switch to the

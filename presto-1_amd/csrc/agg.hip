@@ -312,7 +312,9 @@ __global__ void __launch_bounds__(TG_ORD_WAVES * 64) agg_ordered_chain_kernel(Ag
 // laid out [g][a][256 lanes] so a wave's access is 64 consecutive 8-byte words (conflict-free, no atomics, and the order
 // in which a lane adds its rows is fixed -> deterministic).  At the end of the block the 256 lane partials of each (g, a)
 // are folded with double-double adds and added EXACTLY into the global limb accumulator, so both paths feed the same
-// state and the final rounding is still the exact sum's.
+// state and the final rounding is still the exact sum's.  Every pair addition is error-free: a rounding residue the pair
+// cannot hold (or an addend that would overflow it) goes exactly into the group's limbs (device_agg.h tg_dd_add1 /
+// tg_dd_add / TgSpill) -- for data within a ~106-bit window there is none, and the path costs one more two-sum per row.
 // ---------------------------------------------------------------------------------------------------------------------
 using LowCardPlan = TgLowCardPlan;
 
@@ -350,7 +352,8 @@ __global__ void __launch_bounds__(kBlock) agg_lowcard_kernel(AggArgs args, LowCa
                 tg_flag_special(&a.special[g], v);
                 continue;
             }
-            tg_lc_add_double(hi_base, lo_base, w, v);
+            const double r = tg_lc_add_double(hi_base, lo_base, w, v);
+            if (r != 0.0) tg_kulisch_add(&a.limbs[(size_t)g * kLimbs], &a.special[g], r);   // what the lane's pair cannot hold (device_agg.h)
         }
     }
     tg_lc_fold(lds, plan, states.st, fold);
@@ -579,7 +582,12 @@ void GroupedAccumulators::resolve_pending(int64_t blocks, bool commit)
     if (!fold_pending_ || blocks <= 0) return;
     TG_CHECK_STATE(blocks <= fold_rows_, "pending rows beyond the fold scratch");
     LowCardStates states{};
-    for (size_t k = 0; k < states_.size(); k++) states.st[k].function = device_state((int)k).function;
+    for (size_t k = 0; k < states_.size(); k++) {   // (a commit spills the residues of its pair additions into the limbs)
+        const DeviceState d = device_state((int)k);
+        states.st[k].function = d.function;
+        states.st[k].limbs = d.limbs;
+        states.st[k].special = d.special;
+    }
     agg_resolve_pending_kernel<<<(int)blocks, kBlock, 0, ctx_->stream()>>>(
         TgFoldScratch{fold_partials_->as<unsigned long long>(), (int)fold_stride_, fold_pending_->as<unsigned long long>()}, (int)states_.size(), states, commit ? 1 : 0);
     check_launch("agg_resolve_pending");

@@ -149,15 +149,58 @@ __device__ inline double tg_chain_add_tile(const double *in, int cnt, double os)
 #undef TG_ORD_ADDS
 #undef TG_ORD_MIX
 }
-// double-double add (hi, lo) += (h2, l2)
-__device__ inline void tg_dd_add(double &hi, double &lo, double h2, double l2)
+// ---- error-free double-double arithmetic of the lane-private path ------------------------------------------------------------------------
+// The pairs carry ~106 bits; what does not fit -- the rounding residue of an addition, or a whole addend when the pair would overflow -- is
+// returned to the caller, who sends it exactly into the group's limbs (tg_spill).  So pair + residues == the exact sum at every step, and
+// the path's result is the correctly rounded exact sum like the per-row limb path's.  For values that share a ~106-bit window (TPCH Q1's
+// prices, any data whose totals stay within 2^53 units of the finest input bit) every residue is zero and nothing is spilled.
+__device__ inline void tg_two_sum(double a, double b, double &s, double &e)
 {
-    const double s = hi + h2;
-    const double bb = s - hi;
-    double e = (hi - (s - bb)) + (h2 - bb);
-    e += lo + l2;
-    hi = s + e;
-    lo = e - (hi - s);
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+// (h, l) += v: returns the residue (0 almost always); when h + v overflows the pair is left as it was and v itself is returned
+__device__ inline double tg_dd_add1(double &h, double &l, double v)
+{
+    double s, err, t, r;
+    tg_two_sum(h, v, s, err);
+    tg_two_sum(l, err, t, r);
+    if (!(fabs(t) <= 1.7976931348623157e308)) return v;   // (s = inf makes err, t NaN; t = inf: the errors overflowed)
+    h = s;
+    l = t;
+    return r;
+}
+// (hi, lo) += (h2, l2): hi + lo + h2 + l2 == new (hi + lo) + r1 + r2 exactly.  Returns true -- (hi, lo) unchanged, r1 / r2 unset -- when
+// the sum overflows.
+__device__ inline bool tg_dd_add(double &hi, double &lo, double h2, double l2, double &r1, double &r2)
+{
+    double s, e1, t, u, nh, nl;
+    tg_two_sum(hi, h2, s, e1);
+    tg_two_sum(lo, l2, t, r1);
+    tg_two_sum(e1, t, u, r2);
+    tg_two_sum(s, u, nh, nl);
+    if (!(fabs(nh) <= 1.7976931348623157e308)) return true;   // (an overflow anywhere above ends in nh = inf or NaN)
+    hi = nh;
+    lo = nl;
+    return false;
+}
+// where the residues of one (group, aggregate) go: its limbs, or -- a launch whose totals may still be dropped (fq_onepass: the page's
+// totals are pending) -- a count that makes the page dirty, so that it is run again through the two-launch path, whose spills are final
+struct TgSpill {
+    long long *limbs;
+    unsigned int *special;
+    unsigned long long *dirty;
+};
+__device__ inline TgSpill tg_spill_to(const TgAggState &a, int g, unsigned long long *dirty)
+{
+    return TgSpill{a.limbs ? a.limbs + (size_t)g * TG_LIMBS : nullptr, a.special ? a.special + g : nullptr, dirty};
+}
+__device__ inline void tg_spill(const TgSpill &sp, double v)
+{
+    if (v == 0.0) return;
+    if (sp.dirty) atomicAdd(sp.dirty, 1ULL);
+    else tg_kulisch_add(sp.limbs, sp.special, v);
 }
 
 // ---- low-cardinality path: lane-private accumulators in LDS ---------------------------------------------------------
@@ -191,16 +234,15 @@ __device__ inline void tg_lc_zero(unsigned char *lds, const TgLowCardPlan &p)
     __syncthreads();
 }
 
-// one double into the lane's (hi, lo) slot: two-sum keeps the rounding error in lo
-__device__ inline void tg_lc_add_double(double *hi_base, double *lo_base, int w, double v)
+// one finite double into the lane's (hi, lo) slot; returns what the pair could not hold exactly (tg_dd_add1), for the caller to spill
+__device__ inline double tg_lc_add_double(double *hi_base, double *lo_base, int w, double v)
 {
     const int i = w * TG_AGG_BLOCK + threadIdx.x;
-    const double hi = hi_base[i];
-    const double s = hi + v;
-    const double bb = s - hi;
-    const double err = (hi - (s - bb)) + (v - bb);
-    hi_base[i] = s;
-    lo_base[i] += err;
+    double h = hi_base[i], l = lo_base[i];
+    const double r = tg_dd_add1(h, l, v);
+    hi_base[i] = h;
+    lo_base[i] = l;
+    return r;
 }
 
 __device__ inline void tg_lc_add_bigint(double *hi_base, double *lo_base, int w, long long v)
@@ -235,8 +277,9 @@ struct TgFoldScratch {
     unsigned long long *pending;
 };
 
-// a += b for a (hi, lo) double-double pair, or for the (low, high) words of a 128-bit integer
-__device__ inline void tg_fold_pair(bool bigint, unsigned long long &a0, unsigned long long &a1, unsigned long long b0, unsigned long long b1)
+// a += b for a (hi, lo) double-double pair, or for the (low, high) words of a 128-bit integer.  Doubles: the residues go to `sp` (on
+// overflow: b's two doubles, a stays); sp == nullptr only where the caller discards the result (the shuffle rounds' idle lanes)
+__device__ inline void tg_fold_pair(bool bigint, unsigned long long &a0, unsigned long long &a1, unsigned long long b0, unsigned long long b1, const TgSpill *sp)
 {
     if (bigint) {
         const unsigned long long s = a0 + b0;
@@ -245,19 +288,30 @@ __device__ inline void tg_fold_pair(bool bigint, unsigned long long &a0, unsigne
     }
     else {
         double hi = __longlong_as_double((long long)a0), lo = __longlong_as_double((long long)a1);
-        tg_dd_add(hi, lo, __longlong_as_double((long long)b0), __longlong_as_double((long long)b1));
+        const double h2 = __longlong_as_double((long long)b0), l2 = __longlong_as_double((long long)b1);
+        double r1, r2;
+        if (tg_dd_add(hi, lo, h2, l2, r1, r2)) {
+            r1 = h2;
+            r2 = l2;
+        }
+        if (sp) {
+            tg_spill(*sp, r1);
+            tg_spill(*sp, r2);
+        }
         a0 = (unsigned long long)__double_as_longlong(hi);
         a1 = (unsigned long long)__double_as_longlong(lo);
     }
 }
 
-__device__ inline void tg_fold_wave(bool bigint, unsigned long long &c, unsigned long long &a0, unsigned long long &a1)
+// (lane < d: the lanes whose sums go on to lane 0 -- the others add a value that is not theirs, and their results are dropped)
+__device__ inline void tg_fold_wave(bool bigint, unsigned long long &c, unsigned long long &a0, unsigned long long &a1, const TgSpill &sp)
 {
+    const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         c += __shfl_down(c, d, 64);
         const unsigned long long b0 = __shfl_down(a0, d, 64), b1 = __shfl_down(a1, d, 64);
-        tg_fold_pair(bigint, a0, a1, b0, b1);
+        tg_fold_pair(bigint, a0, a1, b0, b1, lane < d ? &sp : nullptr);
     }
 }
 
@@ -265,8 +319,9 @@ __device__ inline void tg_fold_wave(bool bigint, unsigned long long &c, unsigned
 // rotated start keeps the wave's reads on distinct banks, then three shuffle rounds fold the 8 sums -- 32 items per pass with every
 // lane busy (one wave per item with six full-width shuffle rounds was issue bound: ~2600 cycles per item, 10 us for TPCH Q1's 32
 // items).  The item's total is added to the block's slot: plain read-modify-write, no atomics, no cross-workgroup traffic.
+// `dirty`: null for launches whose totals are final (the residues go to the limbs), else the word that makes the page dirty (see TgSpill)
 template <bool OVERWRITE>
-__device__ inline void tg_lc_fold_to(unsigned char *lds, const TgLowCardPlan &p, const TgAggState *st, unsigned long long *mine)
+__device__ inline void tg_lc_fold_to(unsigned char *lds, const TgLowCardPlan &p, const TgAggState *st, unsigned long long *mine, unsigned long long *dirty)
 {
     __syncthreads();
     const int t = threadIdx.x, chunk = t & 7;
@@ -279,6 +334,7 @@ __device__ inline void tg_lc_fold_to(unsigned char *lds, const TgLowCardPlan &p,
         const unsigned int *cnt = tg_lc_cnt(lds, p, g) + (p.count_from_rows[k] ? p.rows_slot : p.cnt_slot[k]) * TG_AGG_BLOCK + chunk * 32;
         const int w = p.wide_slot[k];
         const bool bigint = st[k].function == TG_AGG_SUM_BIGINT;
+        const TgSpill sp = tg_spill_to(st[k], g, dirty);
         const unsigned long long *hi = (const unsigned long long *)tg_lc_hi(lds, p, g) + (w < 0 ? 0 : w) * TG_AGG_BLOCK + chunk * 32;
         const unsigned long long *lo = (const unsigned long long *)tg_lc_lo(lds, p, g) + (w < 0 ? 0 : w) * TG_AGG_BLOCK + chunk * 32;
         unsigned long long c = 0, a0 = 0, a1 = 0;
@@ -287,14 +343,14 @@ __device__ inline void tg_lc_fold_to(unsigned char *lds, const TgLowCardPlan &p,
             c += cnt[e];
             if (w >= 0) {
                 if (i == 0) { a0 = hi[e]; a1 = lo[e]; }
-                else tg_fold_pair(bigint, a0, a1, hi[e], lo[e]);
+                else tg_fold_pair(bigint, a0, a1, hi[e], lo[e], live ? &sp : nullptr);
             }
         }
 #pragma unroll
         for (int d = 4; d >= 1; d >>= 1) {   // the 8 threads of an item are neighbours
             c += __shfl_down(c, d, 64);
             const unsigned long long b0 = __shfl_down(a0, d, 64), b1 = __shfl_down(a1, d, 64);
-            tg_fold_pair(bigint, a0, a1, b0, b1);
+            tg_fold_pair(bigint, a0, a1, b0, b1, (live && chunk < d) ? &sp : nullptr);
         }
 #ifdef FA_DEBUG_SKIP
         if (FA_DEBUG_SKIP & 8) continue;
@@ -312,7 +368,7 @@ __device__ inline void tg_lc_fold_to(unsigned char *lds, const TgLowCardPlan &p,
             slot[0] += c;
             if (w >= 0) {
                 unsigned long long s0 = slot[1], s1 = slot[2];
-                tg_fold_pair(bigint, s0, s1, a0, a1);
+                tg_fold_pair(bigint, s0, s1, a0, a1, &sp);
                 slot[1] = s0;
                 slot[2] = s1;
             }
@@ -322,7 +378,7 @@ __device__ inline void tg_lc_fold_to(unsigned char *lds, const TgLowCardPlan &p,
 
 __device__ inline void tg_lc_fold(unsigned char *lds, const TgLowCardPlan &p, const TgAggState *st, TgFoldScratch fs)
 {
-    tg_lc_fold_to<false>(lds, p, st, fs.partials + (size_t)blockIdx.x * fs.stride * 3);
+    tg_lc_fold_to<false>(lds, p, st, fs.partials + (size_t)blockIdx.x * fs.stride * 3, nullptr);
 }
 
 // a workgroup row of pending totals joins the same row of the folded partials (the page they belong to turned out clean); the pending
@@ -334,10 +390,12 @@ __device__ inline void tg_commit_pending(TgFoldScratch fs, int n_aggs, const TgA
         unsigned long long *src = pend + (size_t)it * 3, *dst = mainr + (size_t)it * 3;
         const unsigned long long c = src[0];
         if (c != 0) {
-            const bool bigint = st[it % n_aggs].function == TG_AGG_SUM_BIGINT;
+            const int k = it % n_aggs;
+            const bool bigint = st[k].function == TG_AGG_SUM_BIGINT;
+            const TgSpill sp = tg_spill_to(st[k], it / n_aggs, nullptr);   // (the commit is final)
             dst[0] += c;
             unsigned long long s0 = dst[1], s1 = dst[2];
-            tg_fold_pair(bigint, s0, s1, src[1], src[2]);
+            tg_fold_pair(bigint, s0, s1, src[1], src[2], &sp);
             dst[1] = s0;
             dst[2] = s1;
         }
@@ -355,16 +413,17 @@ __device__ inline void tg_fold_flush(TgFoldScratch fs, int rows, int n_aggs, con
     const int g = it / n_aggs, k = it - g * n_aggs;
     const TgAggState &a = st[k];
     const bool bigint = a.function == TG_AGG_SUM_BIGINT;
+    const TgSpill sp = tg_spill_to(a, g, nullptr);
     unsigned long long c = 0, a0 = 0, a1 = 0;
     for (int b = lane; b < rows; b += 64) {
         unsigned long long *slot = fs.partials + ((size_t)b * fs.stride + it) * 3;
         const unsigned long long v = slot[0];
         if (v == 0) continue;
         c += v;
-        tg_fold_pair(bigint, a0, a1, slot[1], slot[2]);
+        tg_fold_pair(bigint, a0, a1, slot[1], slot[2], &sp);
         slot[0] = slot[1] = slot[2] = 0;
     }
-    tg_fold_wave(bigint, c, a0, a1);
+    tg_fold_wave(bigint, c, a0, a1, sp);
     if (lane != 0 || c == 0) return;
     atomicAdd((unsigned long long *)&a.counts[g], c);
     if (a.function == TG_AGG_COUNT_ALL || a.function == TG_AGG_COUNT_COLUMN || tg_is_minmax(a.function)) return;   // (min / max: the rows went to the state word)

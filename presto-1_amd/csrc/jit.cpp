@@ -2276,7 +2276,14 @@ struct FaArgs {
   unsigned int* ord_list_count;   // their number (starts at 0); ord_handoff 0 = lanes walk their groups to the end
   int ord_handoff;
   int pad4;
+  unsigned long long* spill_dirty; // one-pass launches (totals pending): a residue of the lane-private pairs counts here and makes the page
+                                   // dirty; null = the residues go straight to the limbs (device_agg.h TgSpill)
 };
+// what a lane's double-double pair of aggregate k cannot hold exactly (device_agg.h tg_dd_add1)
+__device__ inline void tg_lc_spill(const FaArgs& F, int k, int g, double r) {
+  if (F.spill_dirty) atomicAdd(F.spill_dirty, 1ULL);
+  else tg_kulisch_add(&F.st[k].limbs[(size_t)g * TG_LIMBS], &F.st[k].special[g], r);
+}
 // clean = no row met a new group ([0]), no table overflow ([2]), no expression error ([7] == ~0): groupby.h GbhSpeculateFn
 #define FA_GATE_CLOSED(F) ((F).gate && (((F).gate[0] | (F).gate[2] | ~(F).gate[7]) != 0ULL))
 // group id of a row: compact byte ids when the group-by table delivered them, else int32 ids, else the single global group
@@ -2313,6 +2320,8 @@ template <bool LC> __device__ inline void fa_accumulate_body(const FaArgs& F, un
   const FpArgs& A = F.fp;
   TgRow cur[FA_STRIPES], nxt[FA_STRIPES];
   int gcur[FA_STRIPES], gnxt[FA_STRIPES];
+  bool spilled = false;   // (unused: this kernel's totals are final, its residues go to the limbs)
+  (void)spilled;
 #pragma unroll
   for (int s = 0; s < FA_STRIPES; s++) {
     const long long row = (long long)blockIdx.x * FA_TILE + threadIdx.x + s * 256;
@@ -2339,7 +2348,7 @@ template <bool LC> __device__ inline void fa_accumulate_body(const FaArgs& F, un
 #pragma unroll
     for (int s = 0; s < FA_STRIPES; s++) {
       if (FA_GID_LIVE(gcur[s])) {
-        if (LC) tg_accumulate_row_lc(F, A, row0 + s * 256, cur[s], FA_GID_ID(gcur[s]), lds);
+        if (LC) tg_accumulate_row_lc<false>(F, A, row0 + s * 256, cur[s], FA_GID_ID(gcur[s]), lds, spilled);
         else tg_accumulate_row_gl(F, A, row0 + s * 256, cur[s], FA_GID_ID(gcur[s]));
       }
     }
@@ -2465,6 +2474,7 @@ template <bool MULTI> __device__ __forceinline__ void fq_body(const FqArgs& Q) {
   }
   const int rg = lg < FG_REG_GROUPS ? lg : FG_REG_GROUPS;
   unsigned long long unknown = 0;
+  bool spilled = false;                // a lane-private pair could not hold a row exactly: the page is dirty (counted with the unknown rows)
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the prologue's loads do not flow into the loop header (see fa_accumulate_body)
   while (pc < np) {
     const FpArgs A = FQ_PAGE(pc);
@@ -2517,16 +2527,17 @@ template <bool MULTI> __device__ __forceinline__ void fq_body(const FqArgs& Q) {
           if (fg_eq_record(A, cur[s].k, rec, g2) > 0) { result = g2; break; }
         unknown += result < 0 ? 1ULL : 0ULL;
       }
-      if (sel[s] && result >= 0) tg_accumulate_row_lc(F, A, tb + o, cur[s].r, result, lds);
+      if (sel[s] && result >= 0) tg_accumulate_row_lc<true>(F, A, tb + o, cur[s].r, result, lds, spilled);
     }
 #pragma unroll
     for (int s = 0; s < FQ_STRIPES; s++) cur[s] = nxt[s];
     g = gn; base = bn; pc = pn;
   }
+  unknown += spilled ? 1ULL : 0ULL;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) unknown += __shfl_down(unknown, d, 64);
   if ((threadIdx.x & 63) == 0 && unknown) atomicAdd(&Q.counters[0], unknown);
-  tg_lc_fold_to<true>(lds, F.plan, F.st, F.fold.pending + (size_t)blockIdx.x * F.fold.stride * 3);
+  tg_lc_fold_to<true>(lds, F.plan, F.st, F.fold.pending + (size_t)blockIdx.x * F.fold.stride * 3, F.spill_dirty);
   // the page's verdict goes to the host without a copy in the stream (a copy between two pages' launches keeps the second one waiting):
   // the workgroup that arrives last stores the counters into host memory and raises the flag the host polls
   if (Q.host_out) {
@@ -2587,6 +2598,7 @@ struct FaArgsHost {
     unsigned int *ord_list_count;
     int32_t ord_handoff;
     int32_t pad4;
+    unsigned long long *spill_dirty;
 };
 // host mirror of the generated FqArgs (fq_onepass)
 struct FqArgsHost {
@@ -2824,8 +2836,16 @@ void FusedAggGpu::generate()
         if (is_mm) lc_upd << "  if (t" << k << ") tg_minmax_update(" << mm_word << ", " << mm_code << ");\n";
         if (is_dbl && first_wide) {
             lc_read << "  double h" << w << " = hi_base[" << w << " * 256 + threadIdx.x], l" << w << " = lo_base[" << w << " * 256 + threadIdx.x];\n";
-            lc_upd << "  { const double v_ = t" << k << " ? x" << k << " : 0.0; const double s_ = h" << w << " + v_; const double bb_ = s_ - h" << w << "; l" << w
-                   << " += (h" << w << " - (s_ - bb_)) + (v_ - bb_); h" << w << " = s_; }\n";
+            // error-free: a residue goes to the limbs of every aggregate that shares the slot (each folds the slot into its own state)
+            // (PENDING, the one-pass kernel: its totals may be dropped, so a residue -- or an overflow, which leaves r_ NaN -- only marks the
+            // page dirty; no branch in the loop, the page is run again through the two-launch path)
+            lc_upd << "  { const double v_ = t" << k << " ? x" << k << " : 0.0;\n"
+                   << "    if (PENDING) { double s_, e_, u_, r_; tg_two_sum(h" << w << ", v_, s_, e_); tg_two_sum(l" << w << ", e_, u_, r_); h" << w << " = s_; l" << w
+                   << " = u_; spilled_ |= !(r_ == 0.0); }\n"
+                   << "    else { const double r_ = tg_dd_add1(h" << w << ", l" << w << ", v_); if (r_ != 0.0) {";
+            for (size_t j = k; j < aggs_.size(); j++)
+                if (wide_slot_[j] == w) lc_upd << " tg_lc_spill(F, " << j << ", g, r_);";
+            lc_upd << " } } }\n";
             lc_write << "  hi_base[" << w << " * 256 + threadIdx.x] = h" << w << "; lo_base[" << w << " * 256 + threadIdx.x] = l" << w << ";\n";
         }
         else if (is_big && first_wide) {
@@ -3270,9 +3290,10 @@ extern "C" __global__ void __launch_bounds__(256) fg_probe(FgArgs G) {
     std::string kernels = kFaKernels;
     const size_t split = kernels.find("#define FA_STRIPES");
     src << kernels.substr(0, split);
-    src << "__device__ inline void tg_accumulate_row_lc(const FaArgs& F, const FpArgs& A, long long row, const TgRow& R, int g, unsigned char* lds) {\n" << cols_decl(gr)
+    src << "template <bool PENDING> __device__ inline void tg_accumulate_row_lc(const FaArgs& F, const FpArgs& A, long long row, const TgRow& R, int g, unsigned char* lds, bool& spilled_) {\n"
+        << cols_decl(gr)
         << "  double* hi_base = tg_lc_hi(lds, F.plan, g); double* lo_base = tg_lc_lo(lds, F.plan, g);\n"
-        << "  unsigned int* cnt_base = tg_lc_cnt(lds, F.plan, g);\n  (void)hi_base; (void)lo_base; (void)row;\n"
+        << "  unsigned int* cnt_base = tg_lc_cnt(lds, F.plan, g);\n  (void)hi_base; (void)lo_base; (void)row; (void)spilled_;\n"
         << eval_all << lc_read.str() << "  unsigned int rows_ = cnt_base[" << rows_slot_ << " * 256 + threadIdx.x];\n" << lc_upd.str() << "  rows_ += 1u;\n" << lc_write.str()
         << "  cnt_base[" << rows_slot_ << " * 256 + threadIdx.x] = rows_;\n}\n";
     src << "__device__ inline void tg_accumulate_row_gl(const FaArgs& F, const FpArgs& A, long long row, const TgRow& R, int g) {\n" << cols_decl(gr) << "  (void)row;\n"
@@ -3503,6 +3524,7 @@ void FusedAggGpu::onepass(Context *ctx, const std::vector<const DevicePage *> &p
     Q.store = store;
     Q.store_groups = (int32_t)groups;
     Q.counters = counters;
+    F.spill_dirty = counters;   // (a page whose pairs had to spill is run again through the two-launch path: its totals here are pending)
     Q.prev = prev;
     Q.host_out = host_out;
     Q.done = host_out ? reinterpret_cast<unsigned int *>(static_cast<unsigned long long *>(ctx->zeroed_scratch()) + 1) : nullptr;

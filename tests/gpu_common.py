@@ -43,3 +43,42 @@ def ulp_diff(a, b):
     d = np.abs(ia - ib)
     both_nan = np.isnan(a) & np.isnan(b)
     return np.where(both_nan, 0, d)
+
+
+def run_agg(pkg, ctx, pages, group_types, group_channels, aggs, step=0, hash_channel=-1, expected=100):
+    f = pkg.HashAggregationOperatorFactory(ctx, 0, group_types, group_channels, aggs, step=step, hash_channel=hash_channel, expected_groups=expected)
+    op = f.createOperator()
+    out = pkg.to_pages(op, pages)
+    op.close()
+    rows = []
+    for p in out:
+        rows.extend(p.rows())
+    return rows
+
+
+def drive_with_revokes(op, pages, revoke):
+    """T/operator/OperatorAssertion.java:84-156 (toPagesPartial + finishOperator with revokeMemory): before every addInput and after
+    every getOutput the driver revokes whatever the operator holds as revocable memory"""
+    out = []
+
+    def revoke_all():
+        if revoke and op.revocableMemoryBytes() > 0:
+            op.startMemoryRevoke()
+            op.finishMemoryRevoke()
+    for pg in pages:
+        revoke_all()
+        assert op.needsInput()
+        op.addInput(pg)
+        o = op.getOutput()
+        assert o is None
+    op.finish()
+    for _ in range(1000):
+        if op.isFinished():
+            break
+        o = op.getOutput()
+        if o is not None:
+            out.append(o.to_host())
+            o.release()
+        revoke_all()
+    assert op.isFinished() and not op.needsInput()
+    return [r for p in out for r in p.rows()]

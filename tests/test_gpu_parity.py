@@ -8,7 +8,8 @@ import os
 import numpy as np
 import pytest
 
-from gpu_common import ocol, rand_block, ulp_diff
+from gpu_common import drive_with_revokes as _drive_with_revokes
+from gpu_common import ocol, rand_block, run_agg, ulp_diff
 from seqpages import sequence_page, sequence_values
 
 pytestmark = pytest.mark.gpu
@@ -260,17 +261,6 @@ def test_group_by_hash_integer_table_output_hash_is_recomputed_from_the_value(pk
 # ---------------------------------------------------------------------------------------------------------------------
 # hash aggregation operator
 # ---------------------------------------------------------------------------------------------------------------------
-def run_agg(pkg, ctx, pages, group_types, group_channels, aggs, step=0, hash_channel=-1, expected=100):
-    f = pkg.HashAggregationOperatorFactory(ctx, 0, group_types, group_channels, aggs, step=step, hash_channel=hash_channel, expected_groups=expected)
-    op = f.createOperator()
-    out = pkg.to_pages(op, pages)
-    op.close()
-    rows = []
-    for p in out:
-        rows.extend(p.rows())
-    return rows
-
-
 def test_hash_aggregation_golden(pkg, ctx, oracle):
     # T/operator/TestHashAggregationOperator.java:161-220 (count, sum, avg, count(col) columns; max(varchar) is out of scope)
     n = GOLD["hash_aggregation"]["testHashAggregation"]["rows"]
@@ -3251,34 +3241,6 @@ def test_fused_aggregation_low_cardinality_fold_many_items_growing_groups(pkg, o
     assert ulp_diff(np.array([r[3] for r in rows]), dsum).max() == 0
     assert all(-(2**63) <= s < 2**63 for s in isum)
     assert [r[1] for r in rows] == isum
-
-
-def _drive_with_revokes(op, pages, revoke):
-    """T/operator/OperatorAssertion.java:84-156 (toPagesPartial + finishOperator with revokeMemory): before every addInput and after
-    every getOutput the driver revokes whatever the operator holds as revocable memory"""
-    out = []
-
-    def revoke_all():
-        if revoke and op.revocableMemoryBytes() > 0:
-            op.startMemoryRevoke()
-            op.finishMemoryRevoke()
-    for pg in pages:
-        revoke_all()
-        assert op.needsInput()
-        op.addInput(pg)
-        o = op.getOutput()
-        assert o is None
-    op.finish()
-    for _ in range(1000):
-        if op.isFinished():
-            break
-        o = op.getOutput()
-        if o is not None:
-            out.append(o.to_host())
-            o.release()
-        revoke_all()
-    assert op.isFinished() and not op.needsInput()
-    return [r for p in out for r in p.rows()]
 
 
 @pytest.mark.parametrize("hash_enabled,spill_enabled,revoke", [(True, True, True), (True, True, False), (False, False, False), (False, True, True), (False, True, False)])
