@@ -23,6 +23,7 @@
  *   - tgpu_lookup_outer_*        <-> M/operator/LookupOuterOperator.java:32-235, OuterLookupSource.java:146-190
  *   - tgpu_merge_pages_*         <-> M/operator/project/MergePages.java:64-190
  *   - tgpu_dynamic_filter_source_* <-> M/operator/DynamicFilterSourceOperator.java:74-425
+ *   - tgpu_set_builder_* / tgpu_hash_semi_join_* <-> M/operator/SetBuilderOperator.java:39-233, HashSemiJoinOperator.java:44-218, ChannelSet.java:62-108
  *   - tgpu_serialize_page / tgpu_deserialize_page <-> M/execution/buffer/PagesSerde.java:64-160, PagesSerdeUtil.java:45-71,
  *                                    S/block/{LongArray,IntArray,ByteArray,VariableWidth,RunLength,Dictionary}BlockEncoding.java, EncoderUtil.java:33-118
  *   - tgpu_exchange_*            <-> M/operator/PartitionedOutputOperator.java:406-476 -> M/operator/ExchangeOperator.java (the hop between
@@ -99,6 +100,7 @@ typedef struct tgpu_context tgpu_context;
 typedef struct tgpu_operator_factory tgpu_operator_factory;
 typedef struct tgpu_operator tgpu_operator;
 typedef struct tgpu_lookup_source_factory tgpu_lookup_source_factory;
+typedef struct tgpu_set_supplier tgpu_set_supplier;            /* SetBuilderOperator.SetSupplier */
 typedef struct tgpu_group_by_hash tgpu_group_by_hash;
 typedef struct tgpu_output_page tgpu_output_page;
 
@@ -297,6 +299,28 @@ int32_t tgpu_filter_project_lookup_join_factory_create(tgpu_context *ctx, int32_
  * nulls followed by the build output channels. */
 int32_t tgpu_lookup_outer_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_lookup_source_factory *bridge, int32_t probe_output_type_count,
                                          const int32_t *probe_output_types, tgpu_operator_factory **out);
+
+/* ---- semi join (LocalExecutionPlanner.visitSemiJoin, M/sql/planner/LocalExecutionPlanner.java:2326-2412): x IN (SELECT ...) ---- */
+/* SetBuilderOperatorFactory (M/operator/SetBuilderOperator.java:92-135) + its SetSupplier (:39-90): a sink on the build pipeline that
+ * collects channel `set_channel` of every page into a set in HBM (ChannelSet.java:62-108: null keys are inserted too; containsNull = a null
+ * key was seen) and publishes it to every probe operator at finish().  hash_channel (-1 = none) is accepted and not read: the set hashes
+ * its keys itself.  expected_positions is a sizing hint only.  The factory cannot be duplicated (TGPU_ERR_NOT_SUPPORTED). */
+int32_t tgpu_set_builder_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                        int32_t set_channel, int32_t hash_channel /* -1 = none */, int32_t expected_positions,
+                                        tgpu_set_supplier **supplier_out, tgpu_operator_factory **out);
+/* HashSemiJoinOperator.HashSemiJoinOperatorFactory (M/operator/HashSemiJoinOperator.java:44-118, :166-218): output page = the input
+ * page's channels unchanged (a probe hash channel included), then one BOOLEAN channel; one output page per input page, rows in input
+ * order.  Per row: null probe key -> false if the set is empty, else null; key in the set -> true; else null if the set contains a null,
+ * else false.  Membership is GroupByHash.contains (ChannelSet.java:70-78): DOUBLE NaN / -0.0 as the group-by hash, VARCHAR bytewise.
+ * The probe key type must be the set's type (TGPU_ERR_INVALID_ARGUMENT otherwise).  Like the LookupJoinOperator: is_blocked = 1 and
+ * needs_input = 0 until the set builder has finished; a probe finished before that ends without output.  duplicate() shares the set. */
+int32_t tgpu_hash_semi_join_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_set_supplier *supplier,
+                                           int32_t probe_type_count, const int32_t *probe_types, int32_t probe_join_channel,
+                                           int32_t probe_hash_channel /* -1 = none */, tgpu_operator_factory **out);
+/* valid once the builder finished: distinct keys (a null counts, as in ChannelSet.size), containsNull, HBM bytes, layout (0 bitmap,
+ * 1 hash, 2 generic) */
+int32_t tgpu_set_supplier_stats(tgpu_set_supplier *supplier, int64_t *size, int32_t *contains_null, int64_t *bytes, int32_t *layout);
+void tgpu_set_supplier_destroy(tgpu_set_supplier *supplier);
 
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of

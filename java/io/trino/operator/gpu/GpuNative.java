@@ -109,6 +109,12 @@ public final class GpuNative
             double[] doubleValues, byte[] stringPool, int filterRoot, int[] projectionRoots, int[] probeJoinChannels, int probeHashChannel, int[] probeOutputChannels, int joinType);
     public static native long createLookupOuterFactory(long context, int operatorId, long bridge, int[] probeOutputTypes);
     public static native void destroyBridge(long bridge);
+    /** returns {factory, supplier}: SetBuilderOperatorFactory and its SetSupplier (tgpu_set_builder_factory_create) */
+    public static native long[] createSetBuilderFactory(long context, int operatorId, int[] types, int setChannel, int hashChannel, int expectedPositions);
+    public static native long createHashSemiJoinFactory(long context, int operatorId, long supplier, int[] probeTypes, int probeJoinChannel, int probeHashChannel);
+    /** out = {distinct keys (a null counted), containsNull 0 / 1, HBM bytes, layout} of the built set */
+    public static native void setSupplierStats(long supplier, long[] sizeContainsNullBytesLayout);
+    public static native void destroySetSupplier(long supplier);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);
     public static native long createOrderByFactory(long context, int operatorId, int[] types, int[] outputChannels, int expectedPositions, int[] sortChannels, int[] sortOrders);
     public static native long createMergePagesFactory(long context, int operatorId, int[] types, long minPageSizeInBytes, int minRowCount, long maxPageSizeInBytes);

@@ -293,6 +293,64 @@ public final class GpuOperatorFactories
         return new GpuOperatorFactory(operatorId, planNodeId, "GpuLookupOuterOperator", List.of(), poller, GpuNative.createLookupOuterFactory(context, operatorId, build.bridge, codes));
     }
 
+    /** the semi join's SetSupplier handle (tgpu_set_supplier*) between the set builder and the probes (operator/SetBuilderOperator.java:39-90) */
+    public static final class SetBuild
+    {
+        public final OperatorFactory factory;
+        public final long supplier;
+
+        SetBuild(OperatorFactory factory, long supplier)
+        {
+            this.factory = factory;
+            this.supplier = supplier;
+        }
+
+        /** {distinct keys (a null counted, ChannelSet.size), containsNull 0 / 1, HBM bytes, layout 0 bitmap | 1 hash | 2 generic} of the built set */
+        public long[] stats()
+        {
+            long[] out = new long[4];
+            GpuNative.setSupplierStats(supplier, out);
+            return out;
+        }
+
+        public void destroy()
+        {
+            GpuNative.destroySetSupplier(supplier);
+        }
+    }
+
+    /**
+     * SetBuilderOperatorFactory (operator/SetBuilderOperator.java:92-135; LocalExecutionPlanner.visitSemiJoin :2326-2412).  A DynamicFilterSourceOperator
+     * in front of it is {@link #dynamicFilterSource}.
+     */
+    public Optional<SetBuild> setBuilder(int operatorId, PlanNodeId planNodeId, List<Type> types, int setChannel, OptionalInt hashChannel, int expectedPositions)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(types);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long[] handles = GpuNative.createSetBuilderFactory(context, operatorId, codes, setChannel, hashChannel.orElse(-1), expectedPositions);
+        return Optional.of(new SetBuild(new GpuSetBuilderOperatorFactory(operatorId, planNodeId, types, poller, handles[0], handles[1]), handles[1]));
+    }
+
+    /** HashSemiJoinOperator.HashSemiJoinOperatorFactory (operator/HashSemiJoinOperator.java:44-118): the probe page + one BOOLEAN channel */
+    public Optional<OperatorFactory> hashSemiJoin(int operatorId, PlanNodeId planNodeId, SetBuild build, List<Type> probeTypes, int probeJoinChannel,
+            OptionalInt probeHashChannel)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(probeTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createHashSemiJoinFactory(context, operatorId, build.supplier, codes, probeJoinChannel, probeHashChannel.orElse(-1));
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuHashSemiJoinOperator", probeTypes, poller, factory));
+    }
+
     /** TopNOperator.createOperatorFactory (operator/TopNOperator.java:47-62; LocalExecutionPlanner.visitTopN) */
     public Optional<OperatorFactory> topN(int operatorId, PlanNodeId planNodeId, List<Type> types, long n, List<Integer> sortChannels, List<SortOrder> sortOrders)
     {

@@ -537,6 +537,55 @@ JFN(jlong, createLookupOuterFactory)(JNIEnv *env, jclass c, jlong ctx, jint oper
 
 JFN(void, destroyBridge)(JNIEnv *env, jclass c, jlong bridge) { UNUSED(env); UNUSED(c); tgpu_lookup_source_factory_destroy(H(tgpu_lookup_source_factory, bridge)); }
 
+/* SetBuilderOperatorFactory + its SetSupplier (operator/SetBuilderOperator.java:39-135): returns {factory, supplier}.  Channels are checked
+ * here, in front of the library: setChannel in [0, types), hashChannel -1 or in [0, types), a non-empty type array */
+JFN(jlongArray, createSetBuilderFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jint setChannel, jint hashChannel, jint expectedPositions)
+{
+    UNUSED(c);
+    const jsize n = types ? (*env)->GetArrayLength(env, types) : 0;
+    if (n <= 0 || setChannel < 0 || setChannel >= n || hashChannel < -1 || hashChannel >= n) {
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, "set builder: empty type array, or set / hash channel out of range");
+        return NULL;
+    }
+    ints t = ints_get(env, types);
+    tgpu_set_supplier *supplier = NULL;
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = tgpu_set_builder_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, setChannel, hashChannel, expectedPositions, &supplier, &f);
+    ints_release(env, &t);
+    return two_handles(env, rc, f, supplier);
+}
+
+/* HashSemiJoinOperatorFactory (operator/HashSemiJoinOperator.java:44-118): the probe page + one BOOLEAN channel */
+JFN(jlong, createHashSemiJoinFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jlong supplier, jintArray probeTypes, jint probeJoinChannel, jint probeHashChannel)
+{
+    UNUSED(c);
+    const jsize n = probeTypes ? (*env)->GetArrayLength(env, probeTypes) : 0;
+    if (n <= 0 || probeJoinChannel < 0 || probeJoinChannel >= n || probeHashChannel < -1 || probeHashChannel >= n) {
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, "semi join: empty probe type array, or join / hash channel out of range");
+        return 0;
+    }
+    ints t = ints_get(env, probeTypes);
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = tgpu_hash_semi_join_factory_create(H(tgpu_context, ctx), operatorId, H(tgpu_set_supplier, supplier), t.n, (const int32_t *)t.p, probeJoinChannel,
+                                                    probeHashChannel, &f);
+    ints_release(env, &t);
+    return factory_result(env, rc, f);
+}
+
+/* out = {distinct keys (a null counted), containsNull, HBM bytes, layout} of the built set */
+JFN(void, setSupplierStats)(JNIEnv *env, jclass c, jlong supplier, jlongArray out)
+{
+    UNUSED(c);
+    int64_t size = 0, bytes = 0;
+    int32_t contains_null = 0, layout = 0;
+    int32_t rc = tgpu_set_supplier_stats(H(tgpu_set_supplier, supplier), &size, &contains_null, &bytes, &layout);
+    if (rc < 0) { throw_native(env, rc); return; }
+    jlong v[4] = {size, contains_null, bytes, layout};
+    set_longs(env, out, v, 4);
+}
+
+JFN(void, destroySetSupplier)(JNIEnv *env, jclass c, jlong supplier) { UNUSED(env); UNUSED(c); tgpu_set_supplier_destroy(H(tgpu_set_supplier, supplier)); }
+
 /* TopNOperator.createOperatorFactory (M/operator/TopNOperator.java:47-62); sortOrders: tgpu_sort_order = SortOrder's ordinal (S/connector/SortOrder.java:18-21) */
 JFN(jlong, createTopNFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong n, jintArray sortChannels, jintArray sortOrders)
 {

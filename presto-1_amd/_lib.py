@@ -172,6 +172,10 @@ SYMBOLS = {
     "tgpu_lookup_outer_factory_create": (i32, [vp, i32, vp, i32, P(i32), P(vp)]),
     "tgpu_dynamic_filter_source_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, i64, i32, P(vp)]),
     "tgpu_dynamic_filter_source_result": (i32, [vp, i32, P(i32), P(vp), P(i64), P(i64)]),
+    "tgpu_set_builder_factory_create": (i32, [vp, i32, i32, P(i32), i32, i32, i32, P(vp), P(vp)]),
+    "tgpu_hash_semi_join_factory_create": (i32, [vp, i32, vp, i32, P(i32), i32, i32, P(vp)]),
+    "tgpu_set_supplier_stats": (i32, [vp, P(i64), P(i32), P(i64), P(i32)]),
+    "tgpu_set_supplier_destroy": (None, [vp]),
     "tgpu_merge_pages_factory_create": (i32, [vp, i32, i32, P(i32), i64, i32, i64, P(vp)]),
     "tgpu_partitioned_output_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, i32, i32, i32, i32, P(vp)]),
     "tgpu_partitioned_output_poll": (i32, [vp, P(i32), P(vp)]),

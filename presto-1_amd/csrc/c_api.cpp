@@ -61,6 +61,7 @@ inline Context *ctx_of(const tgpu_operator *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_operator_factory *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_lookup_source_factory *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_group_by_hash *h) { return h ? h->ctx : nullptr; }
+inline Context *ctx_of(const tgpu_set_supplier *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_output_page *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_exchange *h) { return h ? h->ctx : nullptr; }
 
@@ -1190,6 +1191,63 @@ int32_t tgpu_dynamic_filter_source_result(tgpu_operator *op, int32_t filter_chan
         dynamic_filter_result(op->op.get(), filter_channel, kind, &page, min, max);
         if (page) *values = release_output(std::move(page));
     });
+}
+
+int32_t tgpu_set_builder_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t set_channel, int32_t hash_channel,
+                                        int32_t expected_positions, tgpu_set_supplier **supplier_out, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && supplier_out && out, "null argument");
+        (void)expected_positions;   // a sizing hint of the reference's ChannelSetBuilder; the set is sized from the rows it receives
+        std::vector<int32_t> t = vec(types, type_count);
+        TG_CHECK_ARG(set_channel >= 0 && set_channel < type_count, "set channel out of range");
+        TG_CHECK_ARG(valid_type(t[(size_t)set_channel]), "unknown type");
+        auto supplier = std::make_unique<tgpu_set_supplier>();
+        supplier->supplier = std::make_shared<SetSupplier>(t[(size_t)set_channel]);
+        auto f = std::make_unique<tgpu_operator_factory>();
+        f->f = std::make_unique<SetBuilderOperatorFactory>(ctx->ctx.get(), operator_id, std::move(t), set_channel, hash_channel, supplier->supplier);
+        supplier->ctx = ctx->ctx.get();
+        retain(supplier->ctx);
+        *supplier_out = supplier.release();
+        f->ctx = ctx->ctx.get();
+        retain(f->ctx);
+        *out = f.release();
+    });
+}
+
+int32_t tgpu_hash_semi_join_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_set_supplier *supplier, int32_t probe_type_count, const int32_t *probe_types,
+                                           int32_t probe_join_channel, int32_t probe_hash_channel, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && supplier && out, "null argument");
+        auto f = std::make_unique<tgpu_operator_factory>();
+        f->f = std::make_unique<HashSemiJoinOperatorFactory>(ctx->ctx.get(), operator_id, supplier->supplier, vec(probe_types, probe_type_count), probe_join_channel,
+                                                             probe_hash_channel);
+        f->ctx = ctx->ctx.get();
+        retain(f->ctx);
+        *out = f.release();
+    });
+}
+
+int32_t tgpu_set_supplier_stats(tgpu_set_supplier *supplier, int64_t *size, int32_t *contains_null, int64_t *bytes, int32_t *layout)
+{
+    return guard_on(ctx_of(supplier), [&] {
+        TG_CHECK_ARG(supplier != nullptr, "supplier is null");
+        std::shared_ptr<const SemiSetGpu> s = supplier->supplier->set();
+        TG_CHECK_STATE(s != nullptr, "ChannelSet has not been built yet");
+        if (size) *size = s->size();
+        if (contains_null) *contains_null = s->contains_null() ? 1 : 0;
+        if (bytes) *bytes = s->estimated_size();
+        if (layout) *layout = s->layout();
+    });
+}
+
+void tgpu_set_supplier_destroy(tgpu_set_supplier *supplier)
+{
+    if (!supplier) return;
+    Context *c = supplier->ctx;
+    delete supplier;
+    if (c) drop(c);
 }
 
 int32_t tgpu_merge_pages_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t min_page_size_in_bytes,

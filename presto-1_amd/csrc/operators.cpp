@@ -2144,6 +2144,167 @@ void dynamic_filter_result(Operator *op, int32_t k, int32_t *kind, std::unique_p
     p->result(k, kind, values, min, max);
 }
 
+// =====================================================================================================================
+// SetBuilderOperator (M/operator/SetBuilderOperator.java:137-233): a sink.  The key channel of every page goes into the set (semijoin.h);
+// finish() builds it and publishes it to the probes through the SetSupplier.  A precomputed hash channel is accepted and not read: the
+// set hashes its keys itself (observable behaviour is the same: ChannelSet.contains compares keys).
+// =====================================================================================================================
+class SetBuilderOperator : public Operator {
+public:
+    SetBuilderOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, int32_t set_channel, std::shared_ptr<SetSupplier> supplier)
+        : Operator(ctx, id), types_(types), set_channel_(set_channel), supplier_(std::move(supplier)),
+          set_(std::make_shared<SemiSetGpu>(ctx, types[(size_t)set_channel]))
+    {
+    }
+
+    bool needs_input() override { return !finished_; }   // :204-207
+    void add_input(const tgpu_page *page) override { add(ingest_page(ctx_, page)); }
+    void add_input_owned(const DevicePage &page) override { add(page); }
+    std::unique_ptr<OutputPage> get_output() override { return nullptr; }   // :224-228
+
+    void finish() override   // :180-196
+    {
+        if (finished_) return;
+        set_->finish();
+        supplier_->publish(set_);
+        finished_ = true;
+    }
+    bool is_finished() override { return finished_; }
+    // what the builder holds until it is closed: the collected keys, then the set (the probes share it through the supplier)
+    int64_t memory_bytes() override { return closed_ || !set_ ? 0 : set_->estimated_size(); }
+    void close() override
+    {
+        closed_ = true;
+        set_.reset();
+    }
+
+private:
+    void add(const DevicePage &in)   // :209-222
+    {
+        TG_CHECK_STATE(!finished_, "Operator is already finishing");
+        TG_CHECK_ARG(in.cols.size() == types_.size(), "page channel count does not match the operator's types");
+        for (size_t i = 0; i < types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == types_[i], "page channel type does not match the operator's types");
+        set_->add_keys(in.cols[(size_t)set_channel_]);
+    }
+
+    std::vector<int32_t> types_;
+    int32_t set_channel_;
+    std::shared_ptr<SetSupplier> supplier_;
+    std::shared_ptr<SemiSetGpu> set_;
+    bool finished_ = false, closed_ = false;
+};
+
+SetBuilderOperatorFactory::SetBuilderOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int32_t set_channel, int32_t hash_channel,
+                                                     std::shared_ptr<SetSupplier> supplier)
+    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), set_channel_(set_channel), supplier_(std::move(supplier))
+{
+    TG_CHECK_ARG(!types_.empty(), "the set builder needs at least one channel");
+    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown type");
+    TG_CHECK_ARG(set_channel_ >= 0 && set_channel_ < (int)types_.size(), "set channel out of range");
+    TG_CHECK_ARG(hash_channel >= -1 && hash_channel < (int)types_.size(), "hash channel out of range");
+    TG_CHECK_ARG(supplier_->type() == types_[(size_t)set_channel_], "the supplier's type is not the set channel's type");
+}
+
+std::unique_ptr<Operator> SetBuilderOperatorFactory::create_operator()
+{
+    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    return std::make_unique<SetBuilderOperator>(ctx_, operator_id_, types_, set_channel_, supplier_);
+}
+
+// =====================================================================================================================
+// HashSemiJoinOperator (M/operator/HashSemiJoinOperator.java:166-218): the input page's channels unchanged, then one BOOLEAN channel;
+// one output page per input page.  Blocked, and taking no input, until the set is published -- as this library's LookupJoinOperator; a
+// probe finished before that ends without output.  A DICTIONARY / RLE key block is probed once per dictionary entry and the results are
+// gathered through its ids.
+// =====================================================================================================================
+class HashSemiJoinOperator : public Operator {
+public:
+    HashSemiJoinOperator(Context *ctx, int32_t id, std::shared_ptr<SetSupplier> supplier, const std::vector<int32_t> &probe_types, int32_t probe_join_channel)
+        : Operator(ctx, id), supplier_(std::move(supplier)), probe_types_(probe_types), channel_(probe_join_channel)
+    {
+    }
+
+    bool is_blocked() override { return !finishing_ && !supplier_->set(); }
+    bool needs_input() override { return !finishing_ && !pending_ && !is_blocked(); }
+
+    void add_input(const tgpu_page *page) override
+    {
+        std::shared_ptr<const SemiSetGpu> set = ready();
+        TG_CHECK_ARG(page != nullptr, "page is null");
+        TG_CHECK_ARG(page->channel_count == (int32_t)probe_types_.size(), "page channel count does not match the operator's types");
+        const tgpu_block &kb = page->blocks[channel_];
+        DeviceColumn verdict;
+        bool have_verdict = false;
+        if (kb.encoding != TGPU_FLAT && kb.dictionary != nullptr && kb.dictionary->encoding == TGPU_FLAT) {
+            TG_CHECK_ARG(kb.type == probe_types_[(size_t)channel_], "page channel type does not match the operator's types");
+            TG_CHECK_ARG(kb.position_count == page->position_count, "block position count differs from the page's");
+            DeviceColumn dict;
+            BufferPtr ids;
+            ingest_dictionary(ctx_, &kb, dict, ids);
+            verdict = k::gather_column(ctx_, set->probe(dict), ids->as<int32_t>(), page->position_count, false);
+            have_verdict = true;
+        }
+        DevicePage in = ingest_page(ctx_, page);
+        emit(*set, std::move(in), have_verdict ? &verdict : nullptr);
+    }
+    void add_input_owned(const DevicePage &page) override { emit(*ready(), DevicePage(page), nullptr); }
+
+    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    void finish() override { finishing_ = true; }
+    bool is_finished() override { return finishing_ && !pending_; }
+    int64_t memory_bytes() override { return pending_ ? pending_->page.size_in_bytes() : 0; }
+
+private:
+    std::shared_ptr<const SemiSetGpu> ready()
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        TG_CHECK_STATE(!pending_, "Operator still has pending output");
+        std::shared_ptr<const SemiSetGpu> set = supplier_->set();
+        TG_CHECK_STATE(set != nullptr, "ChannelSet has not been built yet");
+        return set;
+    }
+
+    void emit(const SemiSetGpu &set, DevicePage in, const DeviceColumn *verdict)
+    {
+        TG_CHECK_ARG(in.cols.size() == probe_types_.size(), "page channel count does not match the operator's types");
+        for (size_t i = 0; i < probe_types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == probe_types_[i], "page channel type does not match the operator's types");
+        DeviceColumn out = verdict ? *verdict : set.probe(in.cols[(size_t)channel_]);
+        // the page passes through: channels that borrow the caller's device memory get buffers of their own (the output outlives the call)
+        own_borrowed_columns(ctx_, in);
+        in.cols.push_back(std::move(out));
+        pending_ = wrap(std::move(in));
+    }
+
+    std::shared_ptr<SetSupplier> supplier_;
+    std::vector<int32_t> probe_types_;
+    int32_t channel_;
+    std::unique_ptr<OutputPage> pending_;
+    bool finishing_ = false;
+};
+
+HashSemiJoinOperatorFactory::HashSemiJoinOperatorFactory(Context *ctx, int32_t operator_id, std::shared_ptr<SetSupplier> supplier, std::vector<int32_t> probe_types,
+                                                         int32_t probe_join_channel, int32_t probe_hash_channel)
+    : ctx_(ctx), operator_id_(operator_id), supplier_(std::move(supplier)), probe_types_(std::move(probe_types)), probe_join_channel_(probe_join_channel)
+{
+    TG_CHECK_ARG(!probe_types_.empty(), "the semi join probe needs at least one channel");
+    for (int32_t t : probe_types_) TG_CHECK_ARG(valid_type(t), "unknown type");
+    TG_CHECK_ARG(probe_join_channel_ >= 0 && probe_join_channel_ < (int)probe_types_.size(), "probe join channel out of range");
+    TG_CHECK_ARG(probe_hash_channel >= -1 && probe_hash_channel < (int)probe_types_.size(), "probe hash channel out of range");
+    TG_CHECK_ARG(probe_types_[(size_t)probe_join_channel_] == supplier_->type(), "the probe key type is not the set's type");
+}
+
+std::unique_ptr<Operator> HashSemiJoinOperatorFactory::create_operator()
+{
+    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    return std::make_unique<HashSemiJoinOperator>(ctx_, operator_id_, supplier_, probe_types_, probe_join_channel_);
+}
+
+std::unique_ptr<OperatorFactory> HashSemiJoinOperatorFactory::duplicate()
+{
+    // shares the supplier (HashSemiJoinOperator.java:115-118)
+    return std::make_unique<HashSemiJoinOperatorFactory>(ctx_, operator_id_, supplier_, probe_types_, probe_join_channel_, -1);
+}
+
 void Operator::add_input_owned(const DevicePage &page)
 {
     std::vector<tgpu_block> blocks(page.cols.size());

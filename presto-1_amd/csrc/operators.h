@@ -10,6 +10,7 @@
 #include "groupby.h"
 #include "jit.h"
 #include "join.h"
+#include "semijoin.h"
 #include "topn.h"
 
 namespace tgpu {
@@ -333,6 +334,64 @@ private:
     std::shared_ptr<FusedAggGpu> fused_;
 };
 
+// ---- semi join bridge: SetBuilderOperator.SetSupplier (M/operator/SetBuilderOperator.java:39-90) ------------------------------------
+// Shared by the set builder and every probe operator (different drivers, i.e. threads): guarded by one mutex.  The published set is
+// immutable and read by all probes.
+class SetSupplier {
+public:
+    explicit SetSupplier(int32_t type) : type_(type) {}
+    int32_t type() const { return type_; }
+    std::shared_ptr<const SemiSetGpu> set() const
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        return set_;
+    }
+    void publish(std::shared_ptr<const SemiSetGpu> s)   // setChannelSet (:59-63): checkState(wasSet, "ChannelSet already set")
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        TG_CHECK_STATE(!set_, "ChannelSet already set");
+        set_ = std::move(s);
+    }
+
+private:
+    const int32_t type_;
+    mutable std::mutex mu_;
+    std::shared_ptr<const SemiSetGpu> set_;
+};
+
+// ---- SetBuilderOperator (M/operator/SetBuilderOperator.java:92-233) ----------------------------------------------------------------
+class SetBuilderOperatorFactory : public OperatorFactory {
+public:
+    SetBuilderOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int32_t set_channel, int32_t hash_channel,
+                              std::shared_ptr<SetSupplier> supplier);
+    std::unique_ptr<Operator> create_operator() override;
+    // duplicate(): the base class's NOT_SUPPORTED.  The reference's duplicate builds a set of its own behind a new SetSupplier (:120-123),
+    // which no probe factory created through the C ABI could reach.
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::vector<int32_t> types_;
+    int32_t set_channel_;
+    std::shared_ptr<SetSupplier> supplier_;
+};
+
+// ---- HashSemiJoinOperator (M/operator/HashSemiJoinOperator.java:44-218) -------------------------------------------------------------
+class HashSemiJoinOperatorFactory : public OperatorFactory {
+public:
+    HashSemiJoinOperatorFactory(Context *ctx, int32_t operator_id, std::shared_ptr<SetSupplier> supplier, std::vector<int32_t> probe_types,
+                                int32_t probe_join_channel, int32_t probe_hash_channel);
+    std::unique_ptr<Operator> create_operator() override;
+    std::unique_ptr<OperatorFactory> duplicate() override;
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::shared_ptr<SetSupplier> supplier_;
+    std::vector<int32_t> probe_types_;
+    int32_t probe_join_channel_;
+};
+
 // ---- TopNOperator (M/operator/TopNOperator.java:47-62,135-225) ----------------------------------------------------------
 class TopNOperatorFactory : public OperatorFactory {
 public:
@@ -438,6 +497,10 @@ struct tgpu_operator {
 };
 struct tgpu_lookup_source_factory {
     std::shared_ptr<tgpu::LookupSourceFactory> bridge;
+    tgpu::Context *ctx = nullptr;
+};
+struct tgpu_set_supplier {
+    std::shared_ptr<tgpu::SetSupplier> supplier;
     tgpu::Context *ctx = nullptr;
 };
 struct tgpu_group_by_hash {

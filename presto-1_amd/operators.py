@@ -717,6 +717,59 @@ class DynamicFilterSourceOperatorFactory(OperatorFactory):
         return DynamicFilterSourceOperator(h)
 
 
+SET_BITMAP, SET_HASH, SET_GENERIC = 0, 1, 2   # tgpu_set_supplier_stats layouts
+
+
+class SetSupplier:
+    """SetBuilderOperator.SetSupplier (M/operator/SetBuilderOperator.java:39-90): the bridge from the set builder to the semi join probes."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def stats(self):
+        """valid once the builder finished: size (distinct keys, a null counted: ChannelSet.size), contains_null, HBM bytes, layout"""
+        size, cn, nbytes, layout = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
+        _lib.check(_lib.lib().tgpu_set_supplier_stats(self.handle, C.byref(size), C.byref(cn), C.byref(nbytes), C.byref(layout)))
+        return dict(size=size.value, contains_null=bool(cn.value), bytes=nbytes.value, layout=layout.value)
+
+    def close(self):
+        if self.handle:
+            _lib.lib().tgpu_set_supplier_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # a constructor that failed before `handle` existed, or interpreter shutdown
+            pass
+
+
+class SetBuilderOperatorFactory(OperatorFactory):
+    """SetBuilderOperator.SetBuilderOperatorFactory (M/operator/SetBuilderOperator.java:92-135).  `set_supplier` is the bridge to hand
+    to the HashSemiJoinOperatorFactory."""
+
+    def __init__(self, ctx: Context, operator_id, types, set_channel, hash_channel=-1, expected_positions=10_000):
+        t, nt = _i32(types)
+        sup, h = C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().tgpu_set_builder_factory_create(ctx.handle, operator_id, nt, t, int(set_channel), int(hash_channel), int(expected_positions),
+                                                              C.byref(sup), C.byref(h)))
+        super().__init__(h)
+        self.set_supplier = SetSupplier(sup)
+
+
+class HashSemiJoinOperatorFactory(OperatorFactory):
+    """HashSemiJoinOperator.HashSemiJoinOperatorFactory (M/operator/HashSemiJoinOperator.java:44-118): the probe page plus one BOOLEAN
+    channel, `probe_join_channel` IN the set."""
+
+    def __init__(self, ctx: Context, operator_id, set_supplier: SetSupplier, probe_types, probe_join_channel, probe_hash_channel=-1):
+        t, nt = _i32(probe_types)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_hash_semi_join_factory_create(ctx.handle, operator_id, set_supplier.handle, nt, t, int(probe_join_channel),
+                                                                 int(probe_hash_channel), C.byref(h)))
+        super().__init__(h)
+        self._supplier = set_supplier
+
+
 class MergePagesOperatorFactory(OperatorFactory):
     """MergePages.mergePages (M/operator/project/MergePages.java:64-96) as an operator: small pages are coalesced in HBM, big ones pass through"""
 
