@@ -35,8 +35,15 @@
  * handles are independent, also when they belong to one context (their kernels then share its stream and execute in issue
  * order; the context serialises its staging buffers; the per-kernel profile assumes a single driver thread); a built lookup
  * source is immutable and shared read-only by probe operators (outer joins mark visited build positions with idempotent stores).
- * Ownership rule: input buffers are only read during the call (the library copies/uploads what it keeps);
- * output pages are owned by the library until tgpu_output_page_release.
+ * Ownership rule: input buffers are only read during the call (the library copies/uploads what it keeps), with one exception: a
+ * TGPU_DEVICE block whose arrays all lie inside live buffers of the SAME context (the blocks of a tgpu_output_page, or regions of
+ * them) is recognised at ingest and shares those buffers' owners -- an operator that keeps its rows keeps a reference, not a copy,
+ * and the memory outlives tgpu_output_page_release for as long as that reference does.  Library buffers are immutable once they
+ * have left in an output page: nobody, the caller included, writes them.  Device memory of the embedding or of another context is
+ * never recognised and keeps the copy (or, under tgpu_context_set_device_input_stable, the promise below).  A recognised block
+ * saves copies only: the operators that defer their launches to a later call (fused aggregation, fused join) do that for pages of
+ * TGPU_DEVICE blocks under the promise alone.
+ * Output pages are owned by the library until tgpu_output_page_release.
  */
 #ifndef TGPU_H
 #define TGPU_H
@@ -414,8 +421,9 @@ int32_t tgpu_operator_needs_input(tgpu_operator *op);
  * TGPU_DEVICE arrays are read by kernels on the context's stream, some of which may still be queued when the call returns (the
  * aggregation's accumulate launch is enqueued behind its group-by probe and not waited for): the caller may overwrite or free them in
  * STREAM ORDER -- by work on that stream, hipFreeAsync on it, hipFree (which synchronises), or after tgpu_context_synchronize -- the
- * rule of any stream-ordered device buffer.  An operator that keeps rows beyond the call copies them or shares the owner
- * (tgpu_operator_add_input_output_page). */
+ * rule of any stream-ordered device buffer.  An operator that keeps rows beyond the call copies them or shares the owner: the owner
+ * of a page handed over with tgpu_operator_add_input_output_page, and the owners of TGPU_DEVICE blocks that lie inside live buffers of
+ * this context (the blocks of an output page; see "Ownership rule" above) -- such blocks are never written by the caller. */
 int32_t tgpu_operator_add_input(tgpu_operator *op, const tgpu_page *page);
 /* *out = NULL when no page is available (Operator.getOutput() == null); returns TGPU_WOULD_BLOCK instead of TGPU_OK when, in addition,
  * the operator is blocked (a probe waiting for its build side, the outer operator waiting for the probes): the driver should park the

@@ -153,6 +153,14 @@ const char *tgpu_last_error(void) { return last_error().c_str(); }
 /* diagnostics: how many times entry points bound their thread to a context's device (tests) */
 long long tgpu_debug_bind_count(void) { return g_bind_count.load(); }
 const char *tgpu_version(void) { return "tgpu 0.1 (gfx950)"; }
+// Diagnostics for tests and kernel studies (not part of include/tgpu.h): the fused filter/project/probe launches prepared so far in this
+// process, by how the probe-side outputs reach pass 2 -- out[0] two-pass gather, out[1] full carry, out[2] partial carry
+int32_t tgpu_fused_probe_launch_counts(int64_t out[3])
+{
+    if (!out) return TGPU_ERR_INVALID_ARGUMENT;
+    tgpu::fused_probe_launch_counts(out);
+    return TGPU_OK;
+}
 
 int32_t tgpu_set_resource_dir(const char *dir)
 {

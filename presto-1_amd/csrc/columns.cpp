@@ -130,6 +130,20 @@ static DeviceColumn ingest_block_raw(Context *ctx, const tgpu_block *b)
             // (ingest_page batches the reads of all VARCHAR channels of a page into one round trip; see resolve_varchar_ends)
             c.pool_exact = n == 0;
         }
+        // A block that lies inside live buffers of this context (a column the library handed out in an output page, or a region of
+        // one) shares their owners: whoever retains the column keeps a reference instead of copying.  Only when EVERY array of the
+        // block finds its owner -- otherwise (the embedding's memory, another context's) it stays borrowed as a whole.  Library
+        // buffers are never rewritten once they have left in an output page (DESIGN.md §3 "Ownership").
+        if (n > 0 && c.values) {
+            BufferPtr v = ctx->owner_of(c.values, b->type == TGPU_VARCHAR ? 1 : (size_t)n * (size_t)type_width(b->type));   // (VARCHAR: the pool's extent is on the device)
+            BufferPtr nl = c.nulls ? ctx->owner_of(c.nulls, (size_t)n) : nullptr;
+            BufferPtr of = c.offsets ? ctx->owner_of(c.offsets, (size_t)(n + 1) * 4) : nullptr;
+            if (v && (!c.nulls || nl) && (!c.offsets || of)) {
+                c.values_buf = std::move(v);
+                c.nulls_buf = std::move(nl);
+                c.offsets_buf = std::move(of);
+            }
+        }
         return c;
     }
     const uint8_t *nulls = (b->nulls && any_set(b->nulls, n)) ? b->nulls : nullptr;

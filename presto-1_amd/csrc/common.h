@@ -104,6 +104,10 @@ public:
     BufferPtr alloc_zero(size_t bytes);
     void release(void *ptr, size_t capacity);
     size_t bytes_in_use() const { return in_use_; }
+    // The live buffer of THIS context that holds all of [ptr, ptr + bytes), or null (memory of the embedding, of another context, or a
+    // range that leaves its buffer).  A TGPU_DEVICE block that points into a column the library handed out thereby finds its owner
+    // again: the ingested column shares the buffer instead of borrowing it (columns.cpp, ingest_block).
+    BufferPtr owner_of(const void *ptr, size_t bytes);
 
     // pinned host staging (uploads / small readbacks)
     void *pinned(size_t bytes);
@@ -167,6 +171,7 @@ public:
     void profile_reset();
     void profile_begin(const char *name);
     void profile_end();
+    bool in_profile_scope() const { return cur_name_ != nullptr; }
     void profile_collect();
     std::string profile_json();
 
@@ -176,7 +181,10 @@ public:
     int64_t max_output_page_bytes() const { return max_out_bytes_; }
     int64_t max_output_page_rows() const { return max_out_rows_; }
     void set_max_output_page(int64_t bytes, int64_t rows) { max_out_bytes_ = bytes; max_out_rows_ = rows; }
-    // tgpu_context_set_device_input_stable: borrowed TGPU_DEVICE input stays valid and unchanged until the operator's NEXT call returns
+    // tgpu_context_set_device_input_stable: borrowed TGPU_DEVICE input (memory that is not a live buffer of this context, see owner_of)
+    // stays valid and unchanged until the operator's NEXT call returns.  Without it such input is valid during the call only and an
+    // operator that retains it copies it (include/tgpu.h "Memory ownership").  The operators that defer launches to a later call do so
+    // for pages of TGPU_DEVICE blocks under this promise alone, whether or not the blocks found owners (operators.cpp, page_is_retained)
     bool device_input_stable() const { return device_input_stable_; }
     void set_device_input_stable(bool on) { device_input_stable_ = on; }
     int double_sum_order() const { return double_sum_order_; }
@@ -203,6 +211,7 @@ private:
     bool device_input_stable_ = false;
     int64_t max_out_bytes_ = 0, max_out_rows_ = 0;
     std::multimap<size_t, void *> free_;
+    std::map<uintptr_t, std::weak_ptr<DeviceBuffer>> live_;   // base address -> owner of every buffer handed out and not yet released (under mu_)
     size_t in_use_ = 0, cached_ = 0;
     void *pinned_ = nullptr;
     size_t pinned_bytes_ = 0;

@@ -139,7 +139,30 @@ BufferPtr Context::alloc(size_t bytes)
     // never wrote sees the same garbage on every run (test mode: recycled buffers otherwise hold whatever their last user left)
     static const int poison = getenv("TGPU_POISON_ALLOC") ? atoi(getenv("TGPU_POISON_ALLOC")) & 0xff : -1;
     if (poison >= 0) HIP_CHECK(hipMemsetAsync(p, poison, cap, stream_));
-    return std::make_shared<DeviceBuffer>(this, p, bytes, cap);
+    BufferPtr b = std::make_shared<DeviceBuffer>(this, p, bytes, cap);
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        live_[(uintptr_t)p] = b;
+    }
+    return b;
+}
+
+BufferPtr Context::owner_of(const void *ptr, size_t bytes)
+{
+    if (!ptr) return nullptr;
+    const uintptr_t a = (uintptr_t)ptr;
+    BufferPtr b;   // (let go outside the lock: if it has become the last owner, its release takes mu_)
+    uintptr_t base = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = live_.upper_bound(a);
+        if (it == live_.begin()) return nullptr;
+        --it;
+        base = it->first;
+        b = it->second.lock();   // (expired: the last owner is letting go right now)
+    }
+    if (!b || a + bytes < a || a + bytes > base + b->bytes()) return nullptr;
+    return b;
 }
 
 BufferPtr Context::alloc_zero(size_t bytes)
@@ -152,6 +175,7 @@ BufferPtr Context::alloc_zero(size_t bytes)
 void Context::release(void *ptr, size_t capacity)
 {
     std::lock_guard<std::mutex> lk(mu_);
+    live_.erase((uintptr_t)ptr);
     in_use_ -= capacity;
     // keep at most 64 GiB cached; beyond that give memory back to the driver
     if (cached_ + capacity > (64ull << 30)) {

@@ -310,6 +310,8 @@ const char *ctype(int32_t t)
 struct Val {
     std::string v, n, len;  // value var, null-flag var, (VARCHAR) length var
     int32_t type;
+    bool is_const = false;  // a non-null VARCHAR constant: its bytes are known when the kernel is generated (cmp_expr)
+    std::string bytes;
 };
 
 struct Gen {
@@ -417,6 +419,8 @@ struct Gen {
                 if (nd.slen == 0) consts << "0";
                 consts << "};\n";
                 os << ind(d) << r.v << " = " << name << "; " << r.len << " = " << nd.slen << ";\n";
+                r.is_const = true;
+                r.bytes = pool.substr((size_t)nd.ival, (size_t)nd.slen);
                 break;
             }
             default: bad("bad constant type");
@@ -431,10 +435,46 @@ struct Gen {
 
     static bool is_cmp(int op) { return op >= TGPU_OP_EQUAL && op <= TGPU_OP_GREATER_THAN_OR_EQUAL; }
 
+    // x = 'constant': every piece lies inside [x, x + len) -- a last piece that is not a whole one overlaps its predecessor instead of
+    // reaching past the end (the last string of a pool ends where the allocation ends)
+    static std::string varchar_equals_const(const Val &x, const std::string &k)
+    {
+        const int L = (int)k.size();
+        auto imm = [&](int at, int w) {
+            unsigned long long v = 0;
+            for (int i = w - 1; i >= 0; i--) v = (v << 8) | (unsigned char)k[(size_t)(at + i)];
+            return std::to_string(v) + (w == 8 ? "ULL" : "U");
+        };
+        auto piece = [&](int at, int w) {
+            if (w == 1) return "(unsigned)" + x.v + "[" + std::to_string(at) + "] == " + imm(at, 1);
+            return std::string(w == 8 ? "tg_load8(" : "tg_load4(") + x.v + " + " + std::to_string(at) + ") == " + imm(at, w);
+        };
+        std::string e = "(" + x.len + " == " + std::to_string(L);
+        int i = 0;
+        for (; L - i >= 8; i += 8) e += " && " + piece(i, 8);
+        if (i < L) {
+            if (L >= 8) e += " && " + piece(L - 8, 8);
+            else if (L >= 4) {
+                e += " && " + piece(0, 4);
+                if (L > 4) e += " && " + piece(L - 4, 4);
+            }
+            else
+                for (; i < L; i++) e += " && " + piece(i, 1);
+        }
+        return e + ")";
+    }
+
     std::string cmp_expr(int32_t t, int op, const Val &a, const Val &b)
     {
         const char *sym = op == TGPU_OP_EQUAL ? "==" : op == TGPU_OP_NOT_EQUAL ? "!=" : op == TGPU_OP_LESS_THAN ? "<" :
                           op == TGPU_OP_LESS_THAN_OR_EQUAL ? "<=" : op == TGPU_OP_GREATER_THAN ? ">" : ">=";
+        if (t == TGPU_VARCHAR && (op == TGPU_OP_EQUAL || op == TGPU_OP_NOT_EQUAL)) {
+            // equality needs no order: the lengths first (strings of different length load no byte at all), then the bytes in 8- / 4-byte
+            // pieces; against a constant the pieces are immediates.  Ordering comparisons keep the byte loop of tg_strcmp.
+            const std::string neg = op == TGPU_OP_NOT_EQUAL ? "!" : "";
+            if (a.is_const != b.is_const) return neg + varchar_equals_const(a.is_const ? b : a, a.is_const ? a.bytes : b.bytes);
+            return neg + "(" + a.len + " == " + b.len + " && tg_bytes_equal(" + a.v + ", " + b.v + ", " + a.len + "))";
+        }
         if (t == TGPU_VARCHAR) return "(tg_strcmp(" + a.v + ", " + a.len + ", " + b.v + ", " + b.len + ") " + sym + " 0)";
         if (t == TGPU_BOOLEAN) return "((int)" + a.v + " " + sym + " (int)" + b.v + ")";
         return "(" + a.v + " " + sym + " " + b.v + ")";
@@ -662,6 +702,19 @@ __device__ inline int tg_strcmp(const unsigned char* a, int la, const unsigned c
   int m = la < lb ? la : lb;
   for (int i = 0; i < m; i++) { int d = (int)a[i] - (int)b[i]; if (d) return d; }
   return la - lb;
+}
+// pool bytes have no alignment: the wide pieces are unaligned loads (one global_load_dwordx2 / _dword each on gfx950)
+__device__ inline unsigned long long tg_load8(const unsigned char* p) { unsigned long long v; __builtin_memcpy(&v, p, 8); return v; }
+__device__ inline unsigned int tg_load4(const unsigned char* p) { unsigned int v; __builtin_memcpy(&v, p, 4); return v; }
+// n bytes of a and b are equal; reads [a, a + n) and [b, b + n) only: a last piece that is not a whole one overlaps its predecessor
+__device__ inline bool tg_bytes_equal(const unsigned char* a, const unsigned char* b, int n) {
+  if (n >= 8) {
+    for (int i = 0; i + 8 <= n; i += 8) if (tg_load8(a + i) != tg_load8(b + i)) return false;
+    return (n & 7) == 0 || tg_load8(a + n - 8) == tg_load8(b + n - 8);
+  }
+  if (n >= 4) return tg_load4(a) == tg_load4(b) && tg_load4(a + n - 4) == tg_load4(b + n - 4);
+  for (int i = 0; i < n; i++) if (a[i] != b[i]) return false;
+  return true;
 }
 // nearest integer, ties away from zero (java Math.round mirrored around zero = guava HALF_UP); NaN / inf pass through
 __device__ inline double tg_round_half_away(double x) {
@@ -930,6 +983,7 @@ std::shared_ptr<FusedProbeGpu> FusedProbeGpu::shared(const std::vector<int32_t> 
 {
     std::vector<int32_t> extra{join_channel};
     extra.insert(extra.end(), output_channels.begin(), output_channels.end());
+    if (const char *rule = getenv("TGPU_FJ_CARRY_RULE")) extra.push_back(-1 - atoi(rule));   // (kernel studies / tests: the generated source depends on it)
     return cached_object<FusedProbeGpu>(spec_key("fj", input_types, spec, extra),
                                         [&] { return std::make_shared<FusedProbeGpu>(input_types, spec, join_channel, output_channels); });
 }
@@ -1177,6 +1231,13 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
 #pragma unroll
   for (int s = 0; s < FJ_STRIPES; s++) { tg_zero_out(pov[s]); tg_zero_out(sov[s]); }
 #endif
+#if FJ_CARRY == 2
+  // PARTIAL carry: only outputs that the filter / key row already holds travel (no load, no TgRow field is added), and stage D keeps
+  // its place behind the loads -- the values of tile jD step aside (dov) before stage C takes the stage registers for tile jC
+  TgOut dov[FJ_STRIPES];
+#pragma unroll
+  for (int s = 0; s < FJ_STRIPES; s++) tg_zero_out(dov[s]);
+#endif
 #pragma unroll
   for (int s = 0; s < FJ_STRIPES; s++) {
     tg_zero_row(rw[s]);
@@ -1219,7 +1280,11 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
         emit[s] = head[s] >= 0 || ((J.outer & 1) && (sfl[s] & 2));   // PROBE_OUTER: every row that passed the filter (LookupJoinOperator.java:354-361)
       }
     }
-#if FJ_CARRY
+#if FJ_CARRY == 2
+#pragma unroll
+    for (int s = 0; s < FJ_STRIPES; s++) dov[s] = sov[s];
+#endif
+#if FJ_CARRY == 1
     // stage D, part 2 (carry variant: here, while the stage registers still hold tile jD's output values -- stage C below overwrites them)
     if (doD) {
       const long long tile = tile_of(jD);
@@ -1417,7 +1482,7 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-#if !FJ_CARRY
+#if FJ_CARRY != 1
     // stage D, part 2: compact the pairs of tile jD in input order and append them to the block's region
     if (doD) {
       const long long tile = tile_of(jD);
@@ -1445,6 +1510,9 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
           const unsigned int at = o + __builtin_amdgcn_mbcnt_hi((unsigned)(b[s] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b[s], 0u));
           pp[at] = (int)(row0 + s * 64);
           pb[at] = head[s];
+#if FJ_CARRY == 2
+          tg_carry_store(J, region + local + at, dov[s]);
+#endif
         }
         o += (unsigned int)__popcll(b[s]);
       }
@@ -1606,10 +1674,13 @@ __device__ __forceinline__ void fj_emit_body(const FjArgs& J, const unsigned int
           else ((unsigned char*)J.bcol[k].out_values)[dst + i] = pos < 0 ? (unsigned char)0 : ((const unsigned char*)J.bcol[k].values)[pos];
         }
       }
-#if FJ_CARRY
+#if FJ_CARRY == 1
       (void)row;
       tg_carry_move(J, src + i, dst + i);
 #else
+#if FJ_CARRY == 2
+      tg_carry_move(J, src + i, dst + i);   // the carried channels; tg_emit_outputs then covers the others only
+#endif
       tg_emit_outputs(AE, row, dst + i);
 #endif
     }
@@ -1667,10 +1738,22 @@ FusedProbeGpu::FusedProbeGpu(std::vector<int32_t> input_types, const tgpu_page_p
     };
     for (size_t ch = 0; ch < proj_roots_.size(); ch++)
         if ((int)ch != join_channel_ && can_raise(proj_roots_[ch])) supported_ = false;
+    key_can_raise_ = can_raise(proj_roots_[(size_t)join_channel_]);
     if (supported_) generate();
 }
 
 FusedProbeGpu::~FusedProbeGpu() {}
+
+// probe launches prepared so far in this process, by carry mode {two-pass gather, full carry, partial carry} (tgpu_fused_probe_launch_counts)
+static std::atomic<int64_t> g_fj_launches[3];
+// Which free channels the partial carry takes: 0 = every one, 1 = not the join key's.  1: Q3's lineitem launch has the 8-byte key as its
+// only free channel; it is HBM-bound, its emit pass moves only 3 M pairs, and carrying the key raises fj_probe_direct from 66 to 86 VGPRs
+// (7 -> 5 waves per SIMD) -- registers for almost nothing (DESIGN.md §5 "Partial carry").  TGPU_FJ_CARRY_RULE overrides it for kernel studies.
+constexpr int kFjFreeRule = 1;
+void fused_probe_launch_counts(int64_t out[3])
+{
+    for (int i = 0; i < 3; i++) out[i] = g_fj_launches[i].load(std::memory_order_relaxed);
+}
 
 void FusedProbeGpu::generate()
 {
@@ -1751,6 +1834,29 @@ void FusedProbeGpu::generate()
     std::vector<int> carry_only_cols;   // columns only the carried outputs read
     for (int ch : gc.reg_cols)
         if (!gr.reg_cols.count(ch)) carry_only_cols.push_back(ch);
+    // (d) PARTIAL carry (FJ_CARRY 2): an output channel is FREE when pass 1 already holds everything it needs -- fixed width, cannot
+    // raise, reads only columns of the filter / key row (nothing of carry_only_cols, no memory-mode column).  Free channels are carried
+    // as in (c), the others are gathered by pass 2 as in (b): TgRow and tg_load_row stay those of the two-pass kernel.
+    // Which free channels are carried is a static rule (free_rule below), chosen by measurement: DESIGN.md §5 "Partial carry".
+    free_out_.assign(output_channels_.size(), false);
+    partial_supported_ = false;
+    {
+        const char *rule_env = getenv("TGPU_FJ_CARRY_RULE");   // kernel studies: 0 = every free channel, 1 = not the join key's channel
+        const int free_rule = rule_env ? atoi(rule_env) : kFjFreeRule;
+        for (size_t i = 0; i < output_channels_.size() && i < 4; i++) {
+            const int ch = output_channels_[i];
+            if (ch == join_channel_ && (key_can_raise_ || free_rule == 1)) continue;
+            Gen ga(nodes_, pool_, input_types_);
+            ga.reg_mode = true;
+            ga.gen(proj_roots_[(size_t)ch], 1);
+            bool held = ga.used_cols.empty() && ga.consts.str().empty();
+            for (int col : ga.reg_cols) held = held && gr.reg_cols.count(col) != 0;
+            free_out_[i] = held;
+            partial_supported_ = partial_supported_ || held;
+        }
+    }
+    auto all_or_free = [&](size_t i) { return free_out_[i] ? "#if FJ_CARRY\n" : "#if FJ_CARRY == 1\n"; };   // code of channel i: both carry modes, or full carry only
+    auto not_carried = [&](size_t i) { return free_out_[i] ? "#if FJ_CARRY != 2\n" : "#if 1\n"; };          // what pass 2 gathers
 
     std::ostringstream src;
     src << "#ifndef FJ_CARRY\n#define FJ_CARRY 0\n#endif\n";
@@ -1787,17 +1893,18 @@ void FusedProbeGpu::generate()
     for (auto &b : mem_bodies) src << splice(b, mc);
     // the carried outputs of one row (register form), their evaluation, and the two stores
     src << "struct FjArgs;\nstruct TgOut {\n";
-    for (size_t i = 0; i < output_channels_.size(); i++) src << "  " << ctype(proj_types_[(size_t)output_channels_[i]]) << " v" << i << ";\n";
+    for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  " << ctype(proj_types_[(size_t)output_channels_[i]]) << " v" << i << ";\n#endif\n";
     src << "#if !FJ_NO_NULLS\n  unsigned char nulls;\n#endif\n};\n__device__ inline void tg_zero_out(TgOut& O) {\n";
-    for (size_t i = 0; i < output_channels_.size(); i++) src << "  O.v" << i << " = 0;\n";
-    src << "#if !FJ_NO_NULLS\n  O.nulls = 0;\n#endif\n}\n#if FJ_CARRY\n";
+    for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  O.v" << i << " = 0;\n#endif\n";
+    src << "#if !FJ_NO_NULLS\n  O.nulls = 0;\n#endif\n  (void)O;\n}\n#if FJ_CARRY\n";
     {
         const std::string cc = cols_decl(gc);
-        for (auto &b : carry_bodies) src << splice(b, cc);
+        for (size_t i = 0; i < carry_bodies.size(); i++) src << all_or_free(i) << splice(carry_bodies[i], cc) << "#endif\n";
         src << "__device__ inline void tg_carry_eval(const FpArgs& A, long long row, const TgRow& R, TgOut& O) {\n  unsigned char nl = 0;\n";
         for (size_t i = 0; i < output_channels_.size(); i++) {
             const int32_t t = proj_types_[(size_t)output_channels_[i]];
-            src << "  { " << ctype(t) << " v = 0; const bool n = tg_c" << i << "(A, row, R, v); O.v" << i << " = n ? (" << ctype(t) << ")0 : v; nl |= n ? " << (1 << i) << " : 0; }\n";
+            src << all_or_free(i) << "  { " << ctype(t) << " v = 0; const bool n = tg_c" << i << "(A, row, R, v); O.v" << i << " = n ? (" << ctype(t) << ")0 : v; nl |= n ? " << (1 << i)
+                << " : 0; }\n#endif\n";
         }
         src << "#if !FJ_NO_NULLS\n  O.nulls = nl;\n#else\n  (void)nl;\n#endif\n}\n";
     }
@@ -1807,7 +1914,7 @@ void FusedProbeGpu::generate()
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int32_t t = proj_types_[(size_t)output_channels_[i]];
         const std::string T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
-        carry_funcs << "  ((" << T << "*)J.carry[" << i << "])[at] = (" << T << ")O.v" << i << ";\n";
+        carry_funcs << all_or_free(i) << "  ((" << T << "*)J.carry[" << i << "])[at] = (" << T << ")O.v" << i << ";\n#endif\n";
     }
     carry_funcs << "#if !FJ_NO_NULLS\n  if (J.carry_nulls) J.carry_nulls[at] = O.nulls;\n#endif\n}\n"
                 << "__device__ inline void tg_carry_move(const FjArgs& J, long long from, long long to) {\n  const FpArgs& A = J.fp;\n"
@@ -1815,18 +1922,18 @@ void FusedProbeGpu::generate()
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int32_t t = proj_types_[(size_t)output_channels_[i]];
         const std::string T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
-        carry_funcs << "  ((" << T << "*)A.out_values[" << i << "])[to] = ((const " << T << "*)J.carry[" << i << "])[from]; if (A.out_nulls[" << i << "]) A.out_nulls[" << i
-                    << "][to] = (unsigned char)((nl >> " << i << ") & 1u);\n";
+        carry_funcs << all_or_free(i) << "  ((" << T << "*)A.out_values[" << i << "])[to] = ((const " << T << "*)J.carry[" << i << "])[from]; if (A.out_nulls[" << i
+                    << "]) A.out_nulls[" << i << "][to] = (unsigned char)((nl >> " << i << ") & 1u);\n#endif\n";
     }
     carry_funcs << "}\n#endif\n";
     (void)kt;
-    src << "__device__ inline void tg_emit_outputs(const FpArgs& A, long long row, long long o) {\n";
+    src << "__device__ inline void tg_emit_outputs(const FpArgs& A, long long row, long long o) {\n  (void)A; (void)row; (void)o;\n";
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int ch = output_channels_[i];
         const int32_t t = proj_types_[(size_t)ch];
         const char *T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
-        src << "  { " << ctype(t) << " v = 0; const bool n = tg_p" << ch << "(A, row, v); ((" << T << "*)A.out_values[" << i << "])[o] = n ? (" << T << ")0 : (" << T
-            << ")v; if (A.out_nulls[" << i << "]) A.out_nulls[" << i << "][o] = n ? 1 : 0; }\n";   // (no null vector: the host proved the channel null-free)
+        src << not_carried(i) << "  { " << ctype(t) << " v = 0; const bool n = tg_p" << ch << "(A, row, v); ((" << T << "*)A.out_values[" << i << "])[o] = n ? (" << T << ")0 : (" << T
+            << ")v; if (A.out_nulls[" << i << "]) A.out_nulls[" << i << "][o] = n ? 1 : 0; }\n#endif\n";   // (no null vector: the host proved the channel null-free)
     }
     src << "}\n";
     // experiment switches for kernel studies (tools/exp_fused.py); never set in production
@@ -1851,26 +1958,26 @@ static std::string prefilter_source(const std::string &src, int variant)
     // statistics then keep the DIRECT-layout launches (TPCH keys) apart from the open-address ones
     static const char *layout[4] = {"plain", "bitmap", "bloom", "direct"};
     const std::string l = layout[variant % 4];
-    return "#define FJ_PF " + std::to_string(variant % 4) + "\n#define FJ_NO_NULLS " + std::to_string((variant / 4) % 2) + "\n#define FJ_CARRY " + std::to_string((variant / 8) % 2) +
-           "\n#define FJ_EPILOGUE " + std::to_string(variant / 16) + "\n#define fj_pair fj_pair_" + l + "\n#define fj_probe fj_probe_" + l +
+    return "#define FJ_PF " + std::to_string(variant % 4) + "\n#define FJ_NO_NULLS " + std::to_string((variant / 4) % 2) + "\n#define FJ_CARRY " + std::to_string(variant / 24) +
+           "\n#define FJ_EPILOGUE " + std::to_string((variant / 8) % 3) + "\n#define fj_pair fj_pair_" + l + "\n#define fj_probe fj_probe_" + l +
            "\n#define fj_emit fj_emit_" + l + "\n" + src;
 }
 
 void FusedProbeGpu::precompile()
 {
     if (!supported_) return;
-    for (int variant = 0; variant < 8; variant++) {
+    for (int variant = 0; variant < 24; variant++) {   // layout x null vectors x {whole table, one page, a list of pages}
         (void)code_object_for(prefilter_source(source_, variant));
-        (void)code_object_for(prefilter_source(source_, 16 + variant));   // the page variants (FJ_EPILOGUE 1: one page, 2: a list of pages)
-        (void)code_object_for(prefilter_source(source_, 32 + variant));
+        // the default of the exact-bitmap and DIRECT layouts when a channel is free: partial carry (a list of pages never carries)
+        if (partial_supported_ && (variant % 4 == 1 || variant % 4 == 3) && variant / 8 < 2) (void)code_object_for(prefilter_source(source_, 48 + variant));
     }
-    // (the opt-in carry variants, 8 + ..., are compiled on first use)
+    // (the opt-in full carry variants, 24 + ..., are compiled on first use)
 }
 
-JitModule *FusedProbeGpu::module_for(int kind, bool no_nulls, bool carry, int epilogue)
+JitModule *FusedProbeGpu::module_for(int kind, bool no_nulls, int carry, int epilogue)
 {
     std::lock_guard<std::mutex> lk(mu_);
-    const int variant = kind + (no_nulls ? 4 : 0) + (carry ? 8 : 0) + epilogue * 16;   // epilogue: 0 plain, 1 page, 2 list of pages
+    const int variant = kind + (no_nulls ? 4 : 0) + epilogue * 8 + carry * 24;   // epilogue: 0 plain, 1 page, 2 list of pages; carry: 0 none, 1 full, 2 partial
     if (!modules_[variant]) modules_[variant] = load_module(prefilter_source(source_, variant));
     return modules_[variant].get();
 }
@@ -1884,7 +1991,8 @@ struct FusedProbeGpu::Pending {
     JitModule *module = nullptr;
     int pf_kind = 0;
     int64_t chunks = 0;
-    bool outer = false, need_build_positions = false, carry = false;
+    bool outer = false, need_build_positions = false;
+    int carry = 0;
     BufferPtr tile_cnt, tile_src, tile_dst, misc, pair_probe, pair_build;
     std::vector<BufferPtr> carry_regions;
     Context::AsyncRead read;
@@ -1937,8 +2045,15 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     // emit pass falls from 0.63 to 0.28 ms, but the probe launch rises from 0.69 to 1.06 ms (+16 B per row in flight, 118 instead of
     // 80 VGPRs = 4 instead of 6 waves per SIMD under an L2-request-bound lookup) -- a wash (4.31-4.40 ms per step either way).  So the
     // variant is opt-in (TGPU_FJ_CARRY=1; exact key bitmaps, inner joins) and stays tested; the default keeps the two-pass gather.
-    bool carry = false;
-    if (const char *f = getenv("TGPU_FJ_CARRY")) carry = atoi(f) != 0 && carry_supported_ && (tv.rank_base || tv.bitmap) && !output_channels_.empty() && !outer;
+    // PARTIAL carry (generate(), (d)) carries only the outputs pass 1 holds anyway: no load and no row register is added, so it is the
+    // default wherever the full variant is eligible and a channel is free.  TGPU_FJ_CARRY=0 keeps the two-pass gather, =1 the full carry.
+    int carry = 0;
+    if ((tv.rank_base || tv.bitmap) && !output_channels_.empty() && !outer) {
+        const char *f = getenv("TGPU_FJ_CARRY");
+        const int want = f ? atoi(f) : 2;
+        if (want == 1) carry = carry_supported_ ? 1 : 0;
+        else if (want == 2) carry = partial_supported_ ? 2 : 0;
+    }
     const int64_t tile_rows = (int64_t)fj_stripes() * 256;
     // the launch's rows: a page's own rows, or -- several pages -- VIRTUAL rows: every page starts a tile
     std::vector<int32_t> page_tile0;
@@ -1953,7 +2068,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
         page_tile0.push_back((int32_t)t);
         TG_CHECK_ARG(t <= kFjMultiMaxTiles, "too many rows for one multi-page launch");
         n = t * tile_rows;
-        carry = false;
+        carry = 0;
     }
     if (n == 0) return nullptr;
     // pages of up to kFjEpilogueMaxChunks tiles (always one-tile chunks, see below) run the kernel variant whose pass 1 ends with the scan and
@@ -2076,6 +2191,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     if (carry) {
         bool nullable = false;
         for (size_t i = 0; i < output_channels_.size(); i++) {
+            if (carry == 2 && !free_out_[i]) continue;   // (partial: pass 2 gathers this channel)
             carry_regions.push_back(ctx->alloc((size_t)cap * type_width(proj_types_[(size_t)output_channels_[i]])));
             J.carry[i] = carry_regions.back()->ptr();
             const tgpu_expr_node &root = nodes_[(size_t)proj_roots_[(size_t)output_channels_[i]]];
@@ -2089,6 +2205,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     pend->grid1 = grid1;
     pend->tile_cnt = tile_cnt; pend->tile_src = tile_src; pend->tile_dst = tile_dst; pend->misc = misc; pend->pair_probe = pair_probe; pend->pair_build = pair_build;
     // (launch == false: the caller puts pass 1 into one launch with another page's pass 2, launch_pair; only the page variant can)
+    g_fj_launches[carry].fetch_add(1, std::memory_order_relaxed);
     if (launch || !epilogue) launch_probe(ctx, pend);
     signal_guard.armed = false;
     return pend;

@@ -145,6 +145,7 @@ constexpr int64_t kFjMultiMaxTiles = 32768;      // tiles of one launch over a l
 constexpr int64_t kFjEpilogueMaxChunks = 2048;   // probe launches of up to 2048 tiles (1.5 M rows at 768-row tiles; always one-tile chunks) end pass 1 with the epilogue
 
 class LookupSourceGpu;
+void fused_probe_launch_counts(int64_t out[3]);
 
 class FusedProbeGpu {
 public:
@@ -187,7 +188,7 @@ public:
 
 private:
     void generate();
-    struct JitModule *module_for(int prefilter_kind, bool no_nulls, bool carry, int epilogue);
+    struct JitModule *module_for(int prefilter_kind, bool no_nulls, int carry, int epilogue);
     std::mutex mu_;
     std::vector<int32_t> input_types_;
     std::vector<tgpu_expr_node> nodes_;
@@ -197,8 +198,10 @@ private:
     int32_t join_channel_;
     bool supported_ = false;
     std::string source_;
-    std::shared_ptr<JitModule> modules_[48];   // layout (4) x no-null-vectors (2) x carry (2) x {whole table, one page with the epilogue, list of pages} (3)
+    std::shared_ptr<JitModule> modules_[72];   // layout (4) x no-null-vectors (2) x {whole table, one page with the epilogue, list of pages} (3) x carry {none, full, partial} (3)
     bool carry_supported_ = false;
+    bool partial_supported_ = false, key_can_raise_ = false;
+    std::vector<bool> free_out_;   // per output channel: pass 1 holds what it needs (partial carry, generate() (d))
 };
 
 // FilterAndProject feeding a HashAggregation: the filter becomes a row mask in front of the group-by table (no row is

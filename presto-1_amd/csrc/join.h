@@ -10,6 +10,8 @@ namespace tgpu {
 
 // M/operator/PagesIndex.java:209-240: the build side's pages appended into contiguous per-channel HBM columns.
 // SyntheticAddress(pageIndex, position) collapses to the flat row number because pages are stored back to back.
+// A first page whose buffers all have owners is not copied but adopted (join.hip, adopt): its columns may start anywhere inside
+// their buffers, and it is moved into a growable store only if a second page arrives.
 class PagesIndexGpu {
 public:
     PagesIndexGpu(Context *ctx, std::vector<int32_t> types);
@@ -29,9 +31,12 @@ private:
         bool has_nulls = false;
     };
     void reserve(int64_t rows);
+    bool adopt(const DevicePage &page);
+    void append(const DevicePage &page, const std::vector<std::array<int32_t, 2>> *varchar_ends);
     Context *ctx_;
     std::vector<int32_t> types_;
     std::vector<Store> cols_;
+    std::vector<DeviceColumn> adopted_;   // non-empty: the index IS this one page, held by reference (adopt); cols_ is then unused
     int64_t n_ = 0;
 };
 

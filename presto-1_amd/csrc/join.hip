@@ -569,6 +569,7 @@ PagesIndexGpu::PagesIndexGpu(Context *ctx, std::vector<int32_t> types) : ctx_(ct
 int64_t PagesIndexGpu::estimated_size() const
 {
     int64_t s = 0;
+    for (auto &c : adopted_) s += c.size_in_bytes();   // (an adopted page: its rows' share of the buffers it references)
     for (auto &c : cols_) s += c.cap * type_width(c.type) + (c.nulls ? c.cap : 0) + (c.offsets ? (c.cap + 1) * 4 : 0) + c.pool_cap;
     return s;
 }
@@ -601,12 +602,51 @@ void PagesIndexGpu::reserve(int64_t rows)
     }
 }
 
+// The first page of an index whose arrays all have owners (a library-owned page, or device blocks inside live library buffers:
+// columns.cpp ingest_block) is kept BY REFERENCE: no copy, no launch -- a build side that arrives as one page (a table-at-a-time
+// plan's filter or join output) is what the lookup source then reads.  Library buffers are immutable once handed out, and the index
+// never writes or grows an adopted one: the next add_page first moves the rows into a growable store (the copy this saved, done later).
+// VARCHAR channels need offsets that start at 0 and a pool size known on the host (no read-back for the sake of adoption).
+bool PagesIndexGpu::adopt(const DevicePage &page)
+{
+    for (size_t i = 0; i < cols_.size(); i++) {
+        const DeviceColumn &src = page.cols[i];
+        if (src.type != cols_[i].type || src.n != page.n) return false;
+        if (!src.values || !src.values_buf) return false;
+        if (src.nulls && !src.nulls_buf) return false;
+        if (src.type == TGPU_VARCHAR && (!src.offsets || !src.offsets_buf || !src.pool_exact || src.pool_first != 0)) return false;
+    }
+    adopted_ = page.cols;
+    n_ = page.n;
+    return true;
+}
+
 void PagesIndexGpu::add_page(const DevicePage &page, const std::vector<std::array<int32_t, 2>> *varchar_ends)
 {
     TG_CHECK_ARG(page.cols.size() == types_.size(), "page channel count does not match the index");
     if (page.n == 0) return;
     if (n_ + page.n > 0x7fffffffLL) fail(TGPU_ERR_INSUFFICIENT_RESOURCES, "Size of pages index cannot exceed 2 billion entries");  // PagesIndex.java:234-236
+    if (n_ == 0 && adopted_.empty() && !cols_.empty() && getenv("TGPU_DISABLE_BUILD_ADOPTION") == nullptr && adopt(page)) return;
+    if (!adopted_.empty()) {
+        // a second page: the adopted rows move into a growable store, sized as if they had been appended first (exact fit, then doubling)
+        DevicePage first;
+        first.n = n_;
+        first.cols = std::move(adopted_);
+        adopted_.clear();
+        n_ = 0;
+        int64_t cap = std::max<int64_t>(first.n, 1024);
+        while (cap < first.n + page.n) cap <<= 1;
+        reserve(cap);
+        append(first, nullptr);
+    }
     reserve(n_ + page.n);
+    append(page, varchar_ends);
+}
+
+void PagesIndexGpu::append(const DevicePage &page, const std::vector<std::array<int32_t, 2>> *varchar_ends)
+{
+    std::unique_ptr<ProfileScope> prof;   // (a caller's scope, if one is open, keeps the launch: scopes do not nest)
+    if (!ctx_->in_profile_scope()) prof = std::make_unique<ProfileScope>(ctx_, "append_page");
     AppendJobs jobs{};
     int n_jobs = 0;
     long long most = 0;
@@ -673,6 +713,7 @@ void PagesIndexGpu::add_page(const DevicePage &page, const std::vector<std::arra
 DeviceColumn PagesIndexGpu::column(int ch) const
 {
     TG_CHECK_ARG(ch >= 0 && ch < (int)cols_.size(), "channel out of range");
+    if (!adopted_.empty()) return adopted_[(size_t)ch];
     const Store &s = cols_[ch];
     DeviceColumn c;
     c.type = s.type;

@@ -14,12 +14,17 @@
 
 namespace tgpu {
 
-// May an operator keep `in` by reference after add_input returned?  Library-owned pages (another operator's output, an ingested host
-// page) hold their buffers; borrowed device blocks are the caller's unless it promised to leave them alone
-// (tgpu_context_set_device_input_stable).
-static bool page_is_retained(Context *ctx, const DevicePage &in)
+// May an operator keep `in` by reference after add_input returned and launch its kernels in a LATER call?  Library-owned pages (another
+// operator's output handed over as such, an ingested host page) hold their buffers.  A page that came in as TGPU_DEVICE blocks (`blocks`)
+// is the caller's to judge: only its promise (tgpu_context_set_device_input_stable) defers the launches -- also when ingest found the
+// owners of its blocks (Context::owner_of): shared owners replace COPIES (the hash builder, the pass-through operators), they do not
+// change in which call an operator reads the caller's blocks.
+static bool page_is_retained(Context *ctx, const DevicePage &in, const tgpu_page *blocks)
 {
     if (ctx->device_input_stable()) return true;
+    if (blocks)
+        for (int32_t ch = 0; ch < blocks->channel_count; ch++)
+            if (blocks->blocks[ch].encoding == TGPU_FLAT && blocks->blocks[ch].memory == TGPU_DEVICE) return false;
     for (const DeviceColumn &c : in.cols) {
         if (c.n > 0 && !c.values_buf) return false;
         if (c.nulls && !c.nulls_buf) return false;
@@ -1212,7 +1217,7 @@ public:
         const bool fused_ok = !filter && fused_->supported() && cfg_.probe_join_channels.size() == 1 && source->int_table(tv) && tv.links == nullptr &&
                               tv.key_type == fused_->projection_types()[(size_t)cfg_.probe_join_channels[0]] && getenv("TGPU_DISABLE_FUSION") == nullptr;
         if (fused_ok) {
-            const bool async = in.n <= kAsyncBelowRows && page_is_retained(ctx_, in) && getenv("TGPU_DISABLE_ASYNC_JOIN") == nullptr;
+            const bool async = in.n <= kAsyncBelowRows && page_is_retained(ctx_, in, owned ? nullptr : page) && getenv("TGPU_DISABLE_ASYNC_JOIN") == nullptr;
             if (!async) {
                 flush_batch();
                 complete_all();
@@ -1460,6 +1465,7 @@ public:
         // the fused kernels address VARCHAR bytes through the offsets alone: the byte ranges of borrowed device columns stay unread
         DevicePage in = owned ? DevicePage(*owned) : ingest_page(ctx_, page, /*resolve_varchar=*/!fused_ok);
         if (in.n == 0) return;
+        const bool keep = page_is_retained(ctx_, in, owned ? nullptr : page);
         if (!fused_ok) {
             drain_onepass();
             // unfused composition: FilterAndProject, then the aggregation
@@ -1471,7 +1477,7 @@ public:
         // the groups and decide the DOUBLE mode -- and if the group set has settled by then (it has for the few-group aggregations this path
         // is for) the REST of the page is one one-pass launch: every input byte read once instead of the key columns twice.  The rest is
         // judged like any one-pass launch: a row of an unknown group makes it dirty and it is re-run through the two-launch path.
-        if (in.n >= kSplitAboveRows && pending_.empty() && batch_.empty() && clean_streak_ < kOnepassAfter && retained(in) && getenv("TGPU_DISABLE_ONEPASS") == nullptr &&
+        if (in.n >= kSplitAboveRows && pending_.empty() && batch_.empty() && clean_streak_ < kOnepassAfter && keep && getenv("TGPU_DISABLE_ONEPASS") == nullptr &&
             getenv("TGPU_DISABLE_SPECULATION") == nullptr && getenv("TGPU_DISABLE_PAGE_SPLIT") == nullptr) {
             static constexpr int64_t kSlices[3] = {1 << 18, 1 << 18, 1 << 20};
             int64_t at = 0;
@@ -1480,7 +1486,7 @@ public:
                 at += len;
             }
             DevicePage rest = slice_of(in, at, in.n - at);
-            if (onepass_ready(rest)) {
+            if (onepass_ready(keep)) {
                 batch_rows_ += rest.n;
                 batch_.push_back(std::move(rest));
                 launch_onepass();
@@ -1490,7 +1496,7 @@ public:
             }
             return;
         }
-        if (onepass_ready(in)) {
+        if (onepass_ready(keep)) {
             // the operator is blocking (nothing leaves it before finish): small pages are collected, by reference, into one launch
             batch_rows_ += in.n;
             batch_.push_back(std::move(in));
@@ -1608,12 +1614,11 @@ private:
         Context::AsyncRead read;
         Context::Signal signal;
     };
-    bool retained(const DevicePage &in) const { return page_is_retained(ctx_, in); }
-    bool onepass_ready(const DevicePage &in) const
+    bool onepass_ready(bool keep) const   // keep: page_is_retained
     {
         const bool disabled = getenv("TGPU_DISABLE_ONEPASS") != nullptr || getenv("TGPU_DISABLE_SPECULATION") != nullptr;
         return !disabled && clean_streak_ >= kOnepassAfter && fused_->can_onepass(gbh_->group_count()) && !accs_->force_ordered() && accs_->decided() && !accs_->ordered() &&
-               retained(in);
+               keep;
     }
     void launch_onepass()
     {

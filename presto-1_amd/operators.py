@@ -581,6 +581,13 @@ def precompile_fused_probe(input_types, filter_expr, projections, join_channel, 
     _lib.check(_lib.lib().tgpu_precompile_fused_probe(nt, t, C.byref(spec), join_channel, no, oc))
 
 
+def fused_probe_launch_counts():
+    """(two-pass gather, full carry, partial carry): fused probe launches prepared so far in this process, by carry mode"""
+    out = (C.c_int64 * 3)()
+    _lib.check(_lib.lib().tgpu_fused_probe_launch_counts(out))
+    return tuple(int(v) for v in out)
+
+
 class GroupByHash:
     """GroupByHash.createGroupByHash (M/operator/GroupByHash.java:45-59) over the GPU table."""
 
