@@ -24,6 +24,7 @@
  *   - tgpu_merge_pages_*         <-> M/operator/project/MergePages.java:64-190
  *   - tgpu_dynamic_filter_source_* <-> M/operator/DynamicFilterSourceOperator.java:74-425
  *   - tgpu_set_builder_* / tgpu_hash_semi_join_* <-> M/operator/SetBuilderOperator.java:39-233, HashSemiJoinOperator.java:44-218, ChannelSet.java:62-108
+ *   - tgpu_mark_distinct_* / tgpu_distinct_limit_* <-> M/operator/MarkDistinctOperator.java:37-203, MarkDistinctHash.java:31-87, DistinctLimitOperator.java:40-263
  *   - tgpu_serialize_page / tgpu_deserialize_page <-> M/execution/buffer/PagesSerde.java:64-160, PagesSerdeUtil.java:45-71,
  *                                    S/block/{LongArray,IntArray,ByteArray,VariableWidth,RunLength,Dictionary}BlockEncoding.java, EncoderUtil.java:33-118
  *   - tgpu_exchange_*            <-> M/operator/PartitionedOutputOperator.java:406-476 -> M/operator/ExchangeOperator.java (the hop between
@@ -328,6 +329,25 @@ int32_t tgpu_hash_semi_join_factory_create(tgpu_context *ctx, int32_t operator_i
  * 1 hash, 2 generic) */
 int32_t tgpu_set_supplier_stats(tgpu_set_supplier *supplier, int64_t *size, int32_t *contains_null, int64_t *bytes, int32_t *layout);
 void tgpu_set_supplier_destroy(tgpu_set_supplier *supplier);
+
+/* ---- count(DISTINCT x) and SELECT DISTINCT ... LIMIT n (LocalExecutionPlanner.visitMarkDistinct / visitDistinctLimit) ---- */
+/* MarkDistinctOperator.MarkDistinctOperatorFactory (M/operator/MarkDistinctOperator.java:39-92, :94-203; MarkDistinctHash.java:52-69): output
+ * page = the input page's channels unchanged, then one BOOLEAN channel without nulls that is true on the first row of every value of the
+ * mark channels the operator has not seen before (a null key is a value like any other); one output page per input page.  The marker is
+ * what tgpu_agg_spec.mask_channel reads for count(DISTINCT x).  mark_channels: non-empty, any order, at most 8, each in [0, type_count);
+ * hash_channel: -1 or a BIGINT channel holding the precomputed raw hash of the mark channels.  TGPU_ERR_INVALID_ARGUMENT otherwise.
+ * One GroupByHash per operator (expected size 10 000, MarkDistinctHash.java:39); memory_bytes = its estimated size. */
+int32_t tgpu_mark_distinct_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                          int32_t mark_channel_count, const int32_t *mark_channels, int32_t hash_channel /* -1 = none */,
+                                          tgpu_operator_factory **out);
+/* DistinctLimitOperator.DistinctLimitOperatorFactory (M/operator/DistinctLimitOperator.java:42-99, :101-263): output page = the distinct
+ * channels in the given order, then the hash channel if there is one (:125-128), flat; it holds the rows of the input page that start
+ * a new value of the distinct channels, in row order, cut at the remaining limit (:189-202).  No output page for an input page that
+ * contributes no row.  needs_input = not finishing, limit not reached, no page pending; is_finished = no page pending and (finishing
+ * or limit reached): with limit 0 at once.  Arguments as tgpu_mark_distinct_factory_create; limit < 0 is TGPU_ERR_INVALID_ARGUMENT (:70). */
+int32_t tgpu_distinct_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                           int32_t distinct_channel_count, const int32_t *distinct_channels, int64_t limit,
+                                           int32_t hash_channel /* -1 = none */, tgpu_operator_factory **out);
 
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of

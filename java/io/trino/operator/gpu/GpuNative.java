@@ -115,6 +115,10 @@ public final class GpuNative
     /** out = {distinct keys (a null counted), containsNull 0 / 1, HBM bytes, layout} of the built set */
     public static native void setSupplierStats(long supplier, long[] sizeContainsNullBytesLayout);
     public static native void destroySetSupplier(long supplier);
+    /** MarkDistinctOperatorFactory (tgpu_mark_distinct_factory_create): the input page + one BOOLEAN channel; hashChannel -1 = none */
+    public static native long createMarkDistinctFactory(long context, int operatorId, int[] types, int[] markDistinctChannels, int hashChannel);
+    /** DistinctLimitOperatorFactory (tgpu_distinct_limit_factory_create): output = the distinct channels, then the hash channel if any */
+    public static native long createDistinctLimitFactory(long context, int operatorId, int[] types, int[] distinctChannels, long limit, int hashChannel);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);
     public static native long createOrderByFactory(long context, int operatorId, int[] types, int[] outputChannels, int expectedPositions, int[] sortChannels, int[] sortOrders);
     public static native long createMergePagesFactory(long context, int operatorId, int[] types, long minPageSizeInBytes, int minRowCount, long maxPageSizeInBytes);

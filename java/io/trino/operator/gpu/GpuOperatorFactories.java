@@ -351,6 +351,38 @@ public final class GpuOperatorFactories
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuHashSemiJoinOperator", probeTypes, poller, factory));
     }
 
+    /**
+     * MarkDistinctOperator.MarkDistinctOperatorFactory (operator/MarkDistinctOperator.java:51-71; LocalExecutionPlanner.visitMarkDistinct): the source page plus one
+     * BOOLEAN channel that is true on the first row of every value of the mark channels; the aggregation reads it as its mask channel.
+     */
+    public Optional<OperatorFactory> markDistinct(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> markDistinctChannels, OptionalInt hashChannel)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createMarkDistinctFactory(context, operatorId, codes, ints(markDistinctChannels), hashChannel.orElse(-1));
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuMarkDistinctOperator", sourceTypes, poller, factory));
+    }
+
+    /** DistinctLimitOperator.DistinctLimitOperatorFactory (operator/DistinctLimitOperator.java:55-75; LocalExecutionPlanner.visitDistinctLimit) */
+    public Optional<OperatorFactory> distinctLimit(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> distinctChannels, long limit,
+            OptionalInt hashChannel)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createDistinctLimitFactory(context, operatorId, codes, ints(distinctChannels), limit, hashChannel.orElse(-1));
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuDistinctLimitOperator", sourceTypes, poller, factory));
+    }
+
     /** TopNOperator.createOperatorFactory (operator/TopNOperator.java:47-62; LocalExecutionPlanner.visitTopN) */
     public Optional<OperatorFactory> topN(int operatorId, PlanNodeId planNodeId, List<Type> types, long n, List<Integer> sortChannels, List<SortOrder> sortOrders)
     {

@@ -19,6 +19,7 @@
  * TrinoException(StandardErrorCode).
  */
 #include <jni.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -585,6 +586,60 @@ JFN(void, setSupplierStats)(JNIEnv *env, jclass c, jlong supplier, jlongArray ou
 }
 
 JFN(void, destroySetSupplier)(JNIEnv *env, jclass c, jlong supplier) { UNUSED(env); UNUSED(c); tgpu_set_supplier_destroy(H(tgpu_set_supplier, supplier)); }
+
+/* the key channels of the two distinct operators, checked in front of the library: a non-empty type array, a non-empty channel list,
+ * every channel in [0, types), hashChannel -1 or a BIGINT channel.  Returns NULL, or the message to throw once the arrays are released */
+static const char *distinct_channels_error(const ints *t, const ints *ch, jint hashChannel)
+{
+    if (t->n <= 0) return "empty type array";
+    if (ch->n <= 0) return "empty channel list";
+    for (jsize i = 0; i < ch->n; i++)
+        if (ch->p[i] < 0 || ch->p[i] >= t->n) return "channel out of range";
+    if (hashChannel < -1 || hashChannel >= t->n) return "hash channel out of range";
+    if (hashChannel >= 0 && t->p[hashChannel] != TGPU_BIGINT) return "hash channel is not BIGINT";
+    return NULL;
+}
+
+/* MarkDistinctOperatorFactory (operator/MarkDistinctOperator.java:39-92): the input page + one BOOLEAN channel */
+JFN(jlong, createMarkDistinctFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray markDistinctChannels, jint hashChannel)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types), ch = ints_get(env, markDistinctChannels);
+    const char *bad = distinct_channels_error(&t, &ch, hashChannel);
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad) rc = tgpu_mark_distinct_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, ch.n, (const int32_t *)ch.p, hashChannel, &f);
+    ints_release(env, &ch);
+    ints_release(env, &t);
+    if (bad) {
+        char message[96];
+        snprintf(message, sizeof(message), "mark distinct: %s", bad);
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
+
+/* DistinctLimitOperatorFactory (operator/DistinctLimitOperator.java:42-99): the first `limit` distinct rows of the distinct channels */
+JFN(jlong, createDistinctLimitFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray distinctChannels, jlong limit, jint hashChannel)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types), ch = ints_get(env, distinctChannels);
+    const char *bad = limit < 0 ? "negative limit" : distinct_channels_error(&t, &ch, hashChannel);
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad)
+        rc = tgpu_distinct_limit_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, ch.n, (const int32_t *)ch.p, limit, hashChannel, &f);
+    ints_release(env, &ch);
+    ints_release(env, &t);
+    if (bad) {
+        char message[96];
+        snprintf(message, sizeof(message), "distinct limit: %s", bad);
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
 
 /* TopNOperator.createOperatorFactory (M/operator/TopNOperator.java:47-62); sortOrders: tgpu_sort_order = SortOrder's ordinal (S/connector/SortOrder.java:18-21) */
 JFN(jlong, createTopNFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong n, jintArray sortChannels, jintArray sortOrders)

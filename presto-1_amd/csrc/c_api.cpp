@@ -1258,6 +1258,33 @@ void tgpu_set_supplier_destroy(tgpu_set_supplier *supplier)
     if (c) drop(c);
 }
 
+int32_t tgpu_mark_distinct_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t mark_channel_count,
+                                          const int32_t *mark_channels, int32_t hash_channel, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && out, "null argument");
+        auto f = std::make_unique<tgpu_operator_factory>();
+        f->f = std::make_unique<MarkDistinctOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(mark_channels, mark_channel_count), hash_channel);
+        f->ctx = ctx->ctx.get();
+        retain(f->ctx);
+        *out = f.release();
+    });
+}
+
+int32_t tgpu_distinct_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t distinct_channel_count,
+                                           const int32_t *distinct_channels, int64_t limit, int32_t hash_channel, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && out, "null argument");
+        auto f = std::make_unique<tgpu_operator_factory>();
+        f->f = std::make_unique<DistinctLimitOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(distinct_channels, distinct_channel_count),
+                                                              limit, hash_channel);
+        f->ctx = ctx->ctx.get();
+        retain(f->ctx);
+        *out = f.release();
+    });
+}
+
 int32_t tgpu_merge_pages_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t min_page_size_in_bytes,
                                         int32_t min_row_count, int64_t max_page_size_in_bytes, tgpu_operator_factory **out)
 {

@@ -2310,6 +2310,183 @@ std::unique_ptr<OperatorFactory> HashSemiJoinOperatorFactory::duplicate()
     return std::make_unique<HashSemiJoinOperatorFactory>(ctx_, operator_id_, supplier_, probe_types_, probe_join_channel_, -1);
 }
 
+// =====================================================================================================================
+// MarkDistinctOperator (M/operator/MarkDistinctOperator.java:94-203): the input page's channels unchanged, then one BOOLEAN channel
+// without nulls that is true on the first row of every key the operator has not seen before (MarkDistinctHash.java:52-69); one output
+// page per input page.  A null key is a group like any other.  DistinctLimitOperator (M/operator/DistinctLimitOperator.java:101-263):
+// the distinct channels (+ the hash channel) of exactly those rows, cut at the remaining limit.  Both: one GroupByHashGpu per operator,
+// then the marking kernels of distinct.hip.
+// =====================================================================================================================
+namespace {
+void check_distinct_config(const std::vector<int32_t> &types, const std::vector<int32_t> &channels, int32_t hash_channel, const char *what)
+{
+    TG_CHECK_ARG(!types.empty(), std::string(what) + " needs at least one source channel");
+    for (int32_t t : types) TG_CHECK_ARG(valid_type(t), "unknown type");
+    TG_CHECK_ARG(!channels.empty(), std::string(what) + " needs at least one distinct channel");
+    TG_CHECK_ARG((int)channels.size() <= kMaxKeyChannels, "at most 8 key channels are supported");
+    for (int32_t ch : channels) TG_CHECK_ARG(ch >= 0 && ch < (int)types.size(), "distinct channel out of range");
+    TG_CHECK_ARG(hash_channel >= -1 && hash_channel < (int)types.size(), "hash channel out of range");
+    TG_CHECK_ARG(hash_channel < 0 || types[(size_t)hash_channel] == TGPU_BIGINT, "hash channel must be BIGINT");
+}
+
+std::vector<int32_t> types_of_channels(const std::vector<int32_t> &types, const std::vector<int32_t> &channels)
+{
+    std::vector<int32_t> out;
+    for (int32_t ch : channels) out.push_back(types[(size_t)ch]);
+    return out;
+}
+
+void check_page_types(const DevicePage &in, const std::vector<int32_t> &types)
+{
+    TG_CHECK_ARG(in.cols.size() == types.size(), "page channel count does not match the operator's types");
+    for (size_t i = 0; i < types.size(); i++) TG_CHECK_ARG(in.cols[i].type == types[i], "page channel type does not match the operator's types");
+}
+}  // namespace
+
+class MarkDistinctOperator : public Operator {
+public:
+    MarkDistinctOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &mark_channels, int32_t hash_channel)
+        : Operator(ctx, id), types_(types), channels_(mark_channels), hash_channel_(hash_channel),
+          marker_(ctx, types_of_channels(types, mark_channels), hash_channel >= 0, 10000)   // MarkDistinctHash.java:39
+    {
+    }
+
+    bool needs_input() override { return !finishing_ && !pending_; }   // :137-141
+    void add_input(const tgpu_page *page) override
+    {
+        ready();
+        emit(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        ready();
+        emit(DevicePage(page));
+    }
+    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    void finish() override { finishing_ = true; }
+    bool is_finished() override { return finishing_ && !pending_; }   // :131-135
+    int64_t memory_bytes() override { return marker_.estimated_size(); }
+
+private:
+    void ready()
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        TG_CHECK_STATE(!pending_, "Operator still has pending output");
+    }
+
+    void emit(DevicePage in)   // :143-174
+    {
+        check_page_types(in, types_);
+        std::vector<const DeviceColumn *> keys;
+        for (int32_t ch : channels_) keys.push_back(&in.cols[(size_t)ch]);
+        const int64_t *hashes = hash_channel_ >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel_].values : nullptr;
+        DeviceColumn mark = marker_.mark(keys, hashes, in.n);
+        // the page passes through: channels that borrow the caller's device memory get buffers of their own (the output outlives the call)
+        own_borrowed_columns(ctx_, in);
+        in.cols.push_back(std::move(mark));
+        pending_ = wrap(std::move(in));
+    }
+
+    std::vector<int32_t> types_, channels_;
+    int32_t hash_channel_;
+    DistinctMarkerGpu marker_;
+    std::unique_ptr<OutputPage> pending_;
+    bool finishing_ = false;
+};
+
+MarkDistinctOperatorFactory::MarkDistinctOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> mark_channels,
+                                                         int32_t hash_channel)
+    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), mark_channels_(std::move(mark_channels)), hash_channel_(hash_channel)
+{
+    check_distinct_config(types_, mark_channels_, hash_channel_, "mark distinct");
+}
+
+std::unique_ptr<Operator> MarkDistinctOperatorFactory::create_operator()
+{
+    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    return std::make_unique<MarkDistinctOperator>(ctx_, operator_id_, types_, mark_channels_, hash_channel_);
+}
+
+std::unique_ptr<OperatorFactory> MarkDistinctOperatorFactory::duplicate()   // MarkDistinctOperator.java:87-91
+{
+    return std::make_unique<MarkDistinctOperatorFactory>(ctx_, operator_id_, types_, mark_channels_, hash_channel_);
+}
+
+class DistinctLimitOperator : public Operator {
+public:
+    DistinctLimitOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &distinct_channels, int64_t limit,
+                          int32_t hash_channel)
+        : Operator(ctx, id), types_(types), channels_(distinct_channels), hash_channel_(hash_channel), remaining_(limit),
+          marker_(ctx, types_of_channels(types, distinct_channels), hash_channel >= 0, (int32_t)std::max<int64_t>(1, std::min<int64_t>(limit, 10000)))   // :130-138 (a limit of 0 never sees a page)
+    {
+    }
+
+    bool needs_input() override { return !finishing_ && remaining_ > 0 && !pending_; }   // :160-164
+    void add_input(const tgpu_page *page) override
+    {
+        ready();
+        emit(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        ready();
+        emit(page);
+    }
+    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    void finish() override { finishing_ = true; }
+    bool is_finished() override { return !pending_ && (finishing_ || remaining_ == 0); }   // :154-158
+    int64_t memory_bytes() override { return marker_.estimated_size(); }
+
+private:
+    void ready()
+    {
+        TG_CHECK_STATE(needs_input(), "Operator does not need input");
+    }
+
+    void emit(const DevicePage &in)   // :166-223
+    {
+        check_page_types(in, types_);
+        std::vector<const DeviceColumn *> keys;
+        for (int32_t ch : channels_) keys.push_back(&in.cols[(size_t)ch]);
+        const int64_t *hashes = hash_channel_ >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel_].values : nullptr;
+        const int32_t *positions = nullptr;
+        const int64_t kept = marker_.first_rows(keys, hashes, in.n, remaining_, &positions);
+        if (kept == 0) return;   // no output page for a page without a new key (:212-223)
+        DevicePage out;
+        out.n = kept;
+        for (int32_t ch : channels_) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)ch], positions, kept, false));
+        if (hash_channel_ >= 0) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)hash_channel_], positions, kept, false));   // :125-128
+        remaining_ -= kept;
+        pending_ = wrap(std::move(out));
+    }
+
+    std::vector<int32_t> types_, channels_;
+    int32_t hash_channel_;
+    int64_t remaining_;
+    DistinctMarkerGpu marker_;
+    std::unique_ptr<OutputPage> pending_;
+    bool finishing_ = false;
+};
+
+DistinctLimitOperatorFactory::DistinctLimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> distinct_channels,
+                                                           int64_t limit, int32_t hash_channel)
+    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), distinct_channels_(std::move(distinct_channels)), limit_(limit), hash_channel_(hash_channel)
+{
+    check_distinct_config(types_, distinct_channels_, hash_channel_, "distinct limit");
+    TG_CHECK_ARG(limit_ >= 0, "limit must be at least zero");   // :70
+}
+
+std::unique_ptr<Operator> DistinctLimitOperatorFactory::create_operator()
+{
+    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    return std::make_unique<DistinctLimitOperator>(ctx_, operator_id_, types_, distinct_channels_, limit_, hash_channel_);
+}
+
+std::unique_ptr<OperatorFactory> DistinctLimitOperatorFactory::duplicate()   // DistinctLimitOperator.java:94-98
+{
+    return std::make_unique<DistinctLimitOperatorFactory>(ctx_, operator_id_, types_, distinct_channels_, limit_, hash_channel_);
+}
+
 void Operator::add_input_owned(const DevicePage &page)
 {
     std::vector<tgpu_block> blocks(page.cols.size());

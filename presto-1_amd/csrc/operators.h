@@ -7,6 +7,7 @@
 #include <functional>
 
 #include "common.h"
+#include "distinct.h"
 #include "groupby.h"
 #include "jit.h"
 #include "join.h"
@@ -390,6 +391,36 @@ private:
     std::shared_ptr<SetSupplier> supplier_;
     std::vector<int32_t> probe_types_;
     int32_t probe_join_channel_;
+};
+
+// ---- MarkDistinctOperator (M/operator/MarkDistinctOperator.java:37-203) ---------------------------------------------------------------
+class MarkDistinctOperatorFactory : public OperatorFactory {
+public:
+    MarkDistinctOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> mark_channels, int32_t hash_channel);
+    std::unique_ptr<Operator> create_operator() override;
+    std::unique_ptr<OperatorFactory> duplicate() override;
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::vector<int32_t> types_, mark_channels_;
+    int32_t hash_channel_;
+};
+
+// ---- DistinctLimitOperator (M/operator/DistinctLimitOperator.java:40-263) ------------------------------------------------------------
+class DistinctLimitOperatorFactory : public OperatorFactory {
+public:
+    DistinctLimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> distinct_channels, int64_t limit,
+                                 int32_t hash_channel);
+    std::unique_ptr<Operator> create_operator() override;
+    std::unique_ptr<OperatorFactory> duplicate() override;
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::vector<int32_t> types_, distinct_channels_;
+    int64_t limit_;
+    int32_t hash_channel_;
 };
 
 // ---- TopNOperator (M/operator/TopNOperator.java:47-62,135-225) ----------------------------------------------------------

@@ -777,6 +777,30 @@ class HashSemiJoinOperatorFactory(OperatorFactory):
         self._supplier = set_supplier
 
 
+class MarkDistinctOperatorFactory(OperatorFactory):
+    """MarkDistinctOperator.MarkDistinctOperatorFactory (M/operator/MarkDistinctOperator.java:39-92): the input page plus one BOOLEAN
+    channel, true on the first row of every value of `mark_distinct_channels` the operator has not seen before."""
+
+    def __init__(self, ctx: Context, operator_id, source_types, mark_distinct_channels, hash_channel=-1):
+        t, nt = _i32(source_types)
+        m, nm = _i32(mark_distinct_channels)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_mark_distinct_factory_create(ctx.handle, operator_id, nt, t, nm, m, int(hash_channel), C.byref(h)))
+        super().__init__(h)
+
+
+class DistinctLimitOperatorFactory(OperatorFactory):
+    """DistinctLimitOperator.DistinctLimitOperatorFactory (M/operator/DistinctLimitOperator.java:42-99): the first `limit` distinct rows
+    of `distinct_channels`, in the order they arrive; output = the distinct channels, then the hash channel if there is one."""
+
+    def __init__(self, ctx: Context, operator_id, source_types, distinct_channels, limit, hash_channel=-1):
+        t, nt = _i32(source_types)
+        d, nd = _i32(distinct_channels)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_distinct_limit_factory_create(ctx.handle, operator_id, nt, t, nd, d, int(limit), int(hash_channel), C.byref(h)))
+        super().__init__(h)
+
+
 class MergePagesOperatorFactory(OperatorFactory):
     """MergePages.mergePages (M/operator/project/MergePages.java:64-96) as an operator: small pages are coalesced in HBM, big ones pass through"""
 
