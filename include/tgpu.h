@@ -25,6 +25,7 @@
  *   - tgpu_dynamic_filter_source_* <-> M/operator/DynamicFilterSourceOperator.java:74-425
  *   - tgpu_set_builder_* / tgpu_hash_semi_join_* <-> M/operator/SetBuilderOperator.java:39-233, HashSemiJoinOperator.java:44-218, ChannelSet.java:62-108
  *   - tgpu_mark_distinct_* / tgpu_distinct_limit_* <-> M/operator/MarkDistinctOperator.java:37-203, MarkDistinctHash.java:31-87, DistinctLimitOperator.java:40-263
+ *   - tgpu_row_number_* / tgpu_limit_* <-> M/operator/RowNumberOperator.java:43-364, LimitOperator.java:25-120
  *   - tgpu_serialize_page / tgpu_deserialize_page <-> M/execution/buffer/PagesSerde.java:64-160, PagesSerdeUtil.java:45-71,
  *                                    S/block/{LongArray,IntArray,ByteArray,VariableWidth,RunLength,Dictionary}BlockEncoding.java, EncoderUtil.java:33-118
  *   - tgpu_exchange_*            <-> M/operator/PartitionedOutputOperator.java:406-476 -> M/operator/ExchangeOperator.java (the hop between
@@ -348,6 +349,28 @@ int32_t tgpu_mark_distinct_factory_create(tgpu_context *ctx, int32_t operator_id
 int32_t tgpu_distinct_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
                                            int32_t distinct_channel_count, const int32_t *distinct_channels, int64_t limit,
                                            int32_t hash_channel /* -1 = none */, tgpu_operator_factory **out);
+
+/* ---- row_number() OVER (PARTITION BY k) [<= n] and LIMIT n (LocalExecutionPlanner.visitRowNumber / visitLimit) ---- */
+/* RowNumberOperator.RowNumberOperatorFactory (M/operator/RowNumberOperator.java:43-119, :121-364): output page = the output channels in
+ * the given order, then one BIGINT channel without nulls: the row's number inside its partition (the rows that agree on the partition
+ * channels; a null key is a value like any other), counted from 1 in arrival order across all pages.  Always output_channel_count + 1
+ * channels.  max_rows_per_partition = -1: one output page per input page, every row.  >= 0: only the rows whose number is <= the limit,
+ * in row order; no output page for an input page that keeps no row; 0 is legal and keeps nothing.  partition_channel_count = 0: one
+ * partition; with a limit the operator is finished (and needs no input) once it has numbered `limit` rows.  A partitioned operator
+ * never finishes early.  One page at a time: needs_input is false while a page's output is pending.  The partition types are taken
+ * from `types`; at most 8 partition channels.  hash_channel: -1 or a BIGINT channel holding the precomputed raw hash of the partition
+ * channels.  max_rows_per_partition < -1 or > 2^31 - 1 (the reference's limit is a Java int), expected_positions <= 0, a channel out of range or a hash channel without partition channels:
+ * TGPU_ERR_INVALID_ARGUMENT.  memory_bytes = the hash's estimated size + the per-partition counts (:266). */
+int32_t tgpu_row_number_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                       int32_t output_channel_count, const int32_t *output_channels, int32_t partition_channel_count,
+                                       const int32_t *partition_channels, int64_t max_rows_per_partition /* -1 = none */,
+                                       int32_t hash_channel /* -1 = none */, int32_t expected_positions, tgpu_operator_factory **out);
+/* LimitOperator.LimitOperatorFactory (M/operator/LimitOperator.java:27-60, :62-119): whole pages pass through untouched while they fit
+ * into the remaining limit, the page that crosses it is cut to a region of its first rows, finish() zeroes the remainder.
+ * needs_input = remaining > 0 and no page pending; is_finished = remaining == 0 and no page pending: with limit 0 at once.
+ * limit < 0 is TGPU_ERR_INVALID_ARGUMENT (:70). */
+int32_t tgpu_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t limit,
+                                  tgpu_operator_factory **out);
 
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of

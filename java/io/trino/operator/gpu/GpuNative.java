@@ -119,6 +119,10 @@ public final class GpuNative
     public static native long createMarkDistinctFactory(long context, int operatorId, int[] types, int[] markDistinctChannels, int hashChannel);
     /** DistinctLimitOperatorFactory (tgpu_distinct_limit_factory_create): output = the distinct channels, then the hash channel if any */
     public static native long createDistinctLimitFactory(long context, int operatorId, int[] types, int[] distinctChannels, long limit, int hashChannel);
+    /** RowNumberOperatorFactory (tgpu_row_number_factory_create): the output channels + the BIGINT row number; maxRowsPerPartition -1 = none, hashChannel -1 = none */
+    public static native long createRowNumberFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] partitionChannels, long maxRowsPerPartition, int hashChannel, int expectedPositions);
+    /** LimitOperatorFactory (tgpu_limit_factory_create): the first limit rows of the stream */
+    public static native long createLimitFactory(long context, int operatorId, int[] types, long limit);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);
     public static native long createOrderByFactory(long context, int operatorId, int[] types, int[] outputChannels, int expectedPositions, int[] sortChannels, int[] sortOrders);
     public static native long createMergePagesFactory(long context, int operatorId, int[] types, long minPageSizeInBytes, int minRowCount, long maxPageSizeInBytes);

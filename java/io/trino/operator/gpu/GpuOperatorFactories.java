@@ -383,6 +383,39 @@ public final class GpuOperatorFactories
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuDistinctLimitOperator", sourceTypes, poller, factory));
     }
 
+    /**
+     * RowNumberOperator.RowNumberOperatorFactory (operator/RowNumberOperator.java:61-84; LocalExecutionPlanner.visitRowNumber): the output channels, then the BIGINT
+     * number of the row inside its partition; with maxRowsPerPartition only the rows numbered up to it.  The partition types are those of the partition channels.
+     */
+    public Optional<OperatorFactory> rowNumber(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> outputChannels, List<Integer> partitionChannels,
+            Optional<Integer> maxRowsPerPartition, OptionalInt hashChannel, int expectedPositions)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createRowNumberFactory(context, operatorId, codes, ints(outputChannels), ints(partitionChannels),
+                maxRowsPerPartition.map(Integer::longValue).orElse(-1L), hashChannel.orElse(-1), expectedPositions);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuRowNumberOperator", sourceTypes, poller, factory));
+    }
+
+    /** LimitOperator.LimitOperatorFactory (operator/LimitOperator.java:34-39; LocalExecutionPlanner.visitLimit) */
+    public Optional<OperatorFactory> limit(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, long limit)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createLimitFactory(context, operatorId, codes, limit);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuLimitOperator", sourceTypes, poller, factory));
+    }
+
     /** TopNOperator.createOperatorFactory (operator/TopNOperator.java:47-62; LocalExecutionPlanner.visitTopN) */
     public Optional<OperatorFactory> topN(int operatorId, PlanNodeId planNodeId, List<Type> types, long n, List<Integer> sortChannels, List<SortOrder> sortOrders)
     {

@@ -641,6 +641,61 @@ JFN(jlong, createDistinctLimitFactory)(JNIEnv *env, jclass c, jlong ctx, jint op
     return factory_result(env, rc, f);
 }
 
+/* RowNumberOperatorFactory (operator/RowNumberOperator.java:45-119): the output channels + the BIGINT row number; maxRowsPerPartition -1 = none.
+ * Checked in front of the library: every output / partition channel in [0, types), hashChannel -1 or a BIGINT channel and only with partition
+ * channels, maxRowsPerPartition >= -1, expectedPositions > 0 */
+JFN(jlong, createRowNumberFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray partitionChannels,
+                                   jlong maxRowsPerPartition, jint hashChannel, jint expectedPositions)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types), oc = ints_get(env, outputChannels), pc = ints_get(env, partitionChannels);
+    const char *bad = NULL;
+    if (t.n <= 0) bad = "empty type array";
+    for (jsize i = 0; !bad && i < oc.n; i++)
+        if (oc.p[i] < 0 || oc.p[i] >= t.n) bad = "output channel out of range";
+    for (jsize i = 0; !bad && i < pc.n; i++)
+        if (pc.p[i] < 0 || pc.p[i] >= t.n) bad = "partition channel out of range";
+    if (!bad && (hashChannel < -1 || hashChannel >= t.n)) bad = "hash channel out of range";
+    if (!bad && hashChannel >= 0 && pc.n <= 0) bad = "hash channel without partition channels";
+    if (!bad && hashChannel >= 0 && t.p[hashChannel] != TGPU_BIGINT) bad = "hash channel is not BIGINT";
+    if (!bad && maxRowsPerPartition < -1) bad = "negative max rows per partition";
+    if (!bad && expectedPositions <= 0) bad = "expected positions must be positive";
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad)
+        rc = tgpu_row_number_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, oc.n, (const int32_t *)oc.p, pc.n, (const int32_t *)pc.p,
+                                            maxRowsPerPartition, hashChannel, expectedPositions, &f);
+    ints_release(env, &pc);
+    ints_release(env, &oc);
+    ints_release(env, &t);
+    if (bad) {
+        char message[96];
+        snprintf(message, sizeof(message), "row number: %s", bad);
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
+
+/* LimitOperatorFactory (operator/LimitOperator.java:26-60): the first `limit` rows of the stream */
+JFN(jlong, createLimitFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong limit)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types);
+    const char *bad = limit < 0 ? "negative limit" : t.n <= 0 ? "empty type array" : NULL;
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad) rc = tgpu_limit_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, limit, &f);
+    ints_release(env, &t);
+    if (bad) {
+        char message[96];
+        snprintf(message, sizeof(message), "limit: %s", bad);
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
+
 /* TopNOperator.createOperatorFactory (M/operator/TopNOperator.java:47-62); sortOrders: tgpu_sort_order = SortOrder's ordinal (S/connector/SortOrder.java:18-21) */
 JFN(jlong, createTopNFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong n, jintArray sortChannels, jintArray sortOrders)
 {

@@ -10,5 +10,6 @@ from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_
                         Context, FilterAndProjectOperatorFactory, ScanFilterAndProjectOperatorFactory, PageSource, RecordCursor, FilterProjectHashAggregationOperatorFactory, FilterProjectLookupJoinOperatorFactory, GroupByHash, HashAggregationOperatorFactory, HashBuilderOperatorFactory,
                         LookupJoinOperatorFactory, LookupOuterOperatorFactory, Operator, OperatorFactory, page_processor_source, fused_probe_launch_counts, precompile_fused_aggregation, precompile_fused_probe, precompile_page_processor, to_pages,
                         SET_BITMAP, SET_GENERIC, SET_HASH, HashSemiJoinOperatorFactory, SetBuilderOperatorFactory, SetSupplier,
-                        DistinctLimitOperatorFactory, MarkDistinctOperatorFactory)
+                        DistinctLimitOperatorFactory, MarkDistinctOperatorFactory,
+                        LimitOperatorFactory, RowNumberOperatorFactory)
 from .spi import (BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR, Block, DeviceBlock, DictionaryBlock, LazyBlock, OutputPage, Page, RunLengthEncodedBlock)

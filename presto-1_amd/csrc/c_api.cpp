@@ -1285,6 +1285,33 @@ int32_t tgpu_distinct_limit_factory_create(tgpu_context *ctx, int32_t operator_i
     });
 }
 
+int32_t tgpu_row_number_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t output_channel_count,
+                                       const int32_t *output_channels, int32_t partition_channel_count, const int32_t *partition_channels,
+                                       int64_t max_rows_per_partition, int32_t hash_channel, int32_t expected_positions, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && out, "null argument");
+        auto f = std::make_unique<tgpu_operator_factory>();
+        f->f = std::make_unique<RowNumberOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(output_channels, output_channel_count),
+                                                          vec(partition_channels, partition_channel_count), max_rows_per_partition, hash_channel, expected_positions);
+        f->ctx = ctx->ctx.get();
+        retain(f->ctx);
+        *out = f.release();
+    });
+}
+
+int32_t tgpu_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t limit, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && out, "null argument");
+        auto f = std::make_unique<tgpu_operator_factory>();
+        f->f = std::make_unique<LimitOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), limit);
+        f->ctx = ctx->ctx.get();
+        retain(f->ctx);
+        *out = f.release();
+    });
+}
+
 int32_t tgpu_merge_pages_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t min_page_size_in_bytes,
                                         int32_t min_row_count, int64_t max_page_size_in_bytes, tgpu_operator_factory **out)
 {

@@ -11,6 +11,7 @@
 #include "kernels.h"
 
 #include <cstdlib>
+#include <cstring>
 
 namespace tgpu {
 
@@ -2485,6 +2486,199 @@ std::unique_ptr<Operator> DistinctLimitOperatorFactory::create_operator()
 std::unique_ptr<OperatorFactory> DistinctLimitOperatorFactory::duplicate()   // DistinctLimitOperator.java:94-98
 {
     return std::make_unique<DistinctLimitOperatorFactory>(ctx_, operator_id_, types_, distinct_channels_, limit_, hash_channel_);
+}
+
+// =====================================================================================================================
+// RowNumberOperator (M/operator/RowNumberOperator.java:121-364): row_number() OVER (PARTITION BY k), with or without `<= n`.  Output =
+// the output channels, then the BIGINT row number (len(outputChannels) + 1 channels in both modes; the reference's no-limit path sizes
+// its block array by the INPUT page's channel count, :291, which leaves holes when the output channels are a strict subset -- not
+// reproduced).  One page at a time: needs_input is false while a page's result is pending.  Partitioned: one GroupByHashGpu, then the
+// ranking kernels of rownumber.hip.  Not partitioned: the count is a host int64 and the only kernel is the iota of the new column.
+// =====================================================================================================================
+class RowNumberOperator : public Operator {
+public:
+    RowNumberOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &output_channels,
+                      const std::vector<int32_t> &partition_channels, int64_t max_rows, int32_t hash_channel, int32_t expected_positions)
+        : Operator(ctx, id), types_(types), output_channels_(output_channels), partition_channels_(partition_channels), max_rows_(max_rows), hash_channel_(hash_channel),
+          numberer_(ctx, types_of_channels(types, partition_channels), hash_channel >= 0, expected_positions, max_rows)
+    {
+        // TGPU_ROW_NUMBER_PATH=sort, read here: every page down the sort path instead of the choice by group count (the baseline of
+        // tools/exp_row_number.py; the tests reach the sort path with few groups through it)
+        const char *e = getenv("TGPU_ROW_NUMBER_PATH");
+        numberer_.force_sort(e != nullptr && !strcmp(e, "sort"));
+    }
+
+    bool needs_input() override   // :201-209
+    {
+        if (single_partition_done()) return false;
+        return !finishing_ && !pending_;
+    }
+    void add_input(const tgpu_page *page) override
+    {
+        ready();
+        emit(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        ready();
+        emit(DevicePage(page));
+    }
+    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    void finish() override { finishing_ = true; }
+    bool is_finished() override   // :188-199; a partitioned operator never finishes early
+    {
+        if (pending_) return false;
+        return finishing_ || single_partition_done();
+    }
+    int64_t memory_bytes() override { return numberer_.estimated_size(); }   // :266
+
+private:
+    bool single_partition_done() const { return !numberer_.partitioned() && max_rows_ >= 0 && count_ == max_rows_; }
+    void ready()
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        TG_CHECK_STATE(!pending_, "Operator still has pending output");
+        TG_CHECK_STATE(!single_partition_done(), "Operator does not need input");
+    }
+
+    void emit(DevicePage in)   // :225-247
+    {
+        check_page_types(in, types_);
+        DevicePage out;
+        if (!numberer_.partitioned()) {
+            const int64_t take = max_rows_ >= 0 ? std::min(in.n, max_rows_ - count_) : in.n;
+            if (max_rows_ >= 0 && take == 0) return;   // an empty PageBuilder is no page (:335-337)
+            for (int32_t ch : output_channels_) out.cols.push_back(in.cols[(size_t)ch]);
+            own_borrowed_columns(ctx_, out);   // the channels pass through: the output outlives the call
+            if (take < in.n)
+                for (DeviceColumn &c : out.cols) c = k::region_of(ctx_, c, 0, take);
+            out.n = take;
+            out.cols.push_back(numberer_.iota(count_, take));
+            count_ += take;
+            pending_ = wrap(std::move(out));
+            return;
+        }
+        std::vector<const DeviceColumn *> keys;
+        for (int32_t ch : partition_channels_) keys.push_back(&in.cols[(size_t)ch]);
+        const int64_t *hashes = hash_channel_ >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel_].values : nullptr;
+        if (max_rows_ < 0) {   // getRowsWithRowNumber (:289-299)
+            DeviceColumn rn = numberer_.number(keys, hashes, in.n);
+            for (int32_t ch : output_channels_) out.cols.push_back(in.cols[(size_t)ch]);
+            own_borrowed_columns(ctx_, out);
+            out.n = in.n;
+            out.cols.push_back(std::move(rn));
+            pending_ = wrap(std::move(out));
+            return;
+        }
+        const int32_t *positions = nullptr;   // getSelectedRows (:313-342)
+        DeviceColumn rn;
+        const int64_t kept = numberer_.select(keys, hashes, in.n, &positions, &rn);
+        if (kept == 0) return;
+        out.n = kept;
+        for (int32_t ch : output_channels_) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)ch], positions, kept, false));
+        out.cols.push_back(std::move(rn));
+        pending_ = wrap(std::move(out));
+    }
+
+    std::vector<int32_t> types_, output_channels_, partition_channels_;
+    int64_t max_rows_;
+    int32_t hash_channel_;
+    RowNumbererGpu numberer_;
+    int64_t count_ = 0;   // partitionRowCount.get(0) of the single partition
+    std::unique_ptr<OutputPage> pending_;
+    bool finishing_ = false;
+};
+
+RowNumberOperatorFactory::RowNumberOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> output_channels,
+                                                   std::vector<int32_t> partition_channels, int64_t max_rows_per_partition, int32_t hash_channel,
+                                                   int32_t expected_positions)
+    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), output_channels_(std::move(output_channels)), partition_channels_(std::move(partition_channels)),
+      max_rows_(max_rows_per_partition), hash_channel_(hash_channel), expected_positions_(expected_positions)
+{
+    TG_CHECK_ARG(!types_.empty(), "row number needs at least one source channel");
+    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown type");
+    for (int32_t ch : output_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)types_.size(), "output channel out of range");
+    TG_CHECK_ARG((int)partition_channels_.size() <= kMaxKeyChannels, "at most 8 key channels are supported");
+    for (int32_t ch : partition_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)types_.size(), "partition channel out of range");
+    TG_CHECK_ARG(hash_channel_ >= -1 && hash_channel_ < (int)types_.size(), "hash channel out of range");
+    TG_CHECK_ARG(hash_channel_ < 0 || !partition_channels_.empty(), "a hash channel needs partition channels");
+    TG_CHECK_ARG(hash_channel_ < 0 || types_[(size_t)hash_channel_] == TGPU_BIGINT, "hash channel must be BIGINT");
+    TG_CHECK_ARG(max_rows_ >= -1 && max_rows_ <= 0x7fffffffLL, "max rows per partition must be -1 (none) or a non-negative int");
+    TG_CHECK_ARG(expected_positions_ > 0, "expected positions must be positive");
+}
+
+std::unique_ptr<Operator> RowNumberOperatorFactory::create_operator()
+{
+    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    return std::make_unique<RowNumberOperator>(ctx_, operator_id_, types_, output_channels_, partition_channels_, max_rows_, hash_channel_, expected_positions_);
+}
+
+std::unique_ptr<OperatorFactory> RowNumberOperatorFactory::duplicate()   // RowNumberOperator.java:114-118
+{
+    return std::make_unique<RowNumberOperatorFactory>(ctx_, operator_id_, types_, output_channels_, partition_channels_, max_rows_, hash_channel_, expected_positions_);
+}
+
+// =====================================================================================================================
+// LimitOperator (M/operator/LimitOperator.java:62-119): whole pages pass through while they fit, the crossing page is a region of its
+// first `remaining` rows, finish() zeroes the remainder.  No kernel.
+// =====================================================================================================================
+class LimitOperator : public Operator {
+public:
+    LimitOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, int64_t limit) : Operator(ctx, id), types_(types), remaining_(limit) {}
+
+    bool needs_input() override { return remaining_ > 0 && !pending_; }   // :92-96
+    void add_input(const tgpu_page *page) override
+    {
+        TG_CHECK_STATE(needs_input(), "Operator does not need input");   // :101
+        emit(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        TG_CHECK_STATE(needs_input(), "Operator does not need input");
+        emit(DevicePage(page));
+    }
+    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    void finish() override { remaining_ = 0; }                                    // :80-84
+    bool is_finished() override { return remaining_ == 0 && !pending_; }          // :86-90
+
+private:
+    void emit(DevicePage in)   // :98-111
+    {
+        check_page_types(in, types_);
+        own_borrowed_columns(ctx_, in);
+        if (in.n <= remaining_) {
+            remaining_ -= in.n;
+        }
+        else {
+            for (DeviceColumn &c : in.cols) c = k::region_of(ctx_, c, 0, remaining_);
+            in.n = remaining_;
+            remaining_ = 0;
+        }
+        pending_ = wrap(std::move(in));
+    }
+
+    std::vector<int32_t> types_;
+    int64_t remaining_;
+    std::unique_ptr<OutputPage> pending_;
+};
+
+LimitOperatorFactory::LimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t limit)
+    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), limit_(limit)
+{
+    TG_CHECK_ARG(!types_.empty(), "limit needs at least one source channel");
+    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown type");
+    TG_CHECK_ARG(limit_ >= 0, "limit must be at least zero");   // :70
+}
+
+std::unique_ptr<Operator> LimitOperatorFactory::create_operator()
+{
+    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    return std::make_unique<LimitOperator>(ctx_, operator_id_, types_, limit_);
+}
+
+std::unique_ptr<OperatorFactory> LimitOperatorFactory::duplicate()   // LimitOperator.java:55-59
+{
+    return std::make_unique<LimitOperatorFactory>(ctx_, operator_id_, types_, limit_);
 }
 
 void Operator::add_input_owned(const DevicePage &page)

@@ -10,6 +10,7 @@
 #include "distinct.h"
 #include "groupby.h"
 #include "jit.h"
+#include "rownumber.h"
 #include "join.h"
 #include "semijoin.h"
 #include "topn.h"
@@ -421,6 +422,36 @@ private:
     std::vector<int32_t> types_, distinct_channels_;
     int64_t limit_;
     int32_t hash_channel_;
+};
+
+// ---- RowNumberOperator (M/operator/RowNumberOperator.java:43-364) --------------------------------------------------------------------
+class RowNumberOperatorFactory : public OperatorFactory {
+public:
+    RowNumberOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> output_channels, std::vector<int32_t> partition_channels,
+                             int64_t max_rows_per_partition /* -1 = none */, int32_t hash_channel, int32_t expected_positions);
+    std::unique_ptr<Operator> create_operator() override;
+    std::unique_ptr<OperatorFactory> duplicate() override;
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::vector<int32_t> types_, output_channels_, partition_channels_;
+    int64_t max_rows_;
+    int32_t hash_channel_, expected_positions_;
+};
+
+// ---- LimitOperator (M/operator/LimitOperator.java:25-120) ---------------------------------------------------------------------------
+class LimitOperatorFactory : public OperatorFactory {
+public:
+    LimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t limit);
+    std::unique_ptr<Operator> create_operator() override;
+    std::unique_ptr<OperatorFactory> duplicate() override;
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::vector<int32_t> types_;
+    int64_t limit_;
 };
 
 // ---- TopNOperator (M/operator/TopNOperator.java:47-62,135-225) ----------------------------------------------------------

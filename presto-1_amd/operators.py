@@ -801,6 +801,33 @@ class DistinctLimitOperatorFactory(OperatorFactory):
         super().__init__(h)
 
 
+class RowNumberOperatorFactory(OperatorFactory):
+    """RowNumberOperator.RowNumberOperatorFactory (M/operator/RowNumberOperator.java:43-119): `output_channels`, then the BIGINT number of
+    the row inside its partition (the rows equal on `partition_channels`; none = one partition), counted from 1 in arrival order.  With
+    `max_rows_per_partition` only the rows numbered up to it come out."""
+
+    def __init__(self, ctx: Context, operator_id, source_types, output_channels, partition_channels, max_rows_per_partition=None, hash_channel=-1,
+                 expected_positions=10):
+        t, nt = _i32(source_types)
+        o, no = _i32(output_channels)
+        p, np_ = _i32(partition_channels)
+        h = C.c_void_p()
+        m = -1 if max_rows_per_partition is None else int(max_rows_per_partition)
+        _lib.check(_lib.lib().tgpu_row_number_factory_create(ctx.handle, operator_id, nt, t, no, o, np_, p, m, int(hash_channel), int(expected_positions), C.byref(h)))
+        super().__init__(h)
+
+
+class LimitOperatorFactory(OperatorFactory):
+    """LimitOperator.LimitOperatorFactory (M/operator/LimitOperator.java:27-60): the first `limit` rows of the stream; whole pages pass
+    through, the crossing page is cut."""
+
+    def __init__(self, ctx: Context, operator_id, source_types, limit):
+        t, nt = _i32(source_types)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_limit_factory_create(ctx.handle, operator_id, nt, t, int(limit), C.byref(h)))
+        super().__init__(h)
+
+
 class MergePagesOperatorFactory(OperatorFactory):
     """MergePages.mergePages (M/operator/project/MergePages.java:64-96) as an operator: small pages are coalesced in HBM, big ones pass through"""
 
