@@ -496,14 +496,6 @@ __global__ void __launch_bounds__(kBlock) agg_evaluate_kernel(EvalArgs args, int
     }
 }
 
-int grid_for(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, kBlock);
-    int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 bool is_double_state(int32_t f) { return f == TGPU_AGG_SUM_DOUBLE || f == TGPU_AGG_AVG_DOUBLE || f == TGPU_AGG_AVG_BIGINT; }
 bool is_count(int32_t f) { return f == TGPU_AGG_COUNT_ALL || f == TGPU_AGG_COUNT_COLUMN; }
 bool is_minmax(int32_t f) { return f >= TGPU_AGG_MIN_BIGINT && f <= TGPU_AGG_MAX_DOUBLE; }

@@ -10,15 +10,6 @@ namespace k {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 
-static inline int grid_for(Context *ctx, int64_t n, int per_block = kBlock)
-{
-    int64_t blocks = ceil_div(n, per_block);
-    int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // scan: three-level (tile reduce -> scan of tile sums -> tile scan).  Tile = 256 threads x 8 items.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -262,6 +253,17 @@ void widen_i32_to_i64(Context *ctx, const int32_t *in, int64_t *out, int64_t n)
     if (n <= 0) return;
     widen_kernel<<<grid_for(ctx, n), kBlock, 0, ctx->stream()>>>(in, out, n);
     check_launch("widen");
+}
+
+__global__ void __launch_bounds__(kBlock) compact_positions_kernel(const int32_t *__restrict__ flags, const int32_t *__restrict__ rank, int64_t n, int32_t *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        if (flags[i]) out[rank[i]] = (int32_t)i;
+}
+void compact_positions(Context *ctx, const int32_t *flags, const int32_t *rank, int64_t n, int32_t *out)
+{
+    if (n <= 0) return;
+    compact_positions_kernel<<<grid_for(ctx, n), kBlock, 0, ctx->stream()>>>(flags, rank, n, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -105,6 +105,17 @@ void drop(Context *c)
     delete w;
 }
 
+// wraps a new factory F(ctx, operator_id, args...) into the handle *out, which keeps the context alive
+template <class F, class... Args> void make_factory(tgpu_context *ctx, tgpu_operator_factory **out, int32_t operator_id, Args &&...args)
+{
+    TG_CHECK_ARG(ctx && out, "null argument");
+    auto f = std::make_unique<tgpu_operator_factory>();
+    f->f = std::make_unique<F>(ctx->ctx.get(), operator_id, std::forward<Args>(args)...);
+    f->ctx = ctx->ctx.get();
+    retain(f->ctx);
+    *out = f.release();
+}
+
 tgpu_output_page *release_output(std::unique_ptr<OutputPage> o)
 {
     retain(o->ctx);
@@ -244,12 +255,7 @@ int32_t tgpu_filter_project_factory_create(tgpu_context *ctx, int32_t operator_i
                                            const tgpu_page_processor_spec *spec, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<FilterAndProjectOperatorFactory>(ctx->ctx.get(), operator_id, vec(input_types, input_type_count), spec);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<FilterAndProjectOperatorFactory>(ctx, out, operator_id, FilterAndProjectConfig{PageProcessorGpu::shared(vec(input_types, input_type_count), spec)});
     });
 }
 
@@ -258,11 +264,8 @@ int32_t tgpu_scan_filter_project_factory_create(tgpu_context *ctx, int32_t opera
 {
     return guard_on(ctx_of(ctx), [&] {
         TG_CHECK_ARG(ctx && out && spec, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<ScanFilterAndProjectOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), spec);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        std::vector<int32_t> t = vec(types, type_count);
+        make_factory<ScanFilterAndProjectOperatorFactory>(ctx, out, operator_id, ScanFilterAndProjectConfig{t, PageProcessorGpu::shared(t, spec)});
     });
 }
 
@@ -444,11 +447,7 @@ int32_t tgpu_hash_aggregation_factory_create(tgpu_context *ctx, int32_t operator
         cfg.expected_groups = expected_groups;
         cfg.produce_default_output = produce_default_output != 0;
         if (const char *env = getenv("TGPU_MAX_PARTIAL_AGGREGATION_MEMORY")) cfg.max_partial_memory = atoll(env);
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<HashAggregationOperatorFactory>(ctx->ctx.get(), operator_id, std::move(cfg));
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<HashAggregationOperatorFactory>(ctx, out, operator_id, std::move(cfg));
     });
 }
 
@@ -495,14 +494,10 @@ int32_t tgpu_partitioned_hash_builder_factory_create(tgpu_context *ctx, int32_t 
         cfg.partition_count = partition_count;
         auto bridge = std::make_unique<tgpu_lookup_source_factory>();
         bridge->bridge = std::make_shared<LookupSourceFactory>();
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<HashBuilderOperatorFactory>(ctx->ctx.get(), operator_id, std::move(cfg), bridge->bridge);
+        make_factory<HashBuilderOperatorFactory>(ctx, out, operator_id, std::move(cfg), bridge->bridge);
         bridge->ctx = ctx->ctx.get();
         retain(bridge->ctx);
         *bridge_out = bridge.release();
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
     });
 }
 
@@ -511,13 +506,7 @@ int32_t tgpu_top_n_factory_create(tgpu_context *ctx, int32_t operator_id, int32_
                                   tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<TopNOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), n, vec(sort_channels, sort_channel_count),
-                                                     vec(sort_orders, sort_channel_count));
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<TopNOperatorFactory>(ctx, out, operator_id, TopNConfig{vec(types, type_count), n, vec(sort_channels, sort_channel_count), vec(sort_orders, sort_channel_count)});
     });
 }
 
@@ -527,14 +516,9 @@ int32_t tgpu_order_by_factory_create(tgpu_context *ctx, int32_t operator_id, int
                                      tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
         (void)expected_positions;   // a sizing hint of the reference's PagesIndex; the device store grows by doubling
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<OrderByOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(output_channels, output_channel_count),
-                                                        vec(sort_channels, sort_channel_count), vec(sort_orders, sort_channel_count));
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<OrderByOperatorFactory>(ctx, out, operator_id, OrderByConfig{vec(types, type_count), vec(output_channels, output_channel_count),
+                                                                                    vec(sort_channels, sort_channel_count), vec(sort_orders, sort_channel_count)});
     });
 }
 
@@ -595,11 +579,7 @@ int32_t tgpu_lookup_join_factory_create(tgpu_context *ctx, int32_t operator_id, 
         cfg.probe_output_channels = vec(probe_output_channels, probe_output_channel_count);
         cfg.probe_hash_channel = probe_hash_channel;
         cfg.join_type = join_type;
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<LookupJoinOperatorFactory>(ctx->ctx.get(), operator_id, std::move(cfg), bridge->bridge);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<LookupJoinOperatorFactory>(ctx, out, operator_id, std::move(cfg), bridge->bridge);
     });
 }
 
@@ -615,11 +595,7 @@ int32_t tgpu_filter_project_lookup_join_factory_create(tgpu_context *ctx, int32_
         cfg.probe_output_channels = vec(probe_output_channels, probe_output_channel_count);
         cfg.probe_hash_channel = probe_hash_channel;
         cfg.join_type = join_type;
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<FusedFilterProjectJoinOperatorFactory>(ctx->ctx.get(), operator_id, vec(input_types, input_type_count), spec, std::move(cfg), bridge->bridge);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<FusedFilterProjectJoinOperatorFactory>(ctx, out, operator_id, vec(input_types, input_type_count), spec, std::move(cfg), bridge->bridge);
     });
 }
 
@@ -640,11 +616,7 @@ int32_t tgpu_filter_project_hash_aggregation_factory_create(tgpu_context *ctx, i
         cfg.aggs.assign(aggs, aggs + agg_count);
         cfg.expected_groups = expected_groups;
         if (const char *env = getenv("TGPU_MAX_PARTIAL_AGGREGATION_MEMORY")) cfg.max_partial_memory = atoll(env);
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<FusedFilterProjectAggregationOperatorFactory>(ctx->ctx.get(), operator_id, vec(input_types, input_type_count), spec, std::move(cfg));
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<FusedFilterProjectAggregationOperatorFactory>(ctx, out, operator_id, vec(input_types, input_type_count), spec, std::move(cfg));
     });
 }
 
@@ -829,8 +801,8 @@ int32_t tgpu_hash_aggregation_factory_set_max_partial_memory(tgpu_operator_facto
     return guard_on(ctx_of(factory), [&] {
         TG_CHECK_ARG(factory != nullptr && factory->f, "factory is null");
         TG_CHECK_ARG(bytes >= 0, "maxPartialMemory must not be negative");
-        if (auto *f = dynamic_cast<HashAggregationOperatorFactory *>(factory->f.get())) f->set_max_partial_memory(bytes);
-        else if (auto *g = dynamic_cast<FusedFilterProjectAggregationOperatorFactory *>(factory->f.get())) g->set_max_partial_memory(bytes);
+        if (auto *f = dynamic_cast<HashAggregationOperatorFactory *>(factory->f.get())) f->config().max_partial_memory = bytes;
+        else if (auto *g = dynamic_cast<FusedFilterProjectAggregationOperatorFactory *>(factory->f.get())) g->config().max_partial_memory = bytes;
         else fail(TGPU_ERR_NOT_SUPPORTED, "only hash aggregation factories have a partial-aggregation memory limit");
     });
 }
@@ -839,8 +811,8 @@ int32_t tgpu_hash_aggregation_factory_set_spill_enabled(tgpu_operator_factory *f
 {
     return guard_on(ctx_of(factory), [&] {
         TG_CHECK_ARG(factory != nullptr && factory->f, "factory is null");
-        if (auto *f = dynamic_cast<HashAggregationOperatorFactory *>(factory->f.get())) f->set_spill_enabled(enabled != 0);
-        else if (auto *g = dynamic_cast<FusedFilterProjectAggregationOperatorFactory *>(factory->f.get())) g->set_spill_enabled(enabled != 0);
+        if (auto *f = dynamic_cast<HashAggregationOperatorFactory *>(factory->f.get())) f->config().spill_enabled = enabled != 0;
+        else if (auto *g = dynamic_cast<FusedFilterProjectAggregationOperatorFactory *>(factory->f.get())) g->config().spill_enabled = enabled != 0;
         else fail(TGPU_ERR_NOT_SUPPORTED, "only hash aggregation factories can spill");
     });
 }
@@ -1167,11 +1139,7 @@ int32_t tgpu_lookup_outer_factory_create(tgpu_context *ctx, int32_t operator_id,
 {
     return guard_on(ctx_of(ctx), [&] {
         TG_CHECK_ARG(ctx && bridge && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<LookupOuterOperatorFactory>(ctx->ctx.get(), operator_id, vec(probe_output_types, probe_output_type_count), bridge->bridge);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<LookupOuterOperatorFactory>(ctx, out, operator_id, vec(probe_output_types, probe_output_type_count), bridge->bridge);
     });
 }
 
@@ -1180,13 +1148,8 @@ int32_t tgpu_dynamic_filter_source_factory_create(tgpu_context *ctx, int32_t ope
                                                   int32_t min_max_collection_limit, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<DynamicFilterSourceOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(channels, channel_count), max_distinct_values,
-                                                                    max_filter_size_in_bytes, min_max_collection_limit);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<DynamicFilterSourceOperatorFactory>(
+            ctx, out, operator_id, DynamicFilterSourceConfig{vec(types, type_count), vec(channels, channel_count), max_distinct_values, max_filter_size_in_bytes, min_max_collection_limit});
     });
 }
 
@@ -1212,14 +1175,10 @@ int32_t tgpu_set_builder_factory_create(tgpu_context *ctx, int32_t operator_id, 
         TG_CHECK_ARG(valid_type(t[(size_t)set_channel]), "unknown type");
         auto supplier = std::make_unique<tgpu_set_supplier>();
         supplier->supplier = std::make_shared<SetSupplier>(t[(size_t)set_channel]);
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<SetBuilderOperatorFactory>(ctx->ctx.get(), operator_id, std::move(t), set_channel, hash_channel, supplier->supplier);
+        make_factory<SetBuilderOperatorFactory>(ctx, out, operator_id, std::move(t), set_channel, hash_channel, supplier->supplier);
         supplier->ctx = ctx->ctx.get();
         retain(supplier->ctx);
         *supplier_out = supplier.release();
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
     });
 }
 
@@ -1228,12 +1187,7 @@ int32_t tgpu_hash_semi_join_factory_create(tgpu_context *ctx, int32_t operator_i
 {
     return guard_on(ctx_of(ctx), [&] {
         TG_CHECK_ARG(ctx && supplier && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<HashSemiJoinOperatorFactory>(ctx->ctx.get(), operator_id, supplier->supplier, vec(probe_types, probe_type_count), probe_join_channel,
-                                                             probe_hash_channel);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<HashSemiJoinOperatorFactory>(ctx, out, operator_id, HashSemiJoinConfig{supplier->supplier, vec(probe_types, probe_type_count), probe_join_channel, probe_hash_channel});
     });
 }
 
@@ -1262,12 +1216,7 @@ int32_t tgpu_mark_distinct_factory_create(tgpu_context *ctx, int32_t operator_id
                                           const int32_t *mark_channels, int32_t hash_channel, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<MarkDistinctOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(mark_channels, mark_channel_count), hash_channel);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<MarkDistinctOperatorFactory>(ctx, out, operator_id, MarkDistinctConfig{vec(types, type_count), vec(mark_channels, mark_channel_count), hash_channel});
     });
 }
 
@@ -1275,13 +1224,7 @@ int32_t tgpu_distinct_limit_factory_create(tgpu_context *ctx, int32_t operator_i
                                            const int32_t *distinct_channels, int64_t limit, int32_t hash_channel, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<DistinctLimitOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(distinct_channels, distinct_channel_count),
-                                                              limit, hash_channel);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<DistinctLimitOperatorFactory>(ctx, out, operator_id, DistinctLimitConfig{vec(types, type_count), vec(distinct_channels, distinct_channel_count), limit, hash_channel});
     });
 }
 
@@ -1290,25 +1233,16 @@ int32_t tgpu_row_number_factory_create(tgpu_context *ctx, int32_t operator_id, i
                                        int64_t max_rows_per_partition, int32_t hash_channel, int32_t expected_positions, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<RowNumberOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(output_channels, output_channel_count),
-                                                          vec(partition_channels, partition_channel_count), max_rows_per_partition, hash_channel, expected_positions);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<RowNumberOperatorFactory>(ctx, out, operator_id,
+                                               RowNumberConfig{vec(types, type_count), vec(output_channels, output_channel_count), vec(partition_channels, partition_channel_count),
+                                                               max_rows_per_partition, hash_channel, expected_positions});
     });
 }
 
 int32_t tgpu_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t limit, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<LimitOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), limit);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<LimitOperatorFactory>(ctx, out, operator_id, LimitConfig{vec(types, type_count), limit});
     });
 }
 
@@ -1316,12 +1250,7 @@ int32_t tgpu_merge_pages_factory_create(tgpu_context *ctx, int32_t operator_id, 
                                         int32_t min_row_count, int64_t max_page_size_in_bytes, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<MergePagesOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), min_page_size_in_bytes, min_row_count, max_page_size_in_bytes);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<MergePagesOperatorFactory>(ctx, out, operator_id, MergePagesConfig{vec(types, type_count), min_page_size_in_bytes, min_row_count, max_page_size_in_bytes});
     });
 }
 
@@ -1330,13 +1259,9 @@ int32_t tgpu_partitioned_output_factory_create(tgpu_context *ctx, int32_t operat
                                                int32_t null_channel, int32_t partition_function, tgpu_operator_factory **out)
 {
     return guard_on(ctx_of(ctx), [&] {
-        TG_CHECK_ARG(ctx && out, "null argument");
-        auto f = std::make_unique<tgpu_operator_factory>();
-        f->f = std::make_unique<PartitionedOutputOperatorFactory>(ctx->ctx.get(), operator_id, vec(types, type_count), vec(partition_channels, partition_channel_count),
-                                                                  hash_channel, partition_count, replicates_any_row != 0, null_channel, partition_function);
-        f->ctx = ctx->ctx.get();
-        retain(f->ctx);
-        *out = f.release();
+        make_factory<PartitionedOutputOperatorFactory>(ctx, out, operator_id,
+                                                       PartitionedOutputConfig{vec(types, type_count), vec(partition_channels, partition_channel_count), hash_channel, partition_count,
+                                                                               replicates_any_row != 0, null_channel, partition_function});
     });
 }
 

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -275,6 +276,19 @@ inline void check_launch(const char *what)
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the grid of a grid-stride kernel over n rows: one block per `rows_per_block` rows, at most 8 blocks per CU, at least one
+inline int grid_for(Context *ctx, int64_t n, int64_t rows_per_block = 256)
+{
+    return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, rows_per_block), (int64_t)ctx->cu_count() * 8));
+}
+
+// a scratch buffer that persists between calls: replaced (at least doubled) when it is smaller than `need` bytes
+inline void grow(Context *ctx, BufferPtr &buf, size_t need)
+{
+    if (buf && buf->bytes() >= need) return;
+    buf = ctx->alloc(std::max(need, buf ? buf->bytes() * 2 : (size_t)0));
+}
 
 // ---- device columns: always FLAT in HBM (dictionary / RLE inputs are flattened at ingest) ---------------------------
 // Layout in HBM = the reference's block arrays: values[n] (8/4/1 bytes), nulls[n] one byte per row or absent,

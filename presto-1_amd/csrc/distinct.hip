@@ -22,14 +22,6 @@ constexpr int kBlock = 256;
 constexpr int kRows = 4;   // rows in flight per lane
 constexpr int32_t kNoRow = 0x7fffffff;
 
-int grid_for(Context *ctx, int64_t n, int64_t rows_per_block)
-{
-    int64_t blocks = ceil_div(n, rows_per_block);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 // first_row[g - g0] = min(row : gids[row] == g) for every g in [g0, g0 + count).  A run of equal ids over neighbouring lanes sends its
 // first lane only (rows grow with the lane, so that is the run's minimum), as the group-by probe dedupes its runs.  Ids that repeat
 // further apart meet in memory: first_row only ever falls, so a row that reads a value at or below its own number has nothing to add
@@ -65,12 +57,6 @@ __global__ void __launch_bounds__(kBlock) distinct_scatter_kernel(const int32_t 
         const int64_t r = first_row[k];
         if (r < n) mark[r] = 1;   // every new group has a row; kNoRow would mean it had none
     }
-}
-
-void grow(Context *ctx, BufferPtr &buf, size_t need)
-{
-    if (buf && buf->bytes() >= need) return;
-    buf = ctx->alloc(std::max(need, buf ? buf->bytes() * 2 : (size_t)0));
 }
 
 }  // namespace

@@ -190,14 +190,6 @@ __global__ void __launch_bounds__(kBlock) gbh_rehash_kernel(const int64_t *__res
     }
 }
 
-int grid_for(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, kBlock);
-    int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 // fastutil HashCommon.arraySize + BigintGroupByHash.calculateMaxFill, to report the Java table's capacity
 int32_t java_array_size(int32_t expected)
 {

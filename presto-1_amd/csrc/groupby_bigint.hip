@@ -314,14 +314,6 @@ __global__ void __launch_bounds__(kBlock) gbi_rehash_kernel(const KT *__restrict
     }
 }
 
-int grid_for(Context *ctx, int64_t n, int per_block)
-{
-    int64_t blocks = ceil_div(n, per_block);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 }  // namespace
 
 BigintGroupTable::BigintGroupTable(Context *ctx, int32_t type) : ctx_(ctx), type_(type), width_(type_width(type)) {}

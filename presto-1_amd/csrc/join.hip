@@ -26,14 +26,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-int grid_for(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, kBlock);
-    int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 using Slot16 = TgSlot16;
 
 // EQUAL operators on non-null cells (S/type/AbstractLongType.java:132-136, DoubleType.java:157-161: NaN != NaN, -0 == +0)
@@ -1090,11 +1082,6 @@ __global__ void __launch_bounds__(kBlock) unvisited_flags_kernel(const uint8_t *
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) flags[i] = (visited && visited[i]) ? 0 : 1;
 }
-__global__ void __launch_bounds__(kBlock) compact_positions_kernel(const int32_t *__restrict__ flags, const int32_t *__restrict__ rank, int64_t n, int32_t *__restrict__ out)
-{
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        if (flags[i]) out[rank[i]] = (int32_t)i;
-}
 }  // namespace
 
 void LookupSourceGpu::mark_visited(const int32_t *build_positions, int64_t n)
@@ -1117,7 +1104,7 @@ void LookupSourceGpu::unvisited_positions(BufferPtr &positions, int64_t &count)
     unvisited_flags_kernel<<<grid_for(ctx_, n_), kBlock, 0, ctx_->stream()>>>(visited_ ? visited_->as<uint8_t>() : nullptr, n_, flags->as<int32_t>());
     check_launch("unvisited_flags");
     k::exclusive_scan_i32(ctx_, flags->as<int32_t>(), rank->as<int32_t>(), n_, total->as<int64_t>());
-    compact_positions_kernel<<<grid_for(ctx_, n_), kBlock, 0, ctx_->stream()>>>(flags->as<int32_t>(), rank->as<int32_t>(), n_, positions->as<int32_t>());
+    k::compact_positions(ctx_, flags->as<int32_t>(), rank->as<int32_t>(), n_, positions->as<int32_t>());
     check_launch("compact_positions");
     count = ctx_->read_scalar(total->as<int64_t>());
 }

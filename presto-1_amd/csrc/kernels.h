@@ -20,6 +20,8 @@ void fill_i32(Context *ctx, int32_t *p, int32_t v, int64_t n);
 void fill_u64(Context *ctx, uint64_t *p, uint64_t v, int64_t n);
 void iota_i32(Context *ctx, int32_t *p, int64_t n);
 void widen_i32_to_i64(Context *ctx, const int32_t *in, int64_t *out, int64_t n);
+// stream compaction behind exclusive_scan_i32: out[rank[i]] = i for every i whose flag is set (the caller checks the launch)
+void compact_positions(Context *ctx, const int32_t *flags, const int32_t *rank, int64_t n, int32_t *out);
 // any-null over the key columns: out[i] = 1 if any key cell of row i is null
 void any_null(Context *ctx, const KeyCols &keys, int64_t n, uint8_t *out);
 // K10: partition id per row = (raw & 0x7fff...) % partitions (HashGenerator, remote exchanges), or with `local` the

@@ -34,6 +34,88 @@ static bool page_is_retained(Context *ctx, const DevicePage &in, const tgpu_page
     return true;
 }
 
+// ---- what the operators below share ---------------------------------------------------------------------------------------------------
+namespace {
+std::vector<int32_t> types_of_channels(const std::vector<int32_t> &types, const std::vector<int32_t> &channels)
+{
+    std::vector<int32_t> out;
+    for (int32_t ch : channels) out.push_back(types[(size_t)ch]);
+    return out;
+}
+
+void check_page_types(const DevicePage &in, const std::vector<int32_t> &types)
+{
+    TG_CHECK_ARG(in.cols.size() == types.size(), "page channel count does not match the operator's types");
+    for (size_t i = 0; i < types.size(); i++) TG_CHECK_ARG(in.cols[i].type == types[i], "page channel type does not match the operator's types");
+}
+
+// the key columns of a page and its precomputed raw hashes (null without a hash channel): what the group-by, join and set kernels take
+struct KeyInputs {
+    std::vector<const DeviceColumn *> keys;
+    const int64_t *hashes;
+};
+KeyInputs key_inputs(const DevicePage &in, const std::vector<int32_t> &channels, int32_t hash_channel)
+{
+    KeyInputs k{{}, hash_channel >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel].values : nullptr};
+    for (int32_t ch : channels) k.keys.push_back(&in.cols[(size_t)ch]);
+    return k;
+}
+}  // namespace
+
+template <class Config, class Op>
+SimpleOperatorFactory<Config, Op>::SimpleOperatorFactory(Context *ctx, int32_t operator_id, Config cfg) : ctx_(ctx), operator_id_(operator_id), cfg_(std::move(cfg))
+{
+    validate(ctx_, cfg_);
+}
+
+template <class Config, class Op> std::unique_ptr<Operator> SimpleOperatorFactory<Config, Op>::create_operator()
+{
+    check_open();
+    return std::make_unique<Op>(ctx_, operator_id_, cfg_);
+}
+
+template <class Config, class Op> std::unique_ptr<OperatorFactory> SimpleOperatorFactory<Config, Op>::duplicate()
+{
+    auto f = std::make_unique<SimpleOperatorFactory>(*this);   // (the config is not validated again)
+    f->closed_ = false;
+    return f;
+}
+
+// The protocol of an operator that turns one input page into at most one output page (WorkProcessorOperatorAdapter.java:138-216): input is
+// taken while no output is pending, finish() ends it once the pending page is gone.  A subclass says in emit() what a page becomes
+// (it sets pending_, or leaves it empty for a page without output rows) and, where its protocol differs, overrides ready() and the
+// state queries.
+class PageOperator : public Operator {
+public:
+    using Operator::Operator;
+    bool needs_input() override { return !finishing_ && !pending_; }
+    void add_input(const tgpu_page *page) override
+    {
+        ready();
+        emit(ingest_page(ctx_, page));
+    }
+    // a page of this library: channels that pass through share its (reference counted) buffers
+    void add_input_owned(const DevicePage &page) override
+    {
+        ready();
+        emit(DevicePage(page));
+    }
+    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    void finish() override { finishing_ = true; }
+    bool is_finished() override { return finishing_ && !pending_; }
+
+protected:
+    virtual void ready()
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        TG_CHECK_STATE(!pending_, "Operator still has pending output");
+    }
+    virtual void emit(DevicePage in) = 0;
+
+    std::unique_ptr<OutputPage> pending_;
+    bool finishing_ = false;
+};
+
 // =====================================================================================================================
 // FilterAndProjectOperator: WorkProcessorOperatorAdapter protocol (M/operator/WorkProcessorOperatorAdapter.java:138-216)
 // around PageProcessor (M/operator/FilterAndProjectOperator.java:56-64).  One output page per input page that selects
@@ -59,18 +141,15 @@ __global__ void __launch_bounds__(256) dict_compact_kernel(const int32_t *flags,
 }
 }  // namespace
 
-class FilterAndProjectOperator : public Operator {
+class FilterAndProjectOperator : public PageOperator {
 public:
-    FilterAndProjectOperator(Context *ctx, int32_t id, std::shared_ptr<PageProcessorGpu> p) : Operator(ctx, id), processor_(std::move(p)) {}
-
-    bool needs_input() override { return !finishing_ && !pending_; }
+    FilterAndProjectOperator(Context *ctx, int32_t id, const FilterAndProjectConfig &cfg) : PageOperator(ctx, id), processor_(cfg.processor) {}
 
     void add_input(const tgpu_page *page) override
     {
-        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
-        TG_CHECK_STATE(!pending_, "Operator still has pending output");
+        ready();
         if (try_dictionary(page)) return;
-        run(ingest_page(ctx_, page));
+        emit(ingest_page(ctx_, page));
     }
 
     // Dictionary-aware processing (M/operator/project/DictionaryAwarePageFilter.java:56-110, DictionaryAwarePageProjection.java:60-160,
@@ -108,7 +187,7 @@ public:
         if (has_filter) {
             const DeviceColumn &verdict = per_entry.cols[0];
             BufferPtr flags = ctx_->alloc((size_t)n * 4), rank = ctx_->alloc((size_t)n * 4), total = ctx_->alloc(8);
-            const int g = (int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx_->cu_count() * 8);
+            const int g = grid_for(ctx_, n);
             ProfileScope ps(ctx_, "dictionary_select");
             dict_select_kernel<<<g, 256, 0, ctx_->stream()>>>((const uint8_t *)verdict.values, verdict.nulls, ids->as<int32_t>(), n, flags->as<int32_t>());
             k::exclusive_scan_i32(ctx_, flags->as<int32_t>(), rank->as<int32_t>(), n, total->as<int64_t>());
@@ -144,21 +223,10 @@ public:
         return true;
     }
     int64_t dictionary_pages() const { return dictionary_pages_; }
-    // a page of this library: identity projections that pass a block through share its (reference counted) buffers
-    void add_input_owned(const DevicePage &page) override
-    {
-        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
-        TG_CHECK_STATE(!pending_, "Operator still has pending output");
-        run(DevicePage(page));
-    }
-
-    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
-    void finish() override { finishing_ = true; }
-    bool is_finished() override { return finishing_ && !pending_; }
     int64_t memory_bytes() override { return pending_ ? pending_->page.size_in_bytes() : 0; }
 
 private:
-    void run(DevicePage in)
+    void emit(DevicePage in) override
     {
         DevicePage out;
         if (!processor_->process(ctx_, in, out)) return;
@@ -170,10 +238,9 @@ private:
     }
 
     std::shared_ptr<PageProcessorGpu> processor_;
-    std::unique_ptr<OutputPage> pending_;
     int64_t dictionary_pages_ = 0;   // input pages that took the dictionary-aware path
-    bool finishing_ = false;
 };
+static void validate(Context *, const FilterAndProjectConfig &) {}   // (PageProcessorGpu::shared has checked the spec)
 
 // how many input pages of a FilterAndProjectOperator were processed once per dictionary entry (tests, stats)
 int64_t filter_project_dictionary_pages(Operator *op)
@@ -181,23 +248,6 @@ int64_t filter_project_dictionary_pages(Operator *op)
     auto *p = dynamic_cast<FilterAndProjectOperator *>(op);
     TG_CHECK_ARG(p != nullptr, "not a FilterAndProjectOperator");
     return p->dictionary_pages();
-}
-
-FilterAndProjectOperatorFactory::FilterAndProjectOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> input_types,
-                                                                 const tgpu_page_processor_spec *spec)
-    : ctx_(ctx), operator_id_(operator_id), processor_(PageProcessorGpu::shared(input_types, spec))
-{
-}
-
-std::unique_ptr<Operator> FilterAndProjectOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<FilterAndProjectOperator>(ctx_, operator_id_, processor_);
-}
-
-std::unique_ptr<OperatorFactory> FilterAndProjectOperatorFactory::duplicate()
-{
-    return std::unique_ptr<OperatorFactory>(new FilterAndProjectOperatorFactory(*this));   // shares the compiled page processor
 }
 
 // =====================================================================================================================
@@ -209,10 +259,7 @@ std::unique_ptr<OperatorFactory> FilterAndProjectOperatorFactory::duplicate()
 // =====================================================================================================================
 class ScanFilterAndProjectOperator : public Operator {
 public:
-    ScanFilterAndProjectOperator(Context *ctx, int32_t id, std::vector<int32_t> types, std::shared_ptr<PageProcessorGpu> p)
-        : Operator(ctx, id), types_(std::move(types)), processor_(std::move(p))
-    {
-    }
+    ScanFilterAndProjectOperator(Context *ctx, int32_t id, const ScanFilterAndProjectConfig &cfg) : Operator(ctx, id), types_(cfg.types), processor_(cfg.processor) {}
     ~ScanFilterAndProjectOperator() override { close(); }
 
     bool needs_input() override { return false; }                                                                    // :188-191
@@ -351,21 +398,7 @@ private:
     int64_t processed_positions_ = 0, lazy_loaded_ = 0, lazy_skipped_ = 0;
 };
 
-ScanFilterAndProjectOperatorFactory::ScanFilterAndProjectOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, const tgpu_page_processor_spec *spec)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), processor_(PageProcessorGpu::shared(types_, spec))
-{
-}
-
-std::unique_ptr<Operator> ScanFilterAndProjectOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<ScanFilterAndProjectOperator>(ctx_, operator_id_, types_, processor_);
-}
-
-std::unique_ptr<OperatorFactory> ScanFilterAndProjectOperatorFactory::duplicate()
-{
-    return std::unique_ptr<OperatorFactory>(new ScanFilterAndProjectOperatorFactory(*this));
-}
+static void validate(Context *, const ScanFilterAndProjectConfig &) {}
 
 static ScanFilterAndProjectOperator *as_scan(Operator *op)
 {
@@ -467,16 +500,10 @@ protected:
         const int32_t *gids = nullptr;
         BufferPtr gid_buf;
         if (gbh_) {
-            std::vector<const DeviceColumn *> keys;
-            for (int32_t ch : cfg_.group_by_channels) {
-                TG_CHECK_ARG(ch >= 0 && ch < (int)in.cols.size(), "group-by channel out of range");
-                keys.push_back(&in.cols[(size_t)ch]);
-            }
-            const int64_t *hashes = nullptr;
-            if (cfg_.hash_channel >= 0) {
+            for (int32_t ch : cfg_.group_by_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)in.cols.size(), "group-by channel out of range");
+            if (cfg_.hash_channel >= 0)
                 TG_CHECK_ARG(cfg_.hash_channel < (int)in.cols.size() && in.cols[(size_t)cfg_.hash_channel].type == TGPU_BIGINT, "bad hash channel");
-                hashes = (const int64_t *)in.cols[(size_t)cfg_.hash_channel].values;
-            }
+            const auto [keys, hashes] = key_inputs(in, cfg_.group_by_channels, cfg_.hash_channel);
             gid_buf = ctx_->alloc((size_t)in.n * 4);
             gbh_->get_group_ids(keys, hashes, in.n, gid_buf->as<int32_t>());
             gids = gid_buf->as<int32_t>();
@@ -725,23 +752,14 @@ protected:
     int64_t spill_count_ = 0, spilled_bytes_ = 0;
 };
 
-HashAggregationOperatorFactory::HashAggregationOperatorFactory(Context *ctx, int32_t operator_id, HashAggregationConfig cfg)
-    : ctx_(ctx), operator_id_(operator_id), cfg_(std::move(cfg))
+static void validate(Context *, const HashAggregationConfig &cfg)
 {
-    TG_CHECK_ARG(cfg_.group_by_types.size() == cfg_.group_by_channels.size(), "group-by types and channels differ in length");
-    TG_CHECK_ARG((int)cfg_.group_by_types.size() <= kMaxKeyChannels, "at most 8 group-by channels");
-    TG_CHECK_ARG((int)cfg_.aggs.size() <= kMaxAggs, "at most 16 aggregates");
-    TG_CHECK_ARG(cfg_.expected_groups > 0, "expectedGroups must be positive");
-    for (auto &a : cfg_.aggs) TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
+    TG_CHECK_ARG(cfg.group_by_types.size() == cfg.group_by_channels.size(), "group-by types and channels differ in length");
+    TG_CHECK_ARG((int)cfg.group_by_types.size() <= kMaxKeyChannels, "at most 8 group-by channels");
+    TG_CHECK_ARG((int)cfg.aggs.size() <= kMaxAggs, "at most 16 aggregates");
+    TG_CHECK_ARG(cfg.expected_groups > 0, "expectedGroups must be positive");
+    for (auto &a : cfg.aggs) TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
 }
-
-std::unique_ptr<Operator> HashAggregationOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<HashAggregationOperator>(ctx_, operator_id_, cfg_);
-}
-
-std::unique_ptr<OperatorFactory> HashAggregationOperatorFactory::duplicate() { return std::make_unique<HashAggregationOperatorFactory>(ctx_, operator_id_, cfg_); }
 
 // =====================================================================================================================
 // HashBuilderOperator (M/operator/HashBuilderOperator.java:155-191 state machine, spill states omitted: the GPU path reports
@@ -843,7 +861,7 @@ HashBuilderOperatorFactory::HashBuilderOperatorFactory(Context *ctx, int32_t ope
 
 std::unique_ptr<Operator> HashBuilderOperatorFactory::create_operator()
 {
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    check_open();
     TG_CHECK_STATE(created_ < cfg_.partition_count, "one build operator per lookup source partition");
     return std::make_unique<HashBuilderOperator>(ctx_, operator_id_, cfg_, bridge_, created_++);
 }
@@ -950,7 +968,7 @@ static void apply_join_filter(Context *ctx, LookupSourceGpu &source, const JoinF
     const int64_t n = in.n;
     ProfileScope ps(ctx, "join_filter_outer");
     BufferPtr cnt = ctx->alloc_zero((size_t)n * 4), emit = ctx->alloc((size_t)n * 4), start = ctx->alloc((size_t)n * 4), offset = ctx->alloc((size_t)n * 4), total = ctx->alloc(16);
-    const int g = (int)std::min<int64_t>(ceil_div(std::max<int64_t>(n, 1), 256), (int64_t)ctx->cu_count() * 8);
+    const int g = grid_for(ctx, n);
     if (survivors > 0) jf_count_kernel<<<g, 256, 0, ctx->stream()>>>(probe_idx->as<int32_t>(), survivors, cnt->as<int32_t>());
     jf_emit_count_kernel<<<g, 256, 0, ctx->stream()>>>(cnt->as<int32_t>(), n, emit->as<int32_t>());
     k::exclusive_scan_i32(ctx, cnt->as<int32_t>(), start->as<int32_t>(), n, total->as<int64_t>());
@@ -977,13 +995,8 @@ static bool probe_page(Context *ctx, LookupSourceGpu &source, const DevicePage &
 {
     TG_CHECK_ARG(in.cols.size() == cfg.probe_types.size(), "probe page channel count differs from the operator's types");
     if (in.n == 0) return false;
-    std::vector<const DeviceColumn *> keys;
-    for (int32_t ch : cfg.probe_join_channels) keys.push_back(&in.cols[(size_t)ch]);
-    const int64_t *hashes = nullptr;
-    if (cfg.probe_hash_channel >= 0) {
-        TG_CHECK_ARG(in.cols[(size_t)cfg.probe_hash_channel].type == TGPU_BIGINT, "probe hash channel must be BIGINT");
-        hashes = (const int64_t *)in.cols[(size_t)cfg.probe_hash_channel].values;
-    }
+    if (cfg.probe_hash_channel >= 0) TG_CHECK_ARG(in.cols[(size_t)cfg.probe_hash_channel].type == TGPU_BIGINT, "probe hash channel must be BIGINT");
+    const auto [keys, hashes] = key_inputs(in, cfg.probe_join_channels, cfg.probe_hash_channel);
     const bool outer = cfg.join_type == TGPU_JOIN_PROBE_OUTER || cfg.join_type == TGPU_JOIN_FULL_OUTER;
     BufferPtr probe_idx, build_idx;
     int64_t count = 0;
@@ -1069,7 +1082,7 @@ LookupJoinOperatorFactory::LookupJoinOperatorFactory(Context *ctx, int32_t opera
 
 std::unique_ptr<Operator> LookupJoinOperatorFactory::create_operator()
 {
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    check_open();
     return std::make_unique<LookupJoinOperator>(ctx_, operator_id_, cfg_, bridge_);
 }
 
@@ -1160,7 +1173,7 @@ LookupOuterOperatorFactory::LookupOuterOperatorFactory(Context *ctx, int32_t ope
 
 std::unique_ptr<Operator> LookupOuterOperatorFactory::create_operator()
 {
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    check_open();
     TG_CHECK_STATE(!created_, "Only one outer operator can be created");   // LookupOuterOperator.java:86-90 (one per lifespan)
     created_ = true;
     return std::make_unique<LookupOuterOperator>(ctx_, operator_id_, probe_output_types_, bridge_);
@@ -1418,7 +1431,7 @@ FusedFilterProjectJoinOperatorFactory::FusedFilterProjectJoinOperatorFactory(Con
 
 std::unique_ptr<Operator> FusedFilterProjectJoinOperatorFactory::create_operator()
 {
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    check_open();
     return std::make_unique<FusedFilterProjectJoinOperator>(ctx_, operator_id_, cfg_, bridge_, processor_, fused_);
 }
 
@@ -1717,7 +1730,7 @@ FusedFilterProjectAggregationOperatorFactory::FusedFilterProjectAggregationOpera
 
 std::unique_ptr<Operator> FusedFilterProjectAggregationOperatorFactory::create_operator()
 {
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    check_open();
     return std::make_unique<FusedFilterProjectAggregationOperator>(ctx_, operator_id_, cfg_, processor_, fused_);
 }
 
@@ -1732,11 +1745,7 @@ std::unique_ptr<OperatorFactory> FusedFilterProjectAggregationOperatorFactory::d
 // =====================================================================================================================
 class TopNOperator : public Operator {
 public:
-    TopNOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, int64_t n, const std::vector<int32_t> &sort_channels,
-                 const std::vector<int32_t> &sort_orders)
-        : Operator(ctx, id), n_(n), top_(ctx, types, n, sort_channels, sort_orders)
-    {
-    }
+    TopNOperator(Context *ctx, int32_t id, const TopNConfig &cfg) : Operator(ctx, id), n_(cfg.n), top_(ctx, cfg.types, cfg.n, cfg.sort_channels, cfg.sort_orders) {}
 
     // :195-199 (n == 0: the operator is finished from the start and never wants input, :154-156)
     bool needs_input() override { return n_ > 0 && !finishing_; }
@@ -1767,32 +1776,18 @@ private:
     bool finishing_ = false, finished_ = false;
 };
 
-TopNOperatorFactory::TopNOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t n, std::vector<int32_t> sort_channels,
-                                         std::vector<int32_t> sort_orders)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), sort_channels_(std::move(sort_channels)), sort_orders_(std::move(sort_orders)), n_(n)
+static void validate(Context *ctx, const TopNConfig &cfg)
 {
-    TopNGpu check(ctx_, types_, n_, sort_channels_, sort_orders_);   // argument validation up front
+    TopNGpu check(ctx, cfg.types, cfg.n, cfg.sort_channels, cfg.sort_orders);   // its constructor checks the arguments
     (void)check;
 }
-
-std::unique_ptr<Operator> TopNOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<TopNOperator>(ctx_, operator_id_, types_, n_, sort_channels_, sort_orders_);
-}
-
-std::unique_ptr<OperatorFactory> TopNOperatorFactory::duplicate() { return std::make_unique<TopNOperatorFactory>(ctx_, operator_id_, types_, n_, sort_channels_, sort_orders_); }
 
 // =====================================================================================================================
 // OrderByOperator (M/operator/OrderByOperator.java:160-300): PagesIndex.addPage per input page, one sort at finish()
 // =====================================================================================================================
 class OrderByOperator : public Operator {
 public:
-    OrderByOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &output_channels,
-                    const std::vector<int32_t> &sort_channels, const std::vector<int32_t> &sort_orders)
-        : Operator(ctx, id), types_(types), output_channels_(output_channels), sort_channels_(sort_channels), sort_orders_(sort_orders), index_(ctx, types)
-    {
-    }
+    OrderByOperator(Context *ctx, int32_t id, const OrderByConfig &cfg) : Operator(ctx, id), cfg_(cfg), index_(ctx, cfg.types) {}
 
     bool needs_input() override { return !finishing_; }
 
@@ -1800,8 +1795,7 @@ public:
     {
         TG_CHECK_STATE(!finishing_, "Operator is already finishing");
         DevicePage in = ingest_page(ctx_, page);
-        TG_CHECK_ARG(in.cols.size() == types_.size(), "page channel count does not match the operator's types");
-        for (size_t i = 0; i < types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == types_[i], "page channel type does not match the operator's types");
+        check_page_types(in, cfg_.types);
         index_.add_page(in);
     }
 
@@ -1812,12 +1806,12 @@ public:
         DevicePage all;
         all.n = index_.position_count();
         if (all.n == 0) return nullptr;
-        for (size_t i = 0; i < types_.size(); i++) all.cols.push_back(index_.column((int)i));
+        for (size_t i = 0; i < cfg_.types.size(); i++) all.cols.push_back(index_.column((int)i));
         int64_t count = 0;
-        BufferPtr pos = TopNGpu::sorted_positions(ctx_, all, sort_channels_, sort_orders_, all.n, count);
+        BufferPtr pos = TopNGpu::sorted_positions(ctx_, all, cfg_.sort_channels, cfg_.sort_orders, all.n, count);
         DevicePage out;
         out.n = count;
-        for (int32_t ch : output_channels_) out.cols.push_back(k::gather_column(ctx_, all.cols[(size_t)ch], pos->as<int32_t>(), count, false));
+        for (int32_t ch : cfg_.output_channels) out.cols.push_back(k::gather_column(ctx_, all.cols[(size_t)ch], pos->as<int32_t>(), count, false));
         return wrap(std::move(out));
     }
 
@@ -1826,32 +1820,17 @@ public:
     int64_t memory_bytes() override { return index_.estimated_size(); }
 
 private:
-    std::vector<int32_t> types_, output_channels_, sort_channels_, sort_orders_;
+    OrderByConfig cfg_;
     PagesIndexGpu index_;
     bool finishing_ = false, finished_ = false;
 };
 
-OrderByOperatorFactory::OrderByOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> output_channels,
-                                               std::vector<int32_t> sort_channels, std::vector<int32_t> sort_orders)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), output_channels_(std::move(output_channels)), sort_channels_(std::move(sort_channels)),
-      sort_orders_(std::move(sort_orders))
+static void validate(Context *ctx, const OrderByConfig &cfg)
 {
-    TopNGpu check(ctx_, types_, 1, sort_channels_, sort_orders_);   // validates types / sort channels / sort orders
+    TopNGpu check(ctx, cfg.types, 1, cfg.sort_channels, cfg.sort_orders);   // validates types / sort channels / sort orders
     (void)check;
-    for (int32_t ch : output_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)types_.size(), "output channel out of range");
+    for (int32_t ch : cfg.output_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)cfg.types.size(), "output channel out of range");
 }
-
-std::unique_ptr<Operator> OrderByOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<OrderByOperator>(ctx_, operator_id_, types_, output_channels_, sort_channels_, sort_orders_);
-}
-
-std::unique_ptr<OperatorFactory> OrderByOperatorFactory::duplicate()
-{
-    return std::make_unique<OrderByOperatorFactory>(ctx_, operator_id_, types_, output_channels_, sort_channels_, sort_orders_);
-}
-
 
 // =====================================================================================================================
 // DynamicFilterSourceOperator (M/operator/DynamicFilterSourceOperator.java:145-425).  Pages pass through unchanged (:375-381);
@@ -1901,18 +1880,13 @@ __global__ void __launch_bounds__(256) df_keep_kernel(ColView col, int64_t n, in
         keep[r] = ok ? 1 : 0;
     }
 }
-__global__ void __launch_bounds__(256) df_compact_kernel(const int32_t *keep, const int32_t *rank, int64_t n, int32_t *out)
-{
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256)
-        if (keep[r]) out[rank[r]] = (int32_t)r;
-}
 }  // namespace
 
 class DynamicFilterSourceOperator : public Operator {
 public:
-    DynamicFilterSourceOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &channels, int32_t max_distinct, int64_t max_size,
-                                int32_t min_max_limit)
-        : Operator(ctx, id), types_(types), channels_(channels), max_distinct_(max_distinct), max_size_(max_size), min_max_limit_(min_max_limit)
+    DynamicFilterSourceOperator(Context *ctx, int32_t id, const DynamicFilterSourceConfig &cfg)
+        : Operator(ctx, id), types_(cfg.types), channels_(cfg.channels), max_distinct_(cfg.max_distinct_values), max_size_(cfg.max_filter_size_in_bytes),
+          min_max_limit_(cfg.min_max_collection_limit)
     {
         for (int32_t ch : channels_) {
             const int32_t t = types_[(size_t)ch];
@@ -1962,7 +1936,7 @@ public:
                 BufferPtr keep = ctx_->alloc((size_t)n * 4), rank = ctx_->alloc((size_t)n * 4), pos = ctx_->alloc((size_t)n * 4), total = ctx_->alloc(8);
                 df_keep_kernel<<<(int)std::min<int64_t>(ceil_div(n, 256), 1024), 256, 0, ctx_->stream()>>>(view_of(keys.cols[0]), n, keep->as<int32_t>());
                 k::exclusive_scan_i32(ctx_, keep->as<int32_t>(), rank->as<int32_t>(), n, total->as<int64_t>());
-                df_compact_kernel<<<(int)std::min<int64_t>(ceil_div(n, 256), 1024), 256, 0, ctx_->stream()>>>(keep->as<int32_t>(), rank->as<int32_t>(), n, pos->as<int32_t>());
+                k::compact_positions(ctx_, keep->as<int32_t>(), rank->as<int32_t>(), n, pos->as<int32_t>());
                 check_launch("df_compact");
                 out.n = ctx_->read_scalar(total->as<int64_t>());
                 out.cols.push_back(k::gather_column(ctx_, keys.cols[0], pos->as<int32_t>(), out.n, false));
@@ -2010,8 +1984,7 @@ private:
     void collect(DevicePage in, bool borrowed)
     {
         TG_CHECK_STATE(needs_input(), "DynamicFilterSourceOperator: addInput() may not be called after finish() or with a pending page");
-        TG_CHECK_ARG(in.cols.size() == types_.size(), "page channel count does not match the operator's types");
-        for (size_t i = 0; i < types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == types_[i], "page channel type does not match the operator's types");
+        check_page_types(in, types_);
         const int64_t n = in.n;
         if (collecting_sets_) {   // :236-262
             min_max_limit_left_sub(n);
@@ -2117,24 +2090,15 @@ private:
     std::unique_ptr<OutputPage> current_;
 };
 
-DynamicFilterSourceOperatorFactory::DynamicFilterSourceOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> channels,
-                                                                       int32_t max_distinct_values, int64_t max_filter_size_in_bytes, int32_t min_max_collection_limit)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), channels_(std::move(channels)), max_distinct_(max_distinct_values),
-      min_max_limit_(min_max_collection_limit), max_size_(max_filter_size_in_bytes)
+static void validate(Context *, const DynamicFilterSourceConfig &cfg)
 {
-    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown type");
+    for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown type");
     std::set<int32_t> seen;
-    for (int32_t ch : channels_) {
-        TG_CHECK_ARG(ch >= 0 && ch < (int)types_.size(), "filter channel out of range");
+    for (int32_t ch : cfg.channels) {
+        TG_CHECK_ARG(ch >= 0 && ch < (int)cfg.types.size(), "filter channel out of range");
         TG_CHECK_ARG(seen.insert(ch).second, "duplicate channel indices are not allowed");   // :105-106
     }
-    TG_CHECK_ARG(max_distinct_ >= 0 && max_size_ >= 0, "limits must not be negative");
-}
-
-std::unique_ptr<Operator> DynamicFilterSourceOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<DynamicFilterSourceOperator>(ctx_, operator_id_, types_, channels_, max_distinct_, max_size_, min_max_limit_);
+    TG_CHECK_ARG(cfg.max_distinct_values >= 0 && cfg.max_filter_size_in_bytes >= 0, "limits must not be negative");
 }
 
 std::unique_ptr<OperatorFactory> DynamicFilterSourceOperatorFactory::duplicate()
@@ -2188,8 +2152,7 @@ private:
     void add(const DevicePage &in)   // :209-222
     {
         TG_CHECK_STATE(!finished_, "Operator is already finishing");
-        TG_CHECK_ARG(in.cols.size() == types_.size(), "page channel count does not match the operator's types");
-        for (size_t i = 0; i < types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == types_[i], "page channel type does not match the operator's types");
+        check_page_types(in, types_);
         set_->add_keys(in.cols[(size_t)set_channel_]);
     }
 
@@ -2213,7 +2176,7 @@ SetBuilderOperatorFactory::SetBuilderOperatorFactory(Context *ctx, int32_t opera
 
 std::unique_ptr<Operator> SetBuilderOperatorFactory::create_operator()
 {
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
+    check_open();
     return std::make_unique<SetBuilderOperator>(ctx_, operator_id_, types_, set_channel_, supplier_);
 }
 
@@ -2223,10 +2186,10 @@ std::unique_ptr<Operator> SetBuilderOperatorFactory::create_operator()
 // probe finished before that ends without output.  A DICTIONARY / RLE key block is probed once per dictionary entry and the results are
 // gathered through its ids.
 // =====================================================================================================================
-class HashSemiJoinOperator : public Operator {
+class HashSemiJoinOperator : public PageOperator {
 public:
-    HashSemiJoinOperator(Context *ctx, int32_t id, std::shared_ptr<SetSupplier> supplier, const std::vector<int32_t> &probe_types, int32_t probe_join_channel)
-        : Operator(ctx, id), supplier_(std::move(supplier)), probe_types_(probe_types), channel_(probe_join_channel)
+    HashSemiJoinOperator(Context *ctx, int32_t id, const HashSemiJoinConfig &cfg)
+        : PageOperator(ctx, id), supplier_(cfg.supplier), probe_types_(cfg.probe_types), channel_(cfg.probe_join_channel)
     {
     }
 
@@ -2235,7 +2198,7 @@ public:
 
     void add_input(const tgpu_page *page) override
     {
-        std::shared_ptr<const SemiSetGpu> set = ready();
+        ready();
         TG_CHECK_ARG(page != nullptr, "page is null");
         TG_CHECK_ARG(page->channel_count == (int32_t)probe_types_.size(), "page channel count does not match the operator's types");
         const tgpu_block &kb = page->blocks[channel_];
@@ -2247,34 +2210,25 @@ public:
             DeviceColumn dict;
             BufferPtr ids;
             ingest_dictionary(ctx_, &kb, dict, ids);
-            verdict = k::gather_column(ctx_, set->probe(dict), ids->as<int32_t>(), page->position_count, false);
+            verdict = k::gather_column(ctx_, supplier_->set()->probe(dict), ids->as<int32_t>(), page->position_count, false);
             have_verdict = true;
         }
-        DevicePage in = ingest_page(ctx_, page);
-        emit(*set, std::move(in), have_verdict ? &verdict : nullptr);
+        probe(ingest_page(ctx_, page), have_verdict ? &verdict : nullptr);
     }
-    void add_input_owned(const DevicePage &page) override { emit(*ready(), DevicePage(page), nullptr); }
-
-    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
-    void finish() override { finishing_ = true; }
-    bool is_finished() override { return finishing_ && !pending_; }
     int64_t memory_bytes() override { return pending_ ? pending_->page.size_in_bytes() : 0; }
 
 private:
-    std::shared_ptr<const SemiSetGpu> ready()
+    void ready() override
     {
-        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
-        TG_CHECK_STATE(!pending_, "Operator still has pending output");
-        std::shared_ptr<const SemiSetGpu> set = supplier_->set();
-        TG_CHECK_STATE(set != nullptr, "ChannelSet has not been built yet");
-        return set;
+        PageOperator::ready();
+        TG_CHECK_STATE(supplier_->set() != nullptr, "ChannelSet has not been built yet");
     }
+    void emit(DevicePage in) override { probe(std::move(in), nullptr); }
 
-    void emit(const SemiSetGpu &set, DevicePage in, const DeviceColumn *verdict)
+    void probe(DevicePage in, const DeviceColumn *verdict)
     {
-        TG_CHECK_ARG(in.cols.size() == probe_types_.size(), "page channel count does not match the operator's types");
-        for (size_t i = 0; i < probe_types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == probe_types_[i], "page channel type does not match the operator's types");
-        DeviceColumn out = verdict ? *verdict : set.probe(in.cols[(size_t)channel_]);
+        check_page_types(in, probe_types_);
+        DeviceColumn out = verdict ? *verdict : supplier_->set()->probe(in.cols[(size_t)channel_]);
         // the page passes through: channels that borrow the caller's device memory get buffers of their own (the output outlives the call)
         own_borrowed_columns(ctx_, in);
         in.cols.push_back(std::move(out));
@@ -2284,31 +2238,15 @@ private:
     std::shared_ptr<SetSupplier> supplier_;
     std::vector<int32_t> probe_types_;
     int32_t channel_;
-    std::unique_ptr<OutputPage> pending_;
-    bool finishing_ = false;
 };
 
-HashSemiJoinOperatorFactory::HashSemiJoinOperatorFactory(Context *ctx, int32_t operator_id, std::shared_ptr<SetSupplier> supplier, std::vector<int32_t> probe_types,
-                                                         int32_t probe_join_channel, int32_t probe_hash_channel)
-    : ctx_(ctx), operator_id_(operator_id), supplier_(std::move(supplier)), probe_types_(std::move(probe_types)), probe_join_channel_(probe_join_channel)
+static void validate(Context *, const HashSemiJoinConfig &cfg)
 {
-    TG_CHECK_ARG(!probe_types_.empty(), "the semi join probe needs at least one channel");
-    for (int32_t t : probe_types_) TG_CHECK_ARG(valid_type(t), "unknown type");
-    TG_CHECK_ARG(probe_join_channel_ >= 0 && probe_join_channel_ < (int)probe_types_.size(), "probe join channel out of range");
-    TG_CHECK_ARG(probe_hash_channel >= -1 && probe_hash_channel < (int)probe_types_.size(), "probe hash channel out of range");
-    TG_CHECK_ARG(probe_types_[(size_t)probe_join_channel_] == supplier_->type(), "the probe key type is not the set's type");
-}
-
-std::unique_ptr<Operator> HashSemiJoinOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<HashSemiJoinOperator>(ctx_, operator_id_, supplier_, probe_types_, probe_join_channel_);
-}
-
-std::unique_ptr<OperatorFactory> HashSemiJoinOperatorFactory::duplicate()
-{
-    // shares the supplier (HashSemiJoinOperator.java:115-118)
-    return std::make_unique<HashSemiJoinOperatorFactory>(ctx_, operator_id_, supplier_, probe_types_, probe_join_channel_, -1);
+    TG_CHECK_ARG(!cfg.probe_types.empty(), "the semi join probe needs at least one channel");
+    for (int32_t t : cfg.probe_types) TG_CHECK_ARG(valid_type(t), "unknown type");
+    TG_CHECK_ARG(cfg.probe_join_channel >= 0 && cfg.probe_join_channel < (int)cfg.probe_types.size(), "probe join channel out of range");
+    TG_CHECK_ARG(cfg.probe_hash_channel >= -1 && cfg.probe_hash_channel < (int)cfg.probe_types.size(), "probe hash channel out of range");
+    TG_CHECK_ARG(cfg.probe_types[(size_t)cfg.probe_join_channel] == cfg.supplier->type(), "the probe key type is not the set's type");
 }
 
 // =====================================================================================================================
@@ -2329,58 +2267,21 @@ void check_distinct_config(const std::vector<int32_t> &types, const std::vector<
     TG_CHECK_ARG(hash_channel >= -1 && hash_channel < (int)types.size(), "hash channel out of range");
     TG_CHECK_ARG(hash_channel < 0 || types[(size_t)hash_channel] == TGPU_BIGINT, "hash channel must be BIGINT");
 }
-
-std::vector<int32_t> types_of_channels(const std::vector<int32_t> &types, const std::vector<int32_t> &channels)
-{
-    std::vector<int32_t> out;
-    for (int32_t ch : channels) out.push_back(types[(size_t)ch]);
-    return out;
-}
-
-void check_page_types(const DevicePage &in, const std::vector<int32_t> &types)
-{
-    TG_CHECK_ARG(in.cols.size() == types.size(), "page channel count does not match the operator's types");
-    for (size_t i = 0; i < types.size(); i++) TG_CHECK_ARG(in.cols[i].type == types[i], "page channel type does not match the operator's types");
-}
 }  // namespace
 
-class MarkDistinctOperator : public Operator {
+class MarkDistinctOperator : public PageOperator {   // needsInput :137-141, isFinished :131-135
 public:
-    MarkDistinctOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &mark_channels, int32_t hash_channel)
-        : Operator(ctx, id), types_(types), channels_(mark_channels), hash_channel_(hash_channel),
-          marker_(ctx, types_of_channels(types, mark_channels), hash_channel >= 0, 10000)   // MarkDistinctHash.java:39
+    MarkDistinctOperator(Context *ctx, int32_t id, const MarkDistinctConfig &cfg)
+        : PageOperator(ctx, id), cfg_(cfg), marker_(ctx, types_of_channels(cfg.types, cfg.mark_channels), cfg.hash_channel >= 0, 10000)   // MarkDistinctHash.java:39
     {
     }
-
-    bool needs_input() override { return !finishing_ && !pending_; }   // :137-141
-    void add_input(const tgpu_page *page) override
-    {
-        ready();
-        emit(ingest_page(ctx_, page));
-    }
-    void add_input_owned(const DevicePage &page) override
-    {
-        ready();
-        emit(DevicePage(page));
-    }
-    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
-    void finish() override { finishing_ = true; }
-    bool is_finished() override { return finishing_ && !pending_; }   // :131-135
     int64_t memory_bytes() override { return marker_.estimated_size(); }
 
 private:
-    void ready()
+    void emit(DevicePage in) override   // :143-174
     {
-        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
-        TG_CHECK_STATE(!pending_, "Operator still has pending output");
-    }
-
-    void emit(DevicePage in)   // :143-174
-    {
-        check_page_types(in, types_);
-        std::vector<const DeviceColumn *> keys;
-        for (int32_t ch : channels_) keys.push_back(&in.cols[(size_t)ch]);
-        const int64_t *hashes = hash_channel_ >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel_].values : nullptr;
+        check_page_types(in, cfg_.types);
+        const auto [keys, hashes] = key_inputs(in, cfg_.mark_channels, cfg_.hash_channel);
         DeviceColumn mark = marker_.mark(keys, hashes, in.n);
         // the page passes through: channels that borrow the caller's device memory get buffers of their own (the output outlives the call)
         own_borrowed_columns(ctx_, in);
@@ -2388,104 +2289,52 @@ private:
         pending_ = wrap(std::move(in));
     }
 
-    std::vector<int32_t> types_, channels_;
-    int32_t hash_channel_;
+    MarkDistinctConfig cfg_;
     DistinctMarkerGpu marker_;
-    std::unique_ptr<OutputPage> pending_;
-    bool finishing_ = false;
 };
 
-MarkDistinctOperatorFactory::MarkDistinctOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> mark_channels,
-                                                         int32_t hash_channel)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), mark_channels_(std::move(mark_channels)), hash_channel_(hash_channel)
-{
-    check_distinct_config(types_, mark_channels_, hash_channel_, "mark distinct");
-}
+static void validate(Context *, const MarkDistinctConfig &cfg) { check_distinct_config(cfg.types, cfg.mark_channels, cfg.hash_channel, "mark distinct"); }
 
-std::unique_ptr<Operator> MarkDistinctOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<MarkDistinctOperator>(ctx_, operator_id_, types_, mark_channels_, hash_channel_);
-}
-
-std::unique_ptr<OperatorFactory> MarkDistinctOperatorFactory::duplicate()   // MarkDistinctOperator.java:87-91
-{
-    return std::make_unique<MarkDistinctOperatorFactory>(ctx_, operator_id_, types_, mark_channels_, hash_channel_);
-}
-
-class DistinctLimitOperator : public Operator {
+class DistinctLimitOperator : public PageOperator {
 public:
-    DistinctLimitOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &distinct_channels, int64_t limit,
-                          int32_t hash_channel)
-        : Operator(ctx, id), types_(types), channels_(distinct_channels), hash_channel_(hash_channel), remaining_(limit),
-          marker_(ctx, types_of_channels(types, distinct_channels), hash_channel >= 0, (int32_t)std::max<int64_t>(1, std::min<int64_t>(limit, 10000)))   // :130-138 (a limit of 0 never sees a page)
+    DistinctLimitOperator(Context *ctx, int32_t id, const DistinctLimitConfig &cfg)
+        : PageOperator(ctx, id), cfg_(cfg), remaining_(cfg.limit),
+          marker_(ctx, types_of_channels(cfg.types, cfg.distinct_channels), cfg.hash_channel >= 0,
+                  (int32_t)std::max<int64_t>(1, std::min<int64_t>(cfg.limit, 10000)))   // :130-138 (a limit of 0 never sees a page)
     {
     }
 
-    bool needs_input() override { return !finishing_ && remaining_ > 0 && !pending_; }   // :160-164
-    void add_input(const tgpu_page *page) override
-    {
-        ready();
-        emit(ingest_page(ctx_, page));
-    }
-    void add_input_owned(const DevicePage &page) override
-    {
-        ready();
-        emit(page);
-    }
-    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
-    void finish() override { finishing_ = true; }
-    bool is_finished() override { return !pending_ && (finishing_ || remaining_ == 0); }   // :154-158
+    bool needs_input() override { return !finishing_ && remaining_ > 0 && !pending_; }       // :160-164
+    bool is_finished() override { return !pending_ && (finishing_ || remaining_ == 0); }     // :154-158
     int64_t memory_bytes() override { return marker_.estimated_size(); }
 
 private:
-    void ready()
-    {
-        TG_CHECK_STATE(needs_input(), "Operator does not need input");
-    }
+    void ready() override { TG_CHECK_STATE(needs_input(), "Operator does not need input"); }
 
-    void emit(const DevicePage &in)   // :166-223
+    void emit(DevicePage in) override   // :166-223
     {
-        check_page_types(in, types_);
-        std::vector<const DeviceColumn *> keys;
-        for (int32_t ch : channels_) keys.push_back(&in.cols[(size_t)ch]);
-        const int64_t *hashes = hash_channel_ >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel_].values : nullptr;
+        check_page_types(in, cfg_.types);
+        const auto [keys, hashes] = key_inputs(in, cfg_.distinct_channels, cfg_.hash_channel);
         const int32_t *positions = nullptr;
         const int64_t kept = marker_.first_rows(keys, hashes, in.n, remaining_, &positions);
         if (kept == 0) return;   // no output page for a page without a new key (:212-223)
         DevicePage out;
         out.n = kept;
-        for (int32_t ch : channels_) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)ch], positions, kept, false));
-        if (hash_channel_ >= 0) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)hash_channel_], positions, kept, false));   // :125-128
+        for (int32_t ch : cfg_.distinct_channels) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)ch], positions, kept, false));
+        if (cfg_.hash_channel >= 0) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)cfg_.hash_channel], positions, kept, false));   // :125-128
         remaining_ -= kept;
         pending_ = wrap(std::move(out));
     }
 
-    std::vector<int32_t> types_, channels_;
-    int32_t hash_channel_;
+    DistinctLimitConfig cfg_;
     int64_t remaining_;
     DistinctMarkerGpu marker_;
-    std::unique_ptr<OutputPage> pending_;
-    bool finishing_ = false;
 };
 
-DistinctLimitOperatorFactory::DistinctLimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> distinct_channels,
-                                                           int64_t limit, int32_t hash_channel)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), distinct_channels_(std::move(distinct_channels)), limit_(limit), hash_channel_(hash_channel)
+static void validate(Context *, const DistinctLimitConfig &cfg)
 {
-    check_distinct_config(types_, distinct_channels_, hash_channel_, "distinct limit");
-    TG_CHECK_ARG(limit_ >= 0, "limit must be at least zero");   // :70
-}
-
-std::unique_ptr<Operator> DistinctLimitOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<DistinctLimitOperator>(ctx_, operator_id_, types_, distinct_channels_, limit_, hash_channel_);
-}
-
-std::unique_ptr<OperatorFactory> DistinctLimitOperatorFactory::duplicate()   // DistinctLimitOperator.java:94-98
-{
-    return std::make_unique<DistinctLimitOperatorFactory>(ctx_, operator_id_, types_, distinct_channels_, limit_, hash_channel_);
+    check_distinct_config(cfg.types, cfg.distinct_channels, cfg.hash_channel, "distinct limit");
+    TG_CHECK_ARG(cfg.limit >= 0, "limit must be at least zero");   // :70
 }
 
 // =====================================================================================================================
@@ -2495,12 +2344,11 @@ std::unique_ptr<OperatorFactory> DistinctLimitOperatorFactory::duplicate()   // 
 // reproduced).  One page at a time: needs_input is false while a page's result is pending.  Partitioned: one GroupByHashGpu, then the
 // ranking kernels of rownumber.hip.  Not partitioned: the count is a host int64 and the only kernel is the iota of the new column.
 // =====================================================================================================================
-class RowNumberOperator : public Operator {
+class RowNumberOperator : public PageOperator {
 public:
-    RowNumberOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &output_channels,
-                      const std::vector<int32_t> &partition_channels, int64_t max_rows, int32_t hash_channel, int32_t expected_positions)
-        : Operator(ctx, id), types_(types), output_channels_(output_channels), partition_channels_(partition_channels), max_rows_(max_rows), hash_channel_(hash_channel),
-          numberer_(ctx, types_of_channels(types, partition_channels), hash_channel >= 0, expected_positions, max_rows)
+    RowNumberOperator(Context *ctx, int32_t id, const RowNumberConfig &cfg)
+        : PageOperator(ctx, id), cfg_(cfg), max_rows_(cfg.max_rows_per_partition),
+          numberer_(ctx, types_of_channels(cfg.types, cfg.partition_channels), cfg.hash_channel >= 0, cfg.expected_positions, cfg.max_rows_per_partition)
     {
         // TGPU_ROW_NUMBER_PATH=sort, read here: every page down the sort path instead of the choice by group count (the baseline of
         // tools/exp_row_number.py; the tests reach the sort path with few groups through it)
@@ -2508,47 +2356,27 @@ public:
         numberer_.force_sort(e != nullptr && !strcmp(e, "sort"));
     }
 
-    bool needs_input() override   // :201-209
-    {
-        if (single_partition_done()) return false;
-        return !finishing_ && !pending_;
-    }
-    void add_input(const tgpu_page *page) override
-    {
-        ready();
-        emit(ingest_page(ctx_, page));
-    }
-    void add_input_owned(const DevicePage &page) override
-    {
-        ready();
-        emit(DevicePage(page));
-    }
-    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
-    void finish() override { finishing_ = true; }
-    bool is_finished() override   // :188-199; a partitioned operator never finishes early
-    {
-        if (pending_) return false;
-        return finishing_ || single_partition_done();
-    }
+    bool needs_input() override { return !single_partition_done() && PageOperator::needs_input(); }   // :201-209
+    // :188-199; a partitioned operator never finishes early
+    bool is_finished() override { return !pending_ && (finishing_ || single_partition_done()); }
     int64_t memory_bytes() override { return numberer_.estimated_size(); }   // :266
 
 private:
     bool single_partition_done() const { return !numberer_.partitioned() && max_rows_ >= 0 && count_ == max_rows_; }
-    void ready()
+    void ready() override
     {
-        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
-        TG_CHECK_STATE(!pending_, "Operator still has pending output");
+        PageOperator::ready();
         TG_CHECK_STATE(!single_partition_done(), "Operator does not need input");
     }
 
-    void emit(DevicePage in)   // :225-247
+    void emit(DevicePage in) override   // :225-247
     {
-        check_page_types(in, types_);
+        check_page_types(in, cfg_.types);
         DevicePage out;
         if (!numberer_.partitioned()) {
             const int64_t take = max_rows_ >= 0 ? std::min(in.n, max_rows_ - count_) : in.n;
             if (max_rows_ >= 0 && take == 0) return;   // an empty PageBuilder is no page (:335-337)
-            for (int32_t ch : output_channels_) out.cols.push_back(in.cols[(size_t)ch]);
+            for (int32_t ch : cfg_.output_channels) out.cols.push_back(in.cols[(size_t)ch]);
             own_borrowed_columns(ctx_, out);   // the channels pass through: the output outlives the call
             if (take < in.n)
                 for (DeviceColumn &c : out.cols) c = k::region_of(ctx_, c, 0, take);
@@ -2558,12 +2386,10 @@ private:
             pending_ = wrap(std::move(out));
             return;
         }
-        std::vector<const DeviceColumn *> keys;
-        for (int32_t ch : partition_channels_) keys.push_back(&in.cols[(size_t)ch]);
-        const int64_t *hashes = hash_channel_ >= 0 ? (const int64_t *)in.cols[(size_t)hash_channel_].values : nullptr;
+        const auto [keys, hashes] = key_inputs(in, cfg_.partition_channels, cfg_.hash_channel);
         if (max_rows_ < 0) {   // getRowsWithRowNumber (:289-299)
             DeviceColumn rn = numberer_.number(keys, hashes, in.n);
-            for (int32_t ch : output_channels_) out.cols.push_back(in.cols[(size_t)ch]);
+            for (int32_t ch : cfg_.output_channels) out.cols.push_back(in.cols[(size_t)ch]);
             own_borrowed_columns(ctx_, out);
             out.n = in.n;
             out.cols.push_back(std::move(rn));
@@ -2575,74 +2401,48 @@ private:
         const int64_t kept = numberer_.select(keys, hashes, in.n, &positions, &rn);
         if (kept == 0) return;
         out.n = kept;
-        for (int32_t ch : output_channels_) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)ch], positions, kept, false));
+        for (int32_t ch : cfg_.output_channels) out.cols.push_back(k::gather_column(ctx_, in.cols[(size_t)ch], positions, kept, false));
         out.cols.push_back(std::move(rn));
         pending_ = wrap(std::move(out));
     }
 
-    std::vector<int32_t> types_, output_channels_, partition_channels_;
+    RowNumberConfig cfg_;
     int64_t max_rows_;
-    int32_t hash_channel_;
     RowNumbererGpu numberer_;
     int64_t count_ = 0;   // partitionRowCount.get(0) of the single partition
-    std::unique_ptr<OutputPage> pending_;
-    bool finishing_ = false;
 };
 
-RowNumberOperatorFactory::RowNumberOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> output_channels,
-                                                   std::vector<int32_t> partition_channels, int64_t max_rows_per_partition, int32_t hash_channel,
-                                                   int32_t expected_positions)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), output_channels_(std::move(output_channels)), partition_channels_(std::move(partition_channels)),
-      max_rows_(max_rows_per_partition), hash_channel_(hash_channel), expected_positions_(expected_positions)
+static void validate(Context *, const RowNumberConfig &cfg)
 {
-    TG_CHECK_ARG(!types_.empty(), "row number needs at least one source channel");
-    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown type");
-    for (int32_t ch : output_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)types_.size(), "output channel out of range");
-    TG_CHECK_ARG((int)partition_channels_.size() <= kMaxKeyChannels, "at most 8 key channels are supported");
-    for (int32_t ch : partition_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)types_.size(), "partition channel out of range");
-    TG_CHECK_ARG(hash_channel_ >= -1 && hash_channel_ < (int)types_.size(), "hash channel out of range");
-    TG_CHECK_ARG(hash_channel_ < 0 || !partition_channels_.empty(), "a hash channel needs partition channels");
-    TG_CHECK_ARG(hash_channel_ < 0 || types_[(size_t)hash_channel_] == TGPU_BIGINT, "hash channel must be BIGINT");
-    TG_CHECK_ARG(max_rows_ >= -1 && max_rows_ <= 0x7fffffffLL, "max rows per partition must be -1 (none) or a non-negative int");
-    TG_CHECK_ARG(expected_positions_ > 0, "expected positions must be positive");
-}
-
-std::unique_ptr<Operator> RowNumberOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<RowNumberOperator>(ctx_, operator_id_, types_, output_channels_, partition_channels_, max_rows_, hash_channel_, expected_positions_);
-}
-
-std::unique_ptr<OperatorFactory> RowNumberOperatorFactory::duplicate()   // RowNumberOperator.java:114-118
-{
-    return std::make_unique<RowNumberOperatorFactory>(ctx_, operator_id_, types_, output_channels_, partition_channels_, max_rows_, hash_channel_, expected_positions_);
+    const int nt = (int)cfg.types.size();
+    TG_CHECK_ARG(!cfg.types.empty(), "row number needs at least one source channel");
+    for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown type");
+    for (int32_t ch : cfg.output_channels) TG_CHECK_ARG(ch >= 0 && ch < nt, "output channel out of range");
+    TG_CHECK_ARG((int)cfg.partition_channels.size() <= kMaxKeyChannels, "at most 8 key channels are supported");
+    for (int32_t ch : cfg.partition_channels) TG_CHECK_ARG(ch >= 0 && ch < nt, "partition channel out of range");
+    TG_CHECK_ARG(cfg.hash_channel >= -1 && cfg.hash_channel < nt, "hash channel out of range");
+    TG_CHECK_ARG(cfg.hash_channel < 0 || !cfg.partition_channels.empty(), "a hash channel needs partition channels");
+    TG_CHECK_ARG(cfg.hash_channel < 0 || cfg.types[(size_t)cfg.hash_channel] == TGPU_BIGINT, "hash channel must be BIGINT");
+    TG_CHECK_ARG(cfg.max_rows_per_partition >= -1 && cfg.max_rows_per_partition <= 0x7fffffffLL, "max rows per partition must be -1 (none) or a non-negative int");
+    TG_CHECK_ARG(cfg.expected_positions > 0, "expected positions must be positive");
 }
 
 // =====================================================================================================================
 // LimitOperator (M/operator/LimitOperator.java:62-119): whole pages pass through while they fit, the crossing page is a region of its
 // first `remaining` rows, finish() zeroes the remainder.  No kernel.
 // =====================================================================================================================
-class LimitOperator : public Operator {
+class LimitOperator : public PageOperator {
 public:
-    LimitOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, int64_t limit) : Operator(ctx, id), types_(types), remaining_(limit) {}
+    LimitOperator(Context *ctx, int32_t id, const LimitConfig &cfg) : PageOperator(ctx, id), types_(cfg.types), remaining_(cfg.limit) {}
 
-    bool needs_input() override { return remaining_ > 0 && !pending_; }   // :92-96
-    void add_input(const tgpu_page *page) override
-    {
-        TG_CHECK_STATE(needs_input(), "Operator does not need input");   // :101
-        emit(ingest_page(ctx_, page));
-    }
-    void add_input_owned(const DevicePage &page) override
-    {
-        TG_CHECK_STATE(needs_input(), "Operator does not need input");
-        emit(DevicePage(page));
-    }
-    std::unique_ptr<OutputPage> get_output() override { return std::move(pending_); }
+    bool needs_input() override { return remaining_ > 0 && !pending_; }           // :92-96
     void finish() override { remaining_ = 0; }                                    // :80-84
     bool is_finished() override { return remaining_ == 0 && !pending_; }          // :86-90
 
 private:
-    void emit(DevicePage in)   // :98-111
+    void ready() override { TG_CHECK_STATE(needs_input(), "Operator does not need input"); }   // :101
+
+    void emit(DevicePage in) override   // :98-111
     {
         check_page_types(in, types_);
         own_borrowed_columns(ctx_, in);
@@ -2659,26 +2459,13 @@ private:
 
     std::vector<int32_t> types_;
     int64_t remaining_;
-    std::unique_ptr<OutputPage> pending_;
 };
 
-LimitOperatorFactory::LimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t limit)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), limit_(limit)
+static void validate(Context *, const LimitConfig &cfg)
 {
-    TG_CHECK_ARG(!types_.empty(), "limit needs at least one source channel");
-    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown type");
-    TG_CHECK_ARG(limit_ >= 0, "limit must be at least zero");   // :70
-}
-
-std::unique_ptr<Operator> LimitOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<LimitOperator>(ctx_, operator_id_, types_, limit_);
-}
-
-std::unique_ptr<OperatorFactory> LimitOperatorFactory::duplicate()   // LimitOperator.java:55-59
-{
-    return std::make_unique<LimitOperatorFactory>(ctx_, operator_id_, types_, limit_);
+    TG_CHECK_ARG(!cfg.types.empty(), "limit needs at least one source channel");
+    for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown type");
+    TG_CHECK_ARG(cfg.limit >= 0, "limit must be at least zero");   // :70
 }
 
 void Operator::add_input_owned(const DevicePage &page)
@@ -2704,8 +2491,8 @@ void Operator::add_input_owned(const DevicePage &page)
 // =====================================================================================================================
 class MergePagesOperator : public Operator {
 public:
-    MergePagesOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, int64_t min_page_size, int32_t min_row_count, int64_t max_page_size)
-        : Operator(ctx, id), types_(types), min_page_size_(min_page_size), max_page_size_(max_page_size), min_row_count_(min_row_count)
+    MergePagesOperator(Context *ctx, int32_t id, const MergePagesConfig &cfg)
+        : Operator(ctx, id), types_(cfg.types), min_page_size_(cfg.min_page_size_in_bytes), max_page_size_(cfg.max_page_size_in_bytes), min_row_count_(cfg.min_row_count)
     {
     }
 
@@ -2717,8 +2504,7 @@ public:
     void merge(DevicePage in)
     {
         TG_CHECK_STATE(needs_input(), "Operator does not need input");
-        TG_CHECK_ARG(in.cols.size() == types_.size(), "page channel count does not match the operator's types");
-        for (size_t i = 0; i < types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == types_[i], "page channel type does not match the operator's types");
+        check_page_types(in, types_);
         std::vector<std::array<int32_t, 2>> ends;
         const int64_t size = in.n >= min_row_count_ ? 0 : java_size_in_bytes(in, ends);   // (only needed to classify a page with few rows)
         if (in.n >= min_row_count_ || size >= min_page_size_) {   // :145-157
@@ -2810,28 +2596,13 @@ private:
     std::deque<DevicePage> output_;
 };
 
-MergePagesOperatorFactory::MergePagesOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t min_page_size_in_bytes, int32_t min_row_count,
-                                                     int64_t max_page_size_in_bytes)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), min_page_size_(min_page_size_in_bytes), max_page_size_(max_page_size_in_bytes),
-      min_row_count_(min_row_count)
+static void validate(Context *, const MergePagesConfig &cfg)   // MergePages.java:102-106
 {
-    // MergePages.java:102-106
-    TG_CHECK_ARG(min_page_size_ >= 0, "minPageSizeInBytes must be greater or equal than zero");
-    TG_CHECK_ARG(min_row_count_ >= 0, "minRowCount must be greater or equal than zero");
-    TG_CHECK_ARG(max_page_size_ > 0, "maxPageSizeInBytes must be greater than zero");
-    TG_CHECK_ARG(max_page_size_ >= min_page_size_, "maxPageSizeInBytes must be greater or equal than minPageSizeInBytes");
-    for (int32_t t : types_) TG_CHECK_ARG(valid_type(t), "unknown channel type");
-}
-
-std::unique_ptr<Operator> MergePagesOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<MergePagesOperator>(ctx_, operator_id_, types_, min_page_size_, min_row_count_, max_page_size_);
-}
-
-std::unique_ptr<OperatorFactory> MergePagesOperatorFactory::duplicate()
-{
-    return std::make_unique<MergePagesOperatorFactory>(ctx_, operator_id_, types_, min_page_size_, min_row_count_, max_page_size_);
+    TG_CHECK_ARG(cfg.min_page_size_in_bytes >= 0, "minPageSizeInBytes must be greater or equal than zero");
+    TG_CHECK_ARG(cfg.min_row_count >= 0, "minRowCount must be greater or equal than zero");
+    TG_CHECK_ARG(cfg.max_page_size_in_bytes > 0, "maxPageSizeInBytes must be greater than zero");
+    TG_CHECK_ARG(cfg.max_page_size_in_bytes >= cfg.min_page_size_in_bytes, "maxPageSizeInBytes must be greater or equal than minPageSizeInBytes");
+    for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown channel type");
 }
 
 // =====================================================================================================================
@@ -2852,10 +2623,9 @@ __global__ void __launch_bounds__(256) replicate_flags_kernel(const uint8_t *nul
 
 class PartitionedOutputOperator : public Operator {
 public:
-    PartitionedOutputOperator(Context *ctx, int32_t id, const std::vector<int32_t> &types, const std::vector<int32_t> &partition_channels, int32_t hash_channel,
-                              int32_t partition_count, bool replicates_any_row, int32_t null_channel, bool local_function)
-        : Operator(ctx, id), types_(types), partition_channels_(partition_channels), hash_channel_(hash_channel), partition_count_(partition_count),
-          null_channel_(null_channel), replicates_any_row_(replicates_any_row), local_function_(local_function)
+    PartitionedOutputOperator(Context *ctx, int32_t id, const PartitionedOutputConfig &cfg)
+        : Operator(ctx, id), types_(cfg.types), partition_channels_(cfg.partition_channels), hash_channel_(cfg.hash_channel), partition_count_(cfg.partition_count),
+          null_channel_(cfg.null_channel), replicates_any_row_(cfg.replicates_any_row), local_function_(cfg.partition_function == TGPU_PARTITION_LOCAL)
     {
     }
 
@@ -2865,16 +2635,12 @@ public:
     {
         TG_CHECK_STATE(!finishing_, "Operator is already finishing");
         DevicePage in = ingest_page(ctx_, page);
-        TG_CHECK_ARG(in.cols.size() == types_.size(), "page channel count does not match the operator's types");
-        for (size_t i = 0; i < types_.size(); i++) TG_CHECK_ARG(in.cols[i].type == types_[i], "page channel type does not match the operator's types");
+        check_page_types(in, types_);
         const int64_t n = in.n;
         if (n == 0) return;   // :274-277
         BufferPtr own_hashes;
-        const int64_t *hashes = nullptr;
-        if (hash_channel_ >= 0) hashes = (const int64_t *)in.cols[(size_t)hash_channel_].values;
-        else {
-            std::vector<const DeviceColumn *> keys;
-            for (int32_t ch : partition_channels_) keys.push_back(&in.cols[(size_t)ch]);
+        auto [keys, hashes] = key_inputs(in, partition_channels_, hash_channel_);
+        if (hash_channel_ < 0) {
             own_hashes = ctx_->alloc((size_t)n * 8);
             k::hash_rows(ctx_, key_cols_of(keys), n, own_hashes->as<int64_t>());
             hashes = own_hashes->as<int64_t>();
@@ -2887,8 +2653,7 @@ public:
         BufferPtr replicate;
         if (null_flags || replicate_first) {
             replicate = ctx_->alloc((size_t)n);
-            replicate_flags_kernel<<<(int)std::min<int64_t>(ceil_div(n, 256), (int64_t)ctx_->cu_count() * 8), 256, 0, ctx_->stream()>>>(null_flags, n, replicate_first ? 1 : 0,
-                                                                                                                                    replicate->as<uint8_t>());
+            replicate_flags_kernel<<<grid_for(ctx_, n), 256, 0, ctx_->stream()>>>(null_flags, n, replicate_first ? 1 : 0, replicate->as<uint8_t>());
             check_launch("replicate_flags");
             has_any_row_been_replicated_ = true;   // :411-418 (row 0 if the flag was pending; null rows replicate regardless)
         }
@@ -2952,36 +2717,22 @@ private:
     std::deque<std::pair<int32_t, DevicePage>> pending_;
 };
 
-PartitionedOutputOperatorFactory::PartitionedOutputOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> partition_channels,
-                                                                   int32_t hash_channel, int32_t partition_count, bool replicates_any_row, int32_t null_channel,
-                                                                   int32_t partition_function)
-    : ctx_(ctx), operator_id_(operator_id), types_(std::move(types)), partition_channels_(std::move(partition_channels)), hash_channel_(hash_channel),
-      partition_count_(partition_count), null_channel_(null_channel), replicates_any_row_(replicates_any_row), local_function_(partition_function == TGPU_PARTITION_LOCAL)
+static void validate(Context *, const PartitionedOutputConfig &cfg)
 {
-    TG_CHECK_ARG(partition_count_ > 0 && partition_count_ <= 1024, "partition count must be in 1..1024");
-    TG_CHECK_ARG(partition_function == TGPU_PARTITION_HASH_MODULO || partition_function == TGPU_PARTITION_LOCAL, "unknown partition function");
-    if (local_function_) TG_CHECK_ARG((partition_count_ & (partition_count_ - 1)) == 0, "the local partition function needs a power-of-two partition count");
-    TG_CHECK_ARG(null_channel_ < (int)types_.size(), "null channel out of range");
-    if (hash_channel_ >= 0) TG_CHECK_ARG(hash_channel_ < (int)types_.size() && types_[(size_t)hash_channel_] == TGPU_BIGINT, "bad hash channel");
-    else TG_CHECK_ARG(!partition_channels_.empty(), "partitioning needs partition channels or a hash channel");
-    for (int32_t ch : partition_channels_) {
+    const int nt = (int)cfg.types.size();
+    TG_CHECK_ARG(cfg.partition_count > 0 && cfg.partition_count <= 1024, "partition count must be in 1..1024");
+    TG_CHECK_ARG(cfg.partition_function == TGPU_PARTITION_HASH_MODULO || cfg.partition_function == TGPU_PARTITION_LOCAL, "unknown partition function");
+    if (cfg.partition_function == TGPU_PARTITION_LOCAL)
+        TG_CHECK_ARG((cfg.partition_count & (cfg.partition_count - 1)) == 0, "the local partition function needs a power-of-two partition count");
+    TG_CHECK_ARG(cfg.null_channel < nt, "null channel out of range");
+    if (cfg.hash_channel >= 0) TG_CHECK_ARG(cfg.hash_channel < nt && cfg.types[(size_t)cfg.hash_channel] == TGPU_BIGINT, "bad hash channel");
+    else TG_CHECK_ARG(!cfg.partition_channels.empty(), "partitioning needs partition channels or a hash channel");
+    for (int32_t ch : cfg.partition_channels) {
         // (a negative channel = a constant partitioning argument in the reference, :433-448)
         if (ch < 0) fail(TGPU_ERR_NOT_SUPPORTED, "constant partitioning arguments are not supported");
-        TG_CHECK_ARG(ch < (int)types_.size(), "partition channel out of range");
+        TG_CHECK_ARG(ch < nt, "partition channel out of range");
     }
-    TG_CHECK_ARG((int)partition_channels_.size() <= kMaxKeyChannels, "at most 8 partition channels are supported");
-}
-
-std::unique_ptr<Operator> PartitionedOutputOperatorFactory::create_operator()
-{
-    TG_CHECK_STATE(!closed_, "Factory is already closed");
-    return std::make_unique<PartitionedOutputOperator>(ctx_, operator_id_, types_, partition_channels_, hash_channel_, partition_count_, replicates_any_row_, null_channel_,
-                                                       local_function_);
-}
-
-std::unique_ptr<OperatorFactory> PartitionedOutputOperatorFactory::duplicate()
-{
-    return std::unique_ptr<OperatorFactory>(new PartitionedOutputOperatorFactory(*this));
+    TG_CHECK_ARG((int)cfg.partition_channels.size() <= kMaxKeyChannels, "at most 8 partition channels are supported");
 }
 
 bool partitioned_output_poll(Operator *op, int32_t *partition, std::unique_ptr<OutputPage> *out)
@@ -3006,5 +2757,20 @@ void partitioned_output_info(Operator *op, int64_t *rows_added, int64_t *pages_a
     *rows_added = p->rows_added_;
     *pages_added = p->pages_added_;
 }
+
+// the plain factories (operators.h): instantiated here, where the operator classes are complete
+template class SimpleOperatorFactory<FilterAndProjectConfig, FilterAndProjectOperator>;
+template class SimpleOperatorFactory<ScanFilterAndProjectConfig, ScanFilterAndProjectOperator>;
+template class SimpleOperatorFactory<HashAggregationConfig, HashAggregationOperator>;
+template class SimpleOperatorFactory<TopNConfig, TopNOperator>;
+template class SimpleOperatorFactory<OrderByConfig, OrderByOperator>;
+template class SimpleOperatorFactory<DynamicFilterSourceConfig, DynamicFilterSourceOperator>;
+template class SimpleOperatorFactory<HashSemiJoinConfig, HashSemiJoinOperator>;
+template class SimpleOperatorFactory<MarkDistinctConfig, MarkDistinctOperator>;
+template class SimpleOperatorFactory<DistinctLimitConfig, DistinctLimitOperator>;
+template class SimpleOperatorFactory<RowNumberConfig, RowNumberOperator>;
+template class SimpleOperatorFactory<LimitConfig, LimitOperator>;
+template class SimpleOperatorFactory<MergePagesConfig, MergePagesOperator>;
+template class SimpleOperatorFactory<PartitionedOutputConfig, PartitionedOutputOperator>;
 
 }  // namespace tgpu

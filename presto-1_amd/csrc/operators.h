@@ -62,37 +62,41 @@ public:
     virtual std::unique_ptr<OperatorFactory> duplicate() { fail(TGPU_ERR_NOT_SUPPORTED, "this operator factory cannot be duplicated"); }
 
 protected:
+    void check_open() const { TG_CHECK_STATE(!closed_, "Factory is already closed"); }
     bool closed_ = false;
 };
 
-// ---- FilterAndProjectOperator (M/operator/FilterAndProjectOperator.java:37-65,117-147) ----------------------------
-class FilterAndProjectOperatorFactory : public OperatorFactory {
+// The factory of an operator that is described by a copyable Config alone.  The constructor runs validate(ctx, cfg) -- once, before any
+// operator exists; create_operator() hands the config to Op(ctx, operator_id, cfg); duplicate() copies it (shared_ptr members stay
+// shared: the compiled page processor, the SetSupplier).  The members are defined and instantiated in operators.cpp, next to the
+// operator classes.  Factories with bookkeeping of their own (join bridge, partition counting, fused kernels) are written out below.
+template <class Config, class Op> class SimpleOperatorFactory : public OperatorFactory {
 public:
-    FilterAndProjectOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec);
+    SimpleOperatorFactory(Context *ctx, int32_t operator_id, Config cfg);
     std::unique_ptr<Operator> create_operator() override;
     std::unique_ptr<OperatorFactory> duplicate() override;
+    Config &config() { return cfg_; }   // read by the operators created afterwards
 
 private:
     Context *ctx_;
     int32_t operator_id_;
-    std::shared_ptr<PageProcessorGpu> processor_;
+    Config cfg_;
 };
+
+// ---- FilterAndProjectOperator (M/operator/FilterAndProjectOperator.java:37-65,117-147) ----------------------------
+struct FilterAndProjectConfig {
+    std::shared_ptr<PageProcessorGpu> processor;   // PageProcessorGpu::shared(input types, spec)
+};
+using FilterAndProjectOperatorFactory = SimpleOperatorFactory<FilterAndProjectConfig, class FilterAndProjectOperator>;
 
 int64_t filter_project_dictionary_pages(Operator *op);
 
 // ---- ScanFilterAndProjectOperator (M/operator/ScanFilterAndProjectOperator.java:66-447), page-source flavour ------------------------
-class ScanFilterAndProjectOperatorFactory : public OperatorFactory {
-public:
-    ScanFilterAndProjectOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, const tgpu_page_processor_spec *spec);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_;
-    std::shared_ptr<PageProcessorGpu> processor_;
+struct ScanFilterAndProjectConfig {
+    std::vector<int32_t> types;
+    std::shared_ptr<PageProcessorGpu> processor;
 };
+using ScanFilterAndProjectOperatorFactory = SimpleOperatorFactory<ScanFilterAndProjectConfig, class ScanFilterAndProjectOperator>;
 void scan_add_page_source(Operator *op, const tgpu_page_source *source);
 void scan_no_more_splits(Operator *op);
 void scan_stats(Operator *op, int64_t *processed_positions, int64_t *lazy_loaded, int64_t *lazy_skipped);
@@ -109,19 +113,7 @@ struct HashAggregationConfig {
     bool spill_enabled = false;               // HashAggregationOperator.java:133,389-425: SINGLE / FINAL steps get the spillable builder
 };
 
-class HashAggregationOperatorFactory : public OperatorFactory {
-public:
-    HashAggregationOperatorFactory(Context *ctx, int32_t operator_id, HashAggregationConfig cfg);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-    void set_spill_enabled(bool on) { cfg_.spill_enabled = on; }
-    void set_max_partial_memory(int64_t bytes) { cfg_.max_partial_memory = bytes; }
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    HashAggregationConfig cfg_;
-};
+using HashAggregationOperatorFactory = SimpleOperatorFactory<HashAggregationConfig, class HashAggregationOperator>;   // spill_enabled / max_partial_memory: config()
 
 // ---- JoinFilterFunction (M/operator/JoinHash.java:44-47,118-130; M/sql/gen/JoinFilterFunctionCompiler.java): a predicate over
 // (build row, probe row) that a join position must pass besides key equality.  Input channels [0, build types) of the expression
@@ -325,8 +317,7 @@ public:
                                                  HashAggregationConfig cfg);
     std::unique_ptr<Operator> create_operator() override;
     std::unique_ptr<OperatorFactory> duplicate() override;
-    void set_spill_enabled(bool on) { cfg_.spill_enabled = on; }
-    void set_max_partial_memory(int64_t bytes) { cfg_.max_partial_memory = bytes; }
+    HashAggregationConfig &config() { return cfg_; }
 
 private:
     Context *ctx_;
@@ -379,164 +370,93 @@ private:
 };
 
 // ---- HashSemiJoinOperator (M/operator/HashSemiJoinOperator.java:44-218) -------------------------------------------------------------
-class HashSemiJoinOperatorFactory : public OperatorFactory {
-public:
-    HashSemiJoinOperatorFactory(Context *ctx, int32_t operator_id, std::shared_ptr<SetSupplier> supplier, std::vector<int32_t> probe_types,
-                                int32_t probe_join_channel, int32_t probe_hash_channel);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::shared_ptr<SetSupplier> supplier_;
-    std::vector<int32_t> probe_types_;
-    int32_t probe_join_channel_;
+struct HashSemiJoinConfig {
+    std::shared_ptr<SetSupplier> supplier;   // shared with every duplicate (HashSemiJoinOperator.java:115-118)
+    std::vector<int32_t> probe_types;
+    int32_t probe_join_channel = 0, probe_hash_channel = -1;
 };
+using HashSemiJoinOperatorFactory = SimpleOperatorFactory<HashSemiJoinConfig, class HashSemiJoinOperator>;
 
 // ---- MarkDistinctOperator (M/operator/MarkDistinctOperator.java:37-203) ---------------------------------------------------------------
-class MarkDistinctOperatorFactory : public OperatorFactory {
-public:
-    MarkDistinctOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> mark_channels, int32_t hash_channel);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, mark_channels_;
-    int32_t hash_channel_;
+struct MarkDistinctConfig {
+    std::vector<int32_t> types, mark_channels;
+    int32_t hash_channel = -1;
 };
+using MarkDistinctOperatorFactory = SimpleOperatorFactory<MarkDistinctConfig, class MarkDistinctOperator>;   // duplicate(): MarkDistinctOperator.java:87-91
 
 // ---- DistinctLimitOperator (M/operator/DistinctLimitOperator.java:40-263) ------------------------------------------------------------
-class DistinctLimitOperatorFactory : public OperatorFactory {
-public:
-    DistinctLimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> distinct_channels, int64_t limit,
-                                 int32_t hash_channel);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, distinct_channels_;
-    int64_t limit_;
-    int32_t hash_channel_;
+struct DistinctLimitConfig {
+    std::vector<int32_t> types, distinct_channels;
+    int64_t limit = 0;
+    int32_t hash_channel = -1;
 };
+using DistinctLimitOperatorFactory = SimpleOperatorFactory<DistinctLimitConfig, class DistinctLimitOperator>;   // duplicate(): DistinctLimitOperator.java:94-98
 
 // ---- RowNumberOperator (M/operator/RowNumberOperator.java:43-364) --------------------------------------------------------------------
-class RowNumberOperatorFactory : public OperatorFactory {
-public:
-    RowNumberOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> output_channels, std::vector<int32_t> partition_channels,
-                             int64_t max_rows_per_partition /* -1 = none */, int32_t hash_channel, int32_t expected_positions);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, output_channels_, partition_channels_;
-    int64_t max_rows_;
-    int32_t hash_channel_, expected_positions_;
+struct RowNumberConfig {
+    std::vector<int32_t> types, output_channels, partition_channels;
+    int64_t max_rows_per_partition = -1;   // -1 = none
+    int32_t hash_channel = -1, expected_positions = 10;
 };
+using RowNumberOperatorFactory = SimpleOperatorFactory<RowNumberConfig, class RowNumberOperator>;   // duplicate(): RowNumberOperator.java:114-118
 
 // ---- LimitOperator (M/operator/LimitOperator.java:25-120) ---------------------------------------------------------------------------
-class LimitOperatorFactory : public OperatorFactory {
-public:
-    LimitOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t limit);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_;
-    int64_t limit_;
+struct LimitConfig {
+    std::vector<int32_t> types;
+    int64_t limit = 0;
 };
+using LimitOperatorFactory = SimpleOperatorFactory<LimitConfig, class LimitOperator>;   // duplicate(): LimitOperator.java:55-59
 
 // ---- TopNOperator (M/operator/TopNOperator.java:47-62,135-225) ----------------------------------------------------------
-class TopNOperatorFactory : public OperatorFactory {
-public:
-    TopNOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t n, std::vector<int32_t> sort_channels,
-                        std::vector<int32_t> sort_orders);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, sort_channels_, sort_orders_;
-    int64_t n_;
+struct TopNConfig {
+    std::vector<int32_t> types;
+    int64_t n = 0;
+    std::vector<int32_t> sort_channels, sort_orders;
 };
+using TopNOperatorFactory = SimpleOperatorFactory<TopNConfig, class TopNOperator>;
 
 // ---- OrderByOperator (M/operator/OrderByOperator.java:48-131,160-300) ----------------------------------------------------
-class OrderByOperatorFactory : public OperatorFactory {
-public:
-    OrderByOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> output_channels, std::vector<int32_t> sort_channels,
-                           std::vector<int32_t> sort_orders);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, output_channels_, sort_channels_, sort_orders_;
+struct OrderByConfig {
+    std::vector<int32_t> types, output_channels, sort_channels, sort_orders;
 };
+using OrderByOperatorFactory = SimpleOperatorFactory<OrderByConfig, class OrderByOperator>;
 
 // ---- DynamicFilterSourceOperator (M/operator/DynamicFilterSourceOperator.java:46-425) ---------------------------------------------
 // Passes the build side's pages through and collects, per join-key channel, what the probe side's scan may be narrowed to.
-class DynamicFilterSourceOperatorFactory : public OperatorFactory {
+struct DynamicFilterSourceConfig {
+    std::vector<int32_t> types, channels;
+    int32_t max_distinct_values = 0;
+    int64_t max_filter_size_in_bytes = 0;
+    int32_t min_max_collection_limit = 0;
+};
+class DynamicFilterSourceOperatorFactory : public SimpleOperatorFactory<DynamicFilterSourceConfig, class DynamicFilterSourceOperator> {
 public:
-    DynamicFilterSourceOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> channels, int32_t max_distinct_values,
-                                       int64_t max_filter_size_in_bytes, int32_t min_max_collection_limit);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, channels_;
-    int32_t max_distinct_, min_max_limit_;
-    int64_t max_size_;
+    using SimpleOperatorFactory::SimpleOperatorFactory;
+    std::unique_ptr<OperatorFactory> duplicate() override;   // NOT_SUPPORTED, as in the reference (DynamicFilterSourceOperator.java:131-135)
 };
 // the collected domain of filter channel `k` after finish(): kind 0 = ALL, 1 = VALUES (*values: one channel holding the distinct
 // non-null, non-NaN values in first-seen order), 2 = RANGE [*min, *max] (BIGINT / INTEGER / DATE), 3 = NONE (only nulls were seen)
 void dynamic_filter_result(Operator *op, int32_t k, int32_t *kind, std::unique_ptr<OutputPage> *values, int64_t *min, int64_t *max);
 
 // ---- MergePages (M/operator/project/MergePages.java:40-190) as an operator: coalesces small pages in HBM -------------------------
-class MergePagesOperatorFactory : public OperatorFactory {
-public:
-    MergePagesOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, int64_t min_page_size_in_bytes, int32_t min_row_count,
-                              int64_t max_page_size_in_bytes);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_;
-    int64_t min_page_size_, max_page_size_;
-    int32_t min_row_count_;
+struct MergePagesConfig {
+    std::vector<int32_t> types;
+    int64_t min_page_size_in_bytes = 0;
+    int32_t min_row_count = 0;
+    int64_t max_page_size_in_bytes = 0;
 };
+using MergePagesOperatorFactory = SimpleOperatorFactory<MergePagesConfig, class MergePagesOperator>;
 
 // ---- PartitionedOutputOperator (M/operator/PartitionedOutputOperator.java:46-300; PagePartitioner :308-486) ---------------------
 // A sink: input rows are grouped by destination partition and handed out as (partition, page) pairs -- what the reference
 // enqueues into its OutputBuffer -- through poll(); get_output() returns nothing, as in the reference (:303-306).
-class PartitionedOutputOperator;
-class PartitionedOutputOperatorFactory : public OperatorFactory {
-public:
-    PartitionedOutputOperatorFactory(Context *ctx, int32_t operator_id, std::vector<int32_t> types, std::vector<int32_t> partition_channels, int32_t hash_channel,
-                                     int32_t partition_count, bool replicates_any_row, int32_t null_channel, int32_t partition_function);
-    std::unique_ptr<Operator> create_operator() override;
-    std::unique_ptr<OperatorFactory> duplicate() override;
-
-private:
-    Context *ctx_;
-    int32_t operator_id_;
-    std::vector<int32_t> types_, partition_channels_;
-    int32_t hash_channel_, partition_count_, null_channel_;
-    bool replicates_any_row_, local_function_;
+struct PartitionedOutputConfig {
+    std::vector<int32_t> types, partition_channels;
+    int32_t hash_channel = -1, partition_count = 1;
+    bool replicates_any_row = false;
+    int32_t null_channel = -1, partition_function = TGPU_PARTITION_HASH_MODULO;
 };
+using PartitionedOutputOperatorFactory = SimpleOperatorFactory<PartitionedOutputConfig, class PartitionedOutputOperator>;
 // next pending (partition, page) pair of a PartitionedOutputOperator; false = nothing pending
 bool partitioned_output_poll(Operator *op, int32_t *partition, std::unique_ptr<OutputPage> *out);
 void partitioned_output_pending(Operator *op, size_t *max_per_partition, int32_t *partition_count);

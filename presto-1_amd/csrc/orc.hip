@@ -358,14 +358,6 @@ __global__ void __launch_bounds__(256) place_lengths_kernel(const int32_t *__res
         out[i] = (nulls && nulls[i]) ? 0 : compact[rank ? rank[i] : i];
 }
 
-int grid_for(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, 256);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 BufferPtr upload_padded(Context *ctx, const uint8_t *src, int64_t bytes)
 {
     BufferPtr b = ctx->alloc((size_t)bytes + 32);   // read_bits looks up to 9 bytes past a value's first byte

@@ -164,13 +164,6 @@ __global__ void __launch_bounds__(256) copy_strings_kernel(const uint8_t *__rest
     }
 }
 
-int grid_for(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, 256);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(blocks, cap));
-}
-
 BufferPtr upload_padded(Context *ctx, const uint8_t *src, int64_t bytes)
 {
     BufferPtr b = ctx->alloc((size_t)bytes + 16);

@@ -17,14 +17,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-int grid_of(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, kBlock);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 __global__ void __launch_bounds__(kBlock) pair_keys_kernel(const int32_t *__restrict__ ids, int64_t n, unsigned int *__restrict__ keys, int32_t *__restrict__ positions)
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
@@ -80,7 +72,7 @@ void sort_pairs(Context *ctx, BufferPtr &keys, BufferPtr &positions, int64_t m, 
     BufferPtr temp = ctx->alloc(temp_bytes > 0 ? temp_bytes : 1);
     HIP_CHECK(rocprim::radix_sort_pairs(temp->ptr(), temp_bytes, keys->as<unsigned int>(), keys_out->as<unsigned int>(), positions->as<int>(), positions_out, (size_t)m, 0, end_bit,
                                         ctx->stream()));
-    partition_histogram_kernel<<<std::min(grid_of(ctx, m), ctx->cu_count() * 2), kBlock, 0, ctx->stream()>>>(keys->as<unsigned int>(), m, parts, (unsigned long long *)counts_dev);
+    partition_histogram_kernel<<<std::min(grid_for(ctx, m), ctx->cu_count() * 2), kBlock, 0, ctx->stream()>>>(keys->as<unsigned int>(), m, parts, (unsigned long long *)counts_dev);
     check_launch("partition_histogram");
 }
 
@@ -93,7 +85,7 @@ void partition_positions(Context *ctx, const int32_t *part_ids, int64_t n, int32
     if (n <= 0) return;
     ProfileScope ps(ctx, "partition_positions");
     BufferPtr keys = ctx->alloc((size_t)n * 4), positions = ctx->alloc((size_t)n * 4);
-    pair_keys_kernel<<<grid_of(ctx, n), kBlock, 0, ctx->stream()>>>(part_ids, n, keys->as<unsigned int>(), positions->as<int32_t>());
+    pair_keys_kernel<<<grid_for(ctx, n), kBlock, 0, ctx->stream()>>>(part_ids, n, keys->as<unsigned int>(), positions->as<int32_t>());
     check_launch("pair_keys");
     sort_pairs(ctx, keys, positions, n, partitions, positions_out, counts_dev);
 }
@@ -116,13 +108,13 @@ void partition_pairs(Context *ctx, const int32_t *part_ids, const uint8_t *repli
     }
     ProfileScope ps(ctx, "partition_positions");
     BufferPtr mult = ctx->alloc((size_t)n * 4), first = ctx->alloc((size_t)n * 4), total = ctx->alloc(8);
-    pair_multiplicity_kernel<<<grid_of(ctx, n), kBlock, 0, ctx->stream()>>>(replicate, n, partitions, mult->as<int32_t>());
+    pair_multiplicity_kernel<<<grid_for(ctx, n), kBlock, 0, ctx->stream()>>>(replicate, n, partitions, mult->as<int32_t>());
     check_launch("pair_multiplicity");
     exclusive_scan_i32(ctx, mult->as<int32_t>(), first->as<int32_t>(), n, total->as<int64_t>());
     const int64_t m = ctx->read_scalar(total->as<int64_t>());
     if (m > 0x7fffffffLL) fail(TGPU_ERR_INSUFFICIENT_RESOURCES, "replicated rows x partitions exceed 2 billion output rows for one page");
     BufferPtr keys = ctx->alloc((size_t)m * 4), positions = ctx->alloc((size_t)m * 4);
-    expand_pairs_kernel<<<grid_of(ctx, n), kBlock, 0, ctx->stream()>>>(part_ids, replicate, first->as<int32_t>(), n, partitions, keys->as<unsigned int>(),
+    expand_pairs_kernel<<<grid_for(ctx, n), kBlock, 0, ctx->stream()>>>(part_ids, replicate, first->as<int32_t>(), n, partitions, keys->as<unsigned int>(),
                                                                         positions->as<int32_t>());
     check_launch("expand_pairs");
     positions_out = ctx->alloc((size_t)m * 4);

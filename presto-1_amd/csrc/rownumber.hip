@@ -37,20 +37,6 @@ constexpr int kScanSlices = kScanBlock / 64;
 constexpr int64_t kMinChunk = 512;               // rows per wave below which a wave is not worth its row of the matrix
 constexpr int64_t kMatrixBytes = 8ll << 20;      // waves x G1 x 4 B stays within this
 
-int grid_of(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, kBlock);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
-void grow(Context *ctx, BufferPtr &buf, size_t need)
-{
-    if (buf && buf->bytes() >= need) return;
-    buf = ctx->alloc(std::max(need, buf ? buf->bytes() * 2 : (size_t)0));
-}
-
 // ---- few groups -----------------------------------------------------------------------------------------------------------------------
 // wave w owns rows [w * chunk, min(n, (w + 1) * chunk)); chunk is a multiple of 64.  A wave whose chunk is empty stores a row of zeros.
 __global__ void __launch_bounds__(kBlock) row_number_count_kernel(const int32_t *__restrict__ gids, int64_t n, int64_t chunk, int32_t groups,
@@ -201,12 +187,6 @@ __global__ void __launch_bounds__(kBlock) row_number_iota_kernel(int64_t *__rest
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) out[i] = base + i + 1;
 }
 
-__global__ void __launch_bounds__(kBlock) row_number_compact_kernel(const int32_t *__restrict__ keep, const int32_t *__restrict__ rank, int64_t n, int32_t *__restrict__ positions)
-{
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        if (keep[i]) positions[rank[i]] = (int32_t)i;   // rank[i] < kept rows <= n
-}
-
 int bits_of(int64_t groups)
 {
     int bits = 0;
@@ -287,7 +267,7 @@ void RowNumbererGpu::rank_sort(int64_t n, int64_t groups, int64_t *rn, int32_t *
     grow(ctx_, rows_sorted_, (size_t)n * 4);
     grow(ctx_, start_, (size_t)groups * 4);
     ProfileScope ps(ctx_, "row_number_sort");
-    const int g = grid_of(ctx_, n);
+    const int g = grid_for(ctx_, n);
     row_number_pairs_kernel<<<g, kBlock, 0, ctx_->stream()>>>(gids_->as<int32_t>(), n, keys_->as<unsigned int>(), rows_->as<int32_t>());
     check_launch("row_number_pairs");
     const unsigned int end_bit = (unsigned int)std::max(1, bits_of(groups));
@@ -340,7 +320,7 @@ int64_t RowNumbererGpu::select(const std::vector<const DeviceColumn *> &keys, co
     {
         ProfileScope ps(ctx_, "row_number_compact");
         k::exclusive_scan_i32(ctx_, keep_->as<int32_t>(), rank_->as<int32_t>(), n, total_->as<int64_t>());
-        row_number_compact_kernel<<<grid_of(ctx_, n), kBlock, 0, ctx_->stream()>>>(keep_->as<int32_t>(), rank_->as<int32_t>(), n, positions_->as<int32_t>());
+        k::compact_positions(ctx_, keep_->as<int32_t>(), rank_->as<int32_t>(), n, positions_->as<int32_t>());
         check_launch("row_number_compact");
     }
     const int64_t kept = ctx_->read_scalar(total_->as<int64_t>());
@@ -357,7 +337,7 @@ DeviceColumn RowNumbererGpu::iota(int64_t base, int64_t n)
     DeviceColumn out = bigint_column(ctx_, n);
     if (n == 0) return out;
     ProfileScope ps(ctx_, "row_number_iota");
-    row_number_iota_kernel<<<grid_of(ctx_, n), kBlock, 0, ctx_->stream()>>>(out.values_buf->as<int64_t>(), base, n);
+    row_number_iota_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(out.values_buf->as<int64_t>(), base, n);
     check_launch("row_number_iota");
     return out;
 }

@@ -23,14 +23,6 @@ constexpr int kBlock = 256;
 constexpr int kRows = 4;   // probe rows in flight per lane (their dependent word / slot loads overlap)
 constexpr unsigned long long kEmptyKey = 0x8000000000000000ull;   // INT64_MIN: never an INTEGER / DATE key
 
-int grid_for(Context *ctx, int64_t n, int64_t rows_per_block = kBlock)
-{
-    int64_t blocks = ceil_div(n, rows_per_block);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 __device__ __forceinline__ long long key_at(const ColView &c, int64_t r)
 {
     return c.type == TGPU_BIGINT ? ((const long long *)c.values)[r] : (long long)((const int *)c.values)[r];

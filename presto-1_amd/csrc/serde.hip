@@ -35,14 +35,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kHeaderBytes = 13;   // positionCount + markers + uncompressedSize + sizeInBytes
 
-int grid_for(Context *ctx, int64_t n)
-{
-    int64_t blocks = ceil_div(n, kBlock);
-    const int64_t cap = (int64_t)ctx->cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
-
 // ---- kernels ----------------------------------------------------------------------------------------------------------
 // packed null bits -> one byte per position (Java boolean[] valueIsNull) + the int32 not-null flags the scan consumes
 __global__ void __launch_bounds__(kBlock) unpack_null_bits_kernel(const uint8_t *__restrict__ packed, int64_t n, uint8_t *__restrict__ nulls,
