@@ -202,48 +202,51 @@ BufferPtr TopNGpu::sorted_positions(Context *ctx_, const DevicePage &page, const
         ProfileScope ps(ctx_, "topn_select");
         order_codes_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(keys->as<TopNKeys>(), n, codes->as<unsigned long long>(), rows->as<int>());
         check_launch("order_codes");
-        if (n > 4 * kSamples && want < kSamples / 2) {
-            // cutoff from a strided sample, then the rows at or below it, in input order
-            const int64_t stride = n / kSamples;
-            BufferPtr sample = ctx_->alloc((size_t)kSamples * 8), sample_sorted = ctx_->alloc((size_t)kSamples * 8);
-            sample_codes_kernel<<<grid_for(ctx_, kSamples), kBlock, 0, ctx_->stream()>>>(codes->as<unsigned long long>(), n, stride, kSamples, sample->as<unsigned long long>());
-            check_launch("sample_codes");
-            size_t temp_bytes = 0;
-            HIP_CHECK(rocprim::radix_sort_keys(nullptr, temp_bytes, sample->as<unsigned long long>(), sample_sorted->as<unsigned long long>(), (size_t)kSamples, 0, 64,
-                                               ctx_->stream()));
-            BufferPtr temp = ctx_->alloc(temp_bytes ? temp_bytes : 1);
-            HIP_CHECK(rocprim::radix_sort_keys(temp->ptr(), temp_bytes, sample->as<unsigned long long>(), sample_sorted->as<unsigned long long>(), (size_t)kSamples, 0, 64,
-                                               ctx_->stream()));
-            BufferPtr flags = ctx_->alloc((size_t)n * 4), offsets = ctx_->alloc((size_t)n * 4);
-            flag_candidates_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(codes->as<unsigned long long>(), n, sample_sorted->as<unsigned long long>() + (want - 1),
-                                                                                     flags->as<int>());
-            check_launch("flag_candidates");
-            k::exclusive_scan_i32(ctx_, flags->as<int32_t>(), offsets->as<int32_t>(), n, scalar->as<int64_t>());
-            BufferPtr crow = ctx_->alloc((size_t)n * 4), ccode = ctx_->alloc((size_t)n * 8);
-            compact_candidates_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(flags->as<int>(), offsets->as<int>(), codes->as<unsigned long long>(), n, crow->as<int>(),
-                                                                                        ccode->as<unsigned long long>());
-            check_launch("compact_candidates");
-            m = ctx_->read_scalar(scalar->as<long long>());
-            TG_CHECK_STATE(m >= want && m <= n, "candidate count out of range");
-            rows = crow;
-            codes = ccode;
-        }
-        if (m > std::max<int64_t>(8 * want, 1 << 18)) {
-            // still many candidates (coarse codes): order them by code and keep everything up to the ties of the n-th code
-            BufferPtr codes_sorted = ctx_->alloc((size_t)m * 8), rows_sorted = ctx_->alloc((size_t)m * 4);
-            size_t temp_bytes = 0;
-            HIP_CHECK(rocprim::radix_sort_pairs(nullptr, temp_bytes, codes->as<unsigned long long>(), codes_sorted->as<unsigned long long>(), rows->as<int>(),
-                                                rows_sorted->as<int>(), (size_t)m, 0, 64, ctx_->stream()));
-            BufferPtr temp = ctx_->alloc(temp_bytes ? temp_bytes : 1);
-            HIP_CHECK(rocprim::radix_sort_pairs(temp->ptr(), temp_bytes, codes->as<unsigned long long>(), codes_sorted->as<unsigned long long>(), rows->as<int>(),
-                                                rows_sorted->as<int>(), (size_t)m, 0, 64, ctx_->stream()));
-            candidate_count_kernel<<<1, 64, 0, ctx_->stream()>>>(codes_sorted->as<unsigned long long>(), m, want, scalar->as<long long>());
-            check_launch("candidate_count");
-            const int64_t m2 = ctx_->read_scalar(scalar->as<long long>());
-            TG_CHECK_STATE(m2 >= want && m2 <= m, "candidate count out of range");
-            m = m2;
-            rows = rows_sorted;
-        }
+    }
+    // the profile scopes of the next two blocks tell which route a page took
+    if (n > 4 * kSamples && want < kSamples / 2) {
+        // cutoff from a strided sample, then the rows at or below it, in input order
+        ProfileScope ps(ctx_, "topn_sample_cut");
+        const int64_t stride = n / kSamples;
+        BufferPtr sample = ctx_->alloc((size_t)kSamples * 8), sample_sorted = ctx_->alloc((size_t)kSamples * 8);
+        sample_codes_kernel<<<grid_for(ctx_, kSamples), kBlock, 0, ctx_->stream()>>>(codes->as<unsigned long long>(), n, stride, kSamples, sample->as<unsigned long long>());
+        check_launch("sample_codes");
+        size_t temp_bytes = 0;
+        HIP_CHECK(rocprim::radix_sort_keys(nullptr, temp_bytes, sample->as<unsigned long long>(), sample_sorted->as<unsigned long long>(), (size_t)kSamples, 0, 64,
+                                           ctx_->stream()));
+        BufferPtr temp = ctx_->alloc(temp_bytes ? temp_bytes : 1);
+        HIP_CHECK(rocprim::radix_sort_keys(temp->ptr(), temp_bytes, sample->as<unsigned long long>(), sample_sorted->as<unsigned long long>(), (size_t)kSamples, 0, 64,
+                                           ctx_->stream()));
+        BufferPtr flags = ctx_->alloc((size_t)n * 4), offsets = ctx_->alloc((size_t)n * 4);
+        flag_candidates_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(codes->as<unsigned long long>(), n, sample_sorted->as<unsigned long long>() + (want - 1),
+                                                                                 flags->as<int>());
+        check_launch("flag_candidates");
+        k::exclusive_scan_i32(ctx_, flags->as<int32_t>(), offsets->as<int32_t>(), n, scalar->as<int64_t>());
+        BufferPtr crow = ctx_->alloc((size_t)n * 4), ccode = ctx_->alloc((size_t)n * 8);
+        compact_candidates_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(flags->as<int>(), offsets->as<int>(), codes->as<unsigned long long>(), n, crow->as<int>(),
+                                                                                    ccode->as<unsigned long long>());
+        check_launch("compact_candidates");
+        m = ctx_->read_scalar(scalar->as<long long>());
+        TG_CHECK_STATE(m >= want && m <= n, "candidate count out of range");
+        rows = crow;
+        codes = ccode;
+    }
+    if (m > std::max<int64_t>(8 * want, 1 << 18)) {
+        // still many candidates (coarse codes): order them by code and keep everything up to the ties of the n-th code
+        ProfileScope ps(ctx_, "topn_code_radix");
+        BufferPtr codes_sorted = ctx_->alloc((size_t)m * 8), rows_sorted = ctx_->alloc((size_t)m * 4);
+        size_t temp_bytes = 0;
+        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, temp_bytes, codes->as<unsigned long long>(), codes_sorted->as<unsigned long long>(), rows->as<int>(),
+                                            rows_sorted->as<int>(), (size_t)m, 0, 64, ctx_->stream()));
+        BufferPtr temp = ctx_->alloc(temp_bytes ? temp_bytes : 1);
+        HIP_CHECK(rocprim::radix_sort_pairs(temp->ptr(), temp_bytes, codes->as<unsigned long long>(), codes_sorted->as<unsigned long long>(), rows->as<int>(),
+                                            rows_sorted->as<int>(), (size_t)m, 0, 64, ctx_->stream()));
+        candidate_count_kernel<<<1, 64, 0, ctx_->stream()>>>(codes_sorted->as<unsigned long long>(), m, want, scalar->as<long long>());
+        check_launch("candidate_count");
+        const int64_t m2 = ctx_->read_scalar(scalar->as<long long>());
+        TG_CHECK_STATE(m2 >= want && m2 <= m, "candidate count out of range");
+        m = m2;
+        rows = rows_sorted;
     }
     // the candidates, ordered by the full comparator
     BufferPtr sorted = ctx_->alloc((size_t)m * 4);
