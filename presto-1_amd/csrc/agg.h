@@ -36,10 +36,12 @@ public:
     GroupedAccumulators(Context *ctx, std::vector<tgpu_agg_spec> specs, int32_t step);
 
     // raw input (SINGLE / PARTIAL): gids == nullptr means one global group 0
-    void add_input(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count);
+    // gids_ascending: the caller knows that the ids never decrease from row to row (the group-by's run route): the ORDERED mode then
+    // skips its own check of that, and the read-back the check costs
+    void add_input(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending = false);
     // intermediate input (FINAL): aggregate k reads its state from channel spec.input_channel (count) and, for sum / avg,
     // spec.input_channel + 1 (sum)
-    void add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count);
+    void add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending = false);
     // appends the output channels for groups [0, group_count)
     void evaluate(int64_t group_count, std::vector<DeviceColumn> &out);
     // device state of aggregate k for groups [0, reserve()d): used by the JIT-fused project+accumulate kernels
@@ -122,7 +124,7 @@ private:
     enum class Mode { UNDECIDED, EXACT, ORDERED };
     void ensure(int64_t groups);
     void decide_mode(int64_t groups, int64_t lowcard_max_groups);
-    void sort_rows_by_group(const int32_t *gids, int64_t n, int64_t groups, BufferPtr &keys, BufferPtr &rows);
+    void sort_rows_by_group(const int32_t *gids, int64_t n, int64_t groups, BufferPtr &keys, BufferPtr &rows, bool gids_ascending = false);
     Mode mode_ = Mode::UNDECIDED;
     bool allow_ordered_ = false, force_ordered_ = false;
     Context *ctx_;

@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(kBlock) ordered_keys_kernel(const int32_t *__r
         rows[r] = (int)r;
         bad = bad || (r > 0 && gids[r - 1] > g);
     }
-    if (__any(bad) && (threadIdx.x & 63) == 0) *unsorted = 1u;   // idempotent plain store
+    if (unsorted && __any(bad) && (threadIdx.x & 63) == 0) *unsorted = 1u;   // idempotent plain store (null: the caller knows the order)
 }
 
 // {first, end} of every group's stretch of the sorted keys (the words start at 0)
@@ -885,13 +885,16 @@ BufferPtr GroupedAccumulators::group_stretches(const unsigned int *keys, int64_t
 }
 
 // (group id + 1, row) pairs of the page in (group, row) order: stable LSD radix sort on the bits the group ids use
-void GroupedAccumulators::sort_rows_by_group(const int32_t *gids, int64_t n, int64_t groups, BufferPtr &keys, BufferPtr &rows)
+void GroupedAccumulators::sort_rows_by_group(const int32_t *gids, int64_t n, int64_t groups, BufferPtr &keys, BufferPtr &rows, bool gids_ascending)
 {
-    BufferPtr keys_in = ctx_->alloc((size_t)n * 4), rows_in = ctx_->alloc((size_t)n * 4), unsorted = ctx_->alloc_zero(4);
-    ordered_keys_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(gids, n, keys_in->as<unsigned int>(), rows_in->as<int>(), unsorted->as<unsigned int>());
+    const bool always_sort = getenv("TGPU_ALWAYS_SORT") != nullptr;
+    const bool known = gids_ascending && !always_sort;   // ids from the group-by's run route: in order by construction
+    BufferPtr keys_in = ctx_->alloc((size_t)n * 4), rows_in = ctx_->alloc((size_t)n * 4), unsorted = known ? nullptr : ctx_->alloc_zero(4);
+    ordered_keys_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(gids, n, keys_in->as<unsigned int>(), rows_in->as<int>(),
+                                                                          known ? nullptr : unsorted->as<unsigned int>());
     check_launch("ordered_keys");
     // one small read-back (~25 us) against three or four radix sort passes over the page
-    if (getenv("TGPU_ALWAYS_SORT") == nullptr && ctx_->read_scalar(unsorted->as<unsigned int>()) == 0) {
+    if (known || (!always_sort && ctx_->read_scalar(unsorted->as<unsigned int>()) == 0)) {
         keys = keys_in;
         rows = rows_in;
         return;
@@ -908,7 +911,7 @@ void GroupedAccumulators::sort_rows_by_group(const int32_t *gids, int64_t n, int
                                         end_bit, ctx_->stream()));
 }
 
-void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count)
+void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
 {
     if (states_.empty() || n <= 0) return;
     BufferPtr zero_gids;
@@ -961,7 +964,7 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
         const bool chained = doubles <= TG_ORD_MAX_DOUBLES && ids <= ord_chain_max_groups() && n >= ids * kOrdChainMinRows && getenv("TGPU_DISABLE_ORDERED_CHAIN") == nullptr;
         ProfileScope ps(ctx_, chained ? "agg_accumulate_ordered_chain" : "agg_accumulate_ordered");
         BufferPtr keys, rows;
-        sort_rows_by_group(gids, n, group_count, keys, rows);
+        sort_rows_by_group(gids, n, group_count, keys, rows, gids_ascending);
         if (chained) {
             BufferPtr stretches = group_stretches(keys->as<unsigned int>(), n, ids);
             agg_ordered_chain_kernel<<<(int)ids, TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(args, plan, stretches->as<int>(), keys->as<unsigned int>(), rows->as<int>(), n, nullptr,
@@ -1028,7 +1031,7 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
     check_launch("agg_accumulate");
 }
 
-void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count)
+void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
 {
     if (states_.empty() || n <= 0) return;
     BufferPtr zero_gids;
@@ -1064,7 +1067,7 @@ void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const
         TG_CHECK_STATE(gids != nullptr, "ordered accumulation needs group ids");
         ProfileScope ps(ctx_, "agg_combine_ordered");
         BufferPtr keys, rows;
-        sort_rows_by_group(gids, n, group_count, keys, rows);
+        sort_rows_by_group(gids, n, group_count, keys, rows, gids_ascending && zero_gids == nullptr);
         agg_ordered_kernel<true><<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(args, keys->as<unsigned int>(), rows->as<int>(), n, error_->as<unsigned int>(), 0, nullptr,
                                                                                      nullptr);
         check_launch("agg_combine_ordered");

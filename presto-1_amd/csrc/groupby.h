@@ -29,6 +29,14 @@ using GbhProbeFn = std::function<void(const GbhProbeLaunch &)>;
 // gated on the counters being clean ([0] == 0 no row met a new group, [2] == 0 no table overflow, [7] == ~0 no expression error): in the
 // steady state of low-cardinality inputs the wait for the counters then overlaps the consumer instead of idling the device.
 using GbhSpeculateFn = std::function<void(const unsigned long long *counters)>;
+// What the run route (groupby.hip "Run route") tells a caller that asks: in = prefix_rows, the caller wants the number of groups among the
+// page's first prefix_rows rows (0 = not wanted); out = by_runs, the WHOLE page took the run route -- its ids are then non-decreasing and
+// prefix_groups holds the answer (it came back with the route's own read-back).
+struct GbhRunInfo {
+    int64_t prefix_rows = 0;
+    bool by_runs = false;
+    int64_t prefix_groups = 0;
+};
 
 // The single-integer-key table (groupby_bigint.hip): key inline in a 16-byte slot, one random line per row, one atomic per new group.
 // Used by GroupByHashGpu for one BIGINT key (as GroupByHash.createGroupByHash picks BigintGroupByHash, M/operator/GroupByHash.java:45-59)
@@ -73,9 +81,10 @@ public:
     // pipeline's HBM traffic.  Returns true when out_gids8 holds the page's ids (out_gids untouched), false when out_gids does.
     // speculate / *speculated (optional, compact mode): see GbhSpeculateFn; *speculated = the hook ran AND the counters came back clean
     // (what it enqueued took effect); false = it did not run, or ran and -- by its gate -- did nothing.
+    // run (optional): see GbhRunInfo
     bool get_group_ids(const std::vector<const DeviceColumn *> &keys, const int64_t *hashes, int64_t n, int32_t *out_gids,
                        const uint8_t *row_mask = nullptr, bool inline_hash = false, const GbhProbeFn *probe = nullptr, uint8_t *out_gids8 = nullptr,
-                       const GbhSpeculateFn *speculate = nullptr, bool *speculated = nullptr);
+                       const GbhSpeculateFn *speculate = nullptr, bool *speculated = nullptr, GbhRunInfo *run = nullptr);
     // lookup only (GroupByHash.contains): out[i] = group id or -1
     void lookup(const std::vector<const DeviceColumn *> &keys, const int64_t *hashes, int64_t n, int32_t *out_gids);
 
@@ -109,6 +118,12 @@ private:
     bool process_sub_batch(const KeyCols &batch, const int64_t *hashes, const uint8_t *row_mask, int64_t row0, int64_t n, int32_t *out_gids,
                            const GbhProbeFn *probe, int64_t *new_groups);
     void rebuild_table(int64_t min_capacity);
+    // run route: group ids of a sub-batch whose keys ascend run by run; false = they do not (nothing of the attempt is visible)
+    bool process_sub_batch_runs(const KeyCols &batch, const int64_t *hashes, int64_t n, int32_t *out_gids, int64_t probe_row, int64_t *new_groups,
+                                int64_t *prefix_groups);
+    void size_table(int64_t need_groups);   // ensure_table's sizing rule without the table (run mode)
+    void sync_table();                      // run mode: the table as the table route would have it (every published group inserted)
+    void leave_run_mode();
     KeyCols store_view() const;
     BufferPtr device_keys(const KeyCols &k);
     void advance_java_capacity();
@@ -122,8 +137,10 @@ private:
     bool optimistic_ = false;                     // the next sub-batch is an optimistic one (integer table)
     bool high_cardinality_ = false;               // the last sub-batch was mostly new groups: size the table from the page's row bound
     int64_t groups_ = 0;
-    int64_t capacity_ = 0;  // slots of the device table (uint64 words)
+    int64_t capacity_ = 0;  // slots of the device table (uint64 words); in run mode: of the table there will be on first need
     BufferPtr words_;
+    bool run_mode_ = false;       // every page so far took the run route: words_ is empty or holds groups [0, table_groups_) only
+    int64_t table_groups_ = 0;
     std::vector<KeyStore> store_;
     BufferPtr raw_hash_;
     int64_t raw_hash_cap_ = 0;

@@ -180,14 +180,273 @@ __global__ void __launch_bounds__(kBlock) gbh_resolve_kernel(int32_t *__restrict
 }
 
 // grow: re-insert every group into the new table (keys are distinct: only an empty slot is needed)
-__global__ void __launch_bounds__(kBlock) gbh_rehash_kernel(const int64_t *__restrict__ raw_hash, int64_t groups, uint64_t *words, uint64_t mask)
+__global__ void __launch_bounds__(kBlock) gbh_rehash_kernel(const int64_t *__restrict__ raw_hash, int64_t first, int64_t groups, uint64_t *words, uint64_t mask)
 {
-    for (int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += (int64_t)gridDim.x * kBlock) {
+    for (int64_t g = first + (int64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += (int64_t)gridDim.x * kBlock) {
         const uint64_t m = tg_fmix64((uint64_t)raw_hash[g]);
         uint64_t pos = m & mask;
         const uint64_t w = make_old((uint32_t)(m >> 48), (uint32_t)g);
         while (atomicCAS((unsigned long long *)&words[pos], (unsigned long long)kEmpty, (unsigned long long)w) != kEmpty) pos = (pos + 1) & mask;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Run route: a page whose rows are clustered by the group key, with the keys ascending from run to run (a scan stored by the key, or a
+// join that keeps the order of such a probe side: TPCH Q3's lineitem), needs no table to number its groups -- the groups are the runs of
+// equal keys, strictly ascending run heads mean that no key comes back after its run, and the first-seen id of a run is its index.
+//   heads   : row i is a head when its key differs from row i - 1's (row 0: from the key of the last group); every head must compare
+//             GREATER than its predecessor (lexicographic over the channels, values signed) -- anything else sets the violation word.
+//             A null key cell is a violation, too (the route is for the ordered integer keys of scans; nulls take the table).
+//   scan    : exclusive scan of the tiles' head counts; its total is the number of new groups
+//   publish : gid = groups + (heads at or before the row) - 1; heads store key cells and raw hash at their id.  A no-op after a violation.
+// Eligible: fixed-width integer-like channels (BIGINT, INTEGER, DATE, BOOLEAN), no row mask, no external probe kernel.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kRunIters = 8;
+constexpr int kRunTile = kBlock * kRunIters;   // rows per tile (2^20 rows = 512 tiles: their scan is one launch)
+
+// key of row ra against key of row rb: -1 less, 0 equal, 1 greater; 2 = row ra holds a null
+__device__ __forceinline__ int run_compare(const KeyCols &a, long long ra, const KeyCols &b, long long rb)
+{
+    int res = 0;
+    for (int c = 0; c < a.n; c++) {
+        const ColView &x = a.c[c], &y = b.c[c];
+        if (x.nulls && x.nulls[ra]) return 2;
+        if (res != 0) continue;   // decided by an earlier channel (the later ones are still looked at for nulls)
+        switch (x.type) {
+        case TGPU_BIGINT: {
+            const int64_t u = ((const int64_t *)x.values)[ra], v = ((const int64_t *)y.values)[rb];
+            res = u < v ? -1 : (u > v ? 1 : 0);
+            break;
+        }
+        case TGPU_INTEGER:
+        case TGPU_DATE: {
+            const int32_t u = ((const int32_t *)x.values)[ra], v = ((const int32_t *)y.values)[rb];
+            res = u < v ? -1 : (u > v ? 1 : 0);
+            break;
+        }
+        default: {   // TGPU_BOOLEAN (any non-zero byte is true, as in tg_rows_not_distinct)
+            const int u = ((const uint8_t *)x.values)[ra] != 0, v = ((const uint8_t *)y.values)[rb] != 0;
+            res = u - v;
+            break;
+        }
+        }
+    }
+    return res;
+}
+
+// 0: the row continues its predecessor's group, 1: it is a head, 2: violation
+__device__ __forceinline__ int run_head(const KeyCols &batch, long long r, const KeyCols &store, long long groups)
+{
+    int c;
+    if (r > 0) c = run_compare(batch, r, batch, r - 1);
+    else if (groups > 0) c = run_compare(batch, 0, store, groups - 1);
+    else c = run_compare(batch, 0, batch, 0) == 2 ? 2 : 1;
+    return c == 0 ? 0 : (c == 1 ? 1 : 2);
+}
+
+// One channel's part of the comparison of a thread's kRunIters rows with their predecessors: channel-outer, rows-inner, and no branch on
+// what was loaded, so the 2 x kRunIters loads of a channel are in flight together (row by row with an early exit, every load waited for
+// the one before: the launch ran at a quarter of this speed).  res: -1 / 0 / 1 as decided by the channels so far.
+template <typename T, bool BOOL>
+__device__ __forceinline__ void run_compare_channel(const T *__restrict__ p, int64_t base, int64_t n, int (&res)[kRunIters])
+{
+    T u[kRunIters], v[kRunIters];
+#pragma unroll
+    for (int it = 0; it < kRunIters; it++) {
+        const int64_t r = base + it * kBlock;
+        const bool live = r > 0 && r < n;
+        u[it] = live ? p[r] : T(0);
+        v[it] = live ? p[r - 1] : T(0);
+    }
+#pragma unroll
+    for (int it = 0; it < kRunIters; it++) {
+        const T a = BOOL ? T(u[it] != 0) : u[it], b = BOOL ? T(v[it] != 0) : v[it];
+        const int c = (a > b) - (a < b);
+        res[it] = res[it] != 0 ? res[it] : c;
+    }
+}
+
+// One channel's part of the publish pass: the cells of this thread's head rows go to the store at their ids, and into the rows' raw hashes
+template <typename T>
+__device__ __forceinline__ void run_publish_channel(const T *__restrict__ p, T *__restrict__ values, uint8_t *__restrict__ nulls, int64_t base, int64_t n,
+                                                    const long long (&gid)[kRunIters], const bool (&head)[kRunIters], long long (&h)[kRunIters])
+{
+    T v[kRunIters];
+#pragma unroll
+    for (int it = 0; it < kRunIters; it++) {
+        const int64_t r = base + it * kBlock;
+        v[it] = r < n ? p[r] : T(0);
+    }
+#pragma unroll
+    for (int it = 0; it < kRunIters; it++) {
+        long long cell;
+        if constexpr (sizeof(T) == 8) cell = tg_hash_long((long long)v[it]);
+        else if constexpr (sizeof(T) == 4) cell = tg_hash_int((int)v[it]);
+        else cell = tg_hash_boolean(v[it]);
+        h[it] = tg_combine_hash(h[it], cell);
+        if (head[it]) {
+            values[gid[it]] = v[it];
+            nulls[gid[it]] = 0;
+        }
+    }
+}
+
+// head state (run_head) of this thread's rows base + it * kBlock of the sub-batch; rows past n: 0
+__device__ __forceinline__ void run_tile_states(const KeyCols &batch, const KeyCols &store, long long groups, int64_t base, int64_t n, int (&state)[kRunIters])
+{
+    int res[kRunIters];
+    bool isnull[kRunIters];
+#pragma unroll
+    for (int it = 0; it < kRunIters; it++) {
+        res[it] = 0;
+        isnull[it] = false;
+    }
+    for (int c = 0; c < batch.n; c++) {
+        const ColView &x = batch.c[c];
+        if (x.nulls) {
+#pragma unroll
+            for (int it = 0; it < kRunIters; it++) {
+                const int64_t r = base + it * kBlock;
+                if (r < n) isnull[it] = isnull[it] || x.nulls[r] != 0;
+            }
+        }
+        switch (x.type) {
+        case TGPU_BIGINT: run_compare_channel<int64_t, false>((const int64_t *)x.values, base, n, res); break;
+        case TGPU_INTEGER:
+        case TGPU_DATE: run_compare_channel<int32_t, false>((const int32_t *)x.values, base, n, res); break;
+        default: run_compare_channel<uint8_t, true>((const uint8_t *)x.values, base, n, res); break;   // TGPU_BOOLEAN (any non-zero byte is true)
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < kRunIters; it++) {
+        const int64_t r = base + it * kBlock;
+        if (r >= n) state[it] = 0;
+        else if (r == 0) state[it] = run_head(batch, 0, store, groups);   // against the last group's stored key
+        else state[it] = isnull[it] ? 2 : (res[it] == 0 ? 0 : (res[it] > 0 ? 1 : 2));
+    }
+}
+
+// counters: [2] violation word.  A workgroup that finds it set at the start of a tile stops: a shuffled page costs about a launch.
+__global__ void __launch_bounds__(kBlock) gbh_run_heads_kernel(const KeyCols *keys_p, int64_t n, long long groups, int32_t *__restrict__ tile_counts,
+                                                                unsigned long long *counters)
+{
+    const KeyCols &batch = keys_p[0], &store = keys_p[1];
+    __shared__ int s_count[kBlock / 64];
+    __shared__ int s_stop;
+    const int64_t tiles = (n + kRunTile - 1) / kRunTile;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        if (threadIdx.x == 0) s_stop = *(volatile unsigned long long *)&counters[2] != 0;
+        __syncthreads();
+        if (s_stop) return;   // (uniform: every lane reads the same shared word)
+        int state[kRunIters];
+        run_tile_states(batch, store, groups, t * kRunTile + threadIdx.x, n, state);
+        int heads = 0;
+        bool bad = false;
+#pragma unroll
+        for (int it = 0; it < kRunIters; it++) {
+            heads += state[it] == 1;
+            bad = bad || state[it] == 2;
+        }
+        if (__any(bad) && (threadIdx.x & 63) == 0) counters[2] = 1ull;   // idempotent plain store
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) heads += __shfl_down(heads, d, 64);
+        if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = heads;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int total = 0;
+#pragma unroll
+            for (int w = 0; w < kBlock / 64; w++) total += s_count[w];
+            tile_counts[t] = total;
+        }
+    }
+}
+
+// counters: [2] violation word (set: nothing is written), [3] <- group id + 1 of row probe_row (the groups among the rows up to it)
+__global__ void __launch_bounds__(kBlock) gbh_run_publish_kernel(const KeyCols *keys_p, const int64_t *__restrict__ hashes, int64_t n, long long groups,
+                                                                  const int32_t *__restrict__ tile_offsets, int32_t *__restrict__ out,
+                                                                  int64_t *__restrict__ raw_hash, int64_t probe_row, unsigned long long *counters)
+{
+    if (counters[2] != 0) return;   // (uniform: written by the heads launch, which is complete)
+    const KeyCols &batch = keys_p[0], &store = keys_p[1];
+    constexpr int kWaves = kBlock / 64;
+    __shared__ int s_before[kRunIters * kWaves];   // heads of the tile before this wave's rows of iteration `it` (it-major = row order)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tiles = (n + kRunTile - 1) / kRunTile;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        int state[kRunIters];
+        run_tile_states(batch, store, groups, t * kRunTile + threadIdx.x, n, state);
+        unsigned long long ballots[kRunIters];
+#pragma unroll
+        for (int it = 0; it < kRunIters; it++) {
+            ballots[it] = __ballot(state[it] == 1);
+            if (lane == 0) s_before[it * kWaves + wave] = __popcll(ballots[it]);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            static_assert(kRunIters * kWaves <= 64, "one wave scans the tile's wave counts");
+            const int v = lane < kRunIters * kWaves ? s_before[lane] : 0;
+            int incl = v;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += o;
+            }
+            if (lane < kRunIters * kWaves) s_before[lane] = incl - v;
+        }
+        __syncthreads();
+        const long long tile_base = groups + tile_offsets[t];
+        const int64_t base = t * kRunTile + threadIdx.x;
+        long long gid[kRunIters];
+        bool head[kRunIters];
+#pragma unroll
+        for (int it = 0; it < kRunIters; it++) {
+            const int64_t r = base + it * kBlock;
+            gid[it] = tile_base + s_before[it * kWaves + wave] + __popcll(ballots[it] & ((2ULL << lane) - 1ULL)) - 1;
+            head[it] = state[it] == 1;
+            if (r < n) out[r] = (int32_t)gid[it];
+            if (r == probe_row) counters[3] = (unsigned long long)(gid[it] + 1);
+        }
+        // the heads' key cells go to the store channel by channel (the loads of a channel together, as in the comparison); the raw hash
+        // (tg_hash_row's recurrence; no cell is null on this route) is built up on the way
+        long long h[kRunIters];
+#pragma unroll
+        for (int it = 0; it < kRunIters; it++) h[it] = 0;
+        for (int c = 0; c < batch.n; c++) {
+            const ColView &s = batch.c[c];
+            const ColView &d = store.c[c];
+            switch (s.type) {
+            case TGPU_BIGINT: run_publish_channel<int64_t>((const int64_t *)s.values, (int64_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
+            case TGPU_INTEGER:
+            case TGPU_DATE: run_publish_channel<int32_t>((const int32_t *)s.values, (int32_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
+            default: run_publish_channel<uint8_t>((const uint8_t *)s.values, (uint8_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
+            }
+        }
+        if (hashes) {
+#pragma unroll
+            for (int it = 0; it < kRunIters; it++) {
+                const int64_t r = base + it * kBlock;
+                h[it] = r < n ? hashes[r] : 0;
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < kRunIters; it++)
+            if (head[it]) raw_hash[gid[it]] = h[it];
+        __syncthreads();   // s_before is rewritten by the next tile
+    }
+}
+
+// slots for `need_groups` groups at a fill of at most 0.75
+int64_t table_slots_for(int64_t need_groups)
+{
+    int64_t want = 1024;
+    while ((double)want * 0.75 < (double)need_groups + 1) want <<= 1;
+    return want;
+}
+
+bool runs_enabled()
+{
+    const char *e = getenv("TGPU_GBH_RUNS");   // 0: every page takes the table route (tests, A/B measurements)
+    return !(e && e[0] == '0');
 }
 
 // fastutil HashCommon.arraySize + BigintGroupByHash.calculateMaxFill, to report the Java table's capacity
@@ -233,6 +492,7 @@ GroupByHashGpu::GroupByHashGpu(Context *ctx, std::vector<int32_t> types, bool ha
     if (allow_integer_table && types_.size() == 1 && !(off && off[0] == '0') &&
         (types_[0] == TGPU_BIGINT || ((types_[0] == TGPU_INTEGER || types_[0] == TGPU_DATE) && !has_input_hash_)))
         integer_ = std::make_unique<BigintGroupTable>(ctx_, types_[0]);
+    run_mode_ = !integer_;   // until the first page that does not take the run route
 }
 
 int64_t GroupByHashGpu::estimated_size() const
@@ -255,21 +515,58 @@ void GroupByHashGpu::advance_java_capacity()
     }
 }
 
+// Run mode keeps no table: capacity_ follows ensure_table's rule (estimated_size reports the table there will be, so memory accounting
+// does not depend on the route) and the table is built on first need from the published groups -- their keys are distinct and their ids
+// known, so gbh_rehash_kernel's plain insert does.
+void GroupByHashGpu::size_table(int64_t need_groups)
+{
+    const int64_t want = table_slots_for(need_groups);
+    if (want <= capacity_) return;
+    if (want > (1ll << 31)) fail(TGPU_ERR_INSUFFICIENT_RESOURCES, "Size of hash table cannot exceed 1 billion entries");
+    capacity_ = want;
+    words_.reset();   // (a table built for a lookup in between: rebuilt at the new size when it is needed again)
+    table_groups_ = 0;
+}
+
+void GroupByHashGpu::sync_table()
+{
+    if (!run_mode_ || capacity_ == 0) return;
+    size_table(groups_);
+    if (!words_) {
+        words_ = ctx_->alloc((size_t)capacity_ * 8);
+        k::fill_u64(ctx_, words_->as<uint64_t>(), kEmpty, capacity_);
+        table_groups_ = 0;
+    }
+    if (table_groups_ < groups_) {
+        ProfileScope ps(ctx_, "gbh_rehash");
+        gbh_rehash_kernel<<<grid_for(ctx_, groups_ - table_groups_), kBlock, 0, ctx_->stream()>>>(raw_hash_->as<int64_t>(), table_groups_, groups_, words_->as<uint64_t>(),
+                                                                                                 (uint64_t)capacity_ - 1);
+        check_launch("gbh_rehash");
+    }
+    table_groups_ = groups_;
+}
+
+void GroupByHashGpu::leave_run_mode()
+{
+    sync_table();
+    run_mode_ = false;
+}
+
 void GroupByHashGpu::ensure_table(int64_t need_groups)
 {
-    int64_t want = 1024;
-    while ((double)want * 0.75 < (double)need_groups + 1) want <<= 1;
+    const int64_t want = table_slots_for(need_groups);
     if (want <= capacity_) return;
     if (want > (1ll << 31)) fail(TGPU_ERR_INSUFFICIENT_RESOURCES, "Size of hash table cannot exceed 1 billion entries");
     BufferPtr nw = ctx_->alloc((size_t)want * 8);
     k::fill_u64(ctx_, nw->as<uint64_t>(), kEmpty, want);
     if (groups_ > 0) {
         ProfileScope ps(ctx_, "gbh_rehash");
-        gbh_rehash_kernel<<<grid_for(ctx_, groups_), kBlock, 0, ctx_->stream()>>>(raw_hash_->as<int64_t>(), groups_, nw->as<uint64_t>(), (uint64_t)want - 1);
+        gbh_rehash_kernel<<<grid_for(ctx_, groups_), kBlock, 0, ctx_->stream()>>>(raw_hash_->as<int64_t>(), 0, groups_, nw->as<uint64_t>(), (uint64_t)want - 1);
         check_launch("gbh_rehash");
     }
     words_ = nw;
     capacity_ = want;
+    table_groups_ = groups_;
 }
 
 void GroupByHashGpu::ensure_store(int64_t need)
@@ -447,6 +744,42 @@ bool GroupByHashGpu::process_sub_batch(const KeyCols &batch, const int64_t *hash
     return true;
 }
 
+bool GroupByHashGpu::process_sub_batch_runs(const KeyCols &batch, const int64_t *hashes, int64_t n, int32_t *out, int64_t probe_row, int64_t *new_groups_out,
+                                            int64_t *prefix_groups_out)
+{
+    *new_groups_out = 0;
+    size_table(groups_ + std::min<int64_t>(n, sub_batch_));   // what the table route's ensure_table would make of capacity_
+    ensure_store(groups_ + n);                                // the row bound: the publish pass cannot write past the store
+    unsigned long long *ctr = fresh_counters();
+    const int64_t tiles = ceil_div(n, kRunTile);
+    BufferPtr counts = ctx_->alloc((size_t)tiles * 4), offsets = ctx_->alloc((size_t)tiles * 4);
+    {
+        ProfileScope ps(ctx_, "gbh_runs");
+        const KeyCols both[2] = {batch, store_view()};
+        BufferPtr dkeys = ctx_->alloc(sizeof(both));
+        ctx_->upload(dkeys->ptr(), both, sizeof(both));
+        const int g = grid_for(ctx_, n, kRunTile);
+        gbh_run_heads_kernel<<<g, kBlock, 0, ctx_->stream()>>>(dkeys->as<KeyCols>(), n, groups_, counts->as<int32_t>(), ctr);
+        check_launch("gbh_run_heads");
+        k::exclusive_scan_i32(ctx_, counts->as<int32_t>(), offsets->as<int32_t>(), tiles, (int64_t *)&ctr[1]);
+        gbh_run_publish_kernel<<<g, kBlock, 0, ctx_->stream()>>>(dkeys->as<KeyCols>(), hashes, n, groups_, offsets->as<int32_t>(), out, raw_hash_->as<int64_t>(), probe_row,
+                                                                ctr);
+        check_launch("gbh_run_publish");
+    }
+    unsigned long long host_ctr[8];
+    ctx_->download(host_ctr, ctr, sizeof(host_ctr));   // the attempt's one read-back: violation word, new groups, groups up to the probe row
+    if (host_ctr[2] != 0) return false;
+    const int64_t new_groups = (int64_t)host_ctr[1];
+    TG_CHECK_STATE(new_groups >= 0 && new_groups <= n, "run route: bad head count");
+    *prefix_groups_out = (int64_t)host_ctr[3];
+    groups_ += new_groups;
+    last_new_groups_ = new_groups;
+    *new_groups_out = new_groups;
+    if (new_groups > 0) advance_java_capacity();
+    size_table(groups_);   // (only an optimistic sub-batch of more than sub_batch_ rows can have outgrown the sizing above)
+    return true;
+}
+
 // drops every NEW mark of an aborted sub-batch by re-inserting the known groups into a fresh, larger table
 void GroupByHashGpu::rebuild_table(int64_t min_capacity)
 {
@@ -456,18 +789,21 @@ void GroupByHashGpu::rebuild_table(int64_t min_capacity)
     BufferPtr nw = ctx_->alloc((size_t)want * 8);
     k::fill_u64(ctx_, nw->as<uint64_t>(), kEmpty, want);
     if (groups_ > 0) {
-        gbh_rehash_kernel<<<grid_for(ctx_, groups_), kBlock, 0, ctx_->stream()>>>(raw_hash_->as<int64_t>(), groups_, nw->as<uint64_t>(), (uint64_t)want - 1);
+        gbh_rehash_kernel<<<grid_for(ctx_, groups_), kBlock, 0, ctx_->stream()>>>(raw_hash_->as<int64_t>(), 0, groups_, nw->as<uint64_t>(), (uint64_t)want - 1);
         check_launch("gbh_rehash");
     }
     words_ = nw;
     capacity_ = want;
 }
 
+static bool run_key_type(int32_t t) { return t == TGPU_BIGINT || t == TGPU_INTEGER || t == TGPU_DATE || t == TGPU_BOOLEAN; }
+
 bool GroupByHashGpu::get_group_ids(const std::vector<const DeviceColumn *> &keys, const int64_t *hashes, int64_t n, int32_t *out_gids,
                                    const uint8_t *row_mask, bool inline_hash, const GbhProbeFn *probe, uint8_t *out_gids8, const GbhSpeculateFn *speculate,
-                                   bool *speculated)
+                                   bool *speculated, GbhRunInfo *run)
 {
     if (speculated) *speculated = false;
+    if (run) run->by_runs = false;
     TG_CHECK_ARG(keys.size() == types_.size(), "wrong number of key channels");
     for (size_t i = 0; i < keys.size(); i++) TG_CHECK_ARG(keys[i]->type == types_[i], "group-by key channel type mismatch");
     if (n <= 0) return false;
@@ -482,12 +818,21 @@ bool GroupByHashGpu::get_group_ids(const std::vector<const DeviceColumn *> &keys
         (void)get_group_ids(keys, hashes, n, out_gids, row_mask, inline_hash, probe, nullptr);
         return false;
     }
+    if (run_mode_) {
+        bool eligible = probe == nullptr && out_gids8 == nullptr && row_mask == nullptr && runs_enabled();
+        for (int32_t t : types_) eligible = eligible && run_key_type(t);
+        if (!eligible) leave_run_mode();
+    }
+    bool all_runs = run_mode_;
+    const int64_t *table_hashes = hashes;   // the table route's raw hashes: materialised when it is first taken
     BufferPtr own_hashes;
-    if (!hashes && !inline_hash) {
+    auto need_hashes = [&] {
+        if (table_hashes || inline_hash) return;
         own_hashes = ctx_->alloc((size_t)n * 8);
         k::hash_rows(ctx_, key_cols_of(keys), n, own_hashes->as<int64_t>());
-        hashes = own_hashes->as<int64_t>();
-    }
+        table_hashes = own_hashes->as<int64_t>();
+    };
+    if (!run_mode_) need_hashes();
     // Sub-batching bounds the table growth a single launch can need.  Once a sub-batch created no new group (the steady state
     // of low-cardinality inputs: TPCH Q1 has 4 groups in 600 M rows) the next one is 64x larger: fewer, longer launches.  Such an
     // optimistic launch can overflow the table only if it meets tens of millions of new keys; the probe kernel then flags it,
@@ -495,6 +840,7 @@ bool GroupByHashGpu::get_group_ids(const std::vector<const DeviceColumn *> &keys
     // With few expected groups the very first launches ramp up from a small piece (2^14 rows): while the table is empty every
     // row takes the insert path and, with few distinct keys, they all contend for the same slots; once the first groups exist
     // the probe kernels answer from their cached copies.  next_sub_ persists across pages.
+    if (!run_mode_) hashes = table_hashes;
     int64_t sub = next_sub_;
     int64_t start = 0;
     while (start < n) {
@@ -506,6 +852,24 @@ bool GroupByHashGpu::get_group_ids(const std::vector<const DeviceColumn *> &keys
         for (auto &v : views) vp.push_back(&v);
         int64_t new_groups = 0;
         bool ok = true;
+        if (run_mode_) {
+            // the run route, cut into the table route's sub-batches so that capacity_, next_sub_ and last_new_groups_ evolve as they would there
+            const int64_t probe_row = run && run->prefix_rows > start && run->prefix_rows <= start + len ? run->prefix_rows - 1 - start : -1;
+            int64_t prefix_groups = 0;
+            if (process_sub_batch_runs(key_cols_of(vp), hashes ? hashes + start : nullptr, len, out_gids + start, probe_row, &new_groups, &prefix_groups)) {
+                if (run && probe_row >= 0) run->prefix_groups = prefix_groups;
+                start += len;
+                if (new_groups == 0) sub = sub >= (1ll << 17) ? (1ll << 30) : sub * 64;
+                else sub = sub < sub_batch_ ? std::min<int64_t>(sub * 8, sub_batch_) : sub_batch_;
+                next_sub_ = sub;
+                continue;
+            }
+            // the keys do not ascend run by run: the table takes over, for this sub-batch and for the life of the object
+            leave_run_mode();
+            all_runs = false;
+            need_hashes();
+            hashes = table_hashes;
+        }
         if (compact && groups_ == 0) {
             // nothing to look up yet: every group of this sub-batch is new, so the compact attempt would only be repeated
             BufferPtr tmp = ctx_->alloc((size_t)len * 4);
@@ -575,6 +939,7 @@ bool GroupByHashGpu::get_group_ids(const std::vector<const DeviceColumn *> &keys
         (void)get_group_ids(keys, hashes, n, out_gids, row_mask, inline_hash, probe, nullptr);
         return false;
     }
+    if (run) run->by_runs = all_runs;
     return out_gids8 != nullptr;
 }
 
@@ -633,6 +998,7 @@ void GroupByHashGpu::lookup(const std::vector<const DeviceColumn *> &keys, const
         k::hash_rows(ctx_, key_cols_of(keys), n, own_hashes->as<int64_t>());
         hashes = own_hashes->as<int64_t>();
     }
+    sync_table();   // run mode: the table is built (or brought up to date) for the first reader
     ensure_table(groups_);
     ensure_store(groups_ > 0 ? groups_ : 1);
     BufferPtr dbatch = device_keys(key_cols_of(keys)), dstore = device_keys(store_view());

@@ -499,24 +499,30 @@ protected:
     {
         const int32_t *gids = nullptr;
         BufferPtr gid_buf;
+        bool ascending = false;
         if (gbh_) {
             for (int32_t ch : cfg_.group_by_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)in.cols.size(), "group-by channel out of range");
             if (cfg_.hash_channel >= 0)
                 TG_CHECK_ARG(cfg_.hash_channel < (int)in.cols.size() && in.cols[(size_t)cfg_.hash_channel].type == TGPU_BIGINT, "bad hash channel");
             const auto [keys, hashes] = key_inputs(in, cfg_.group_by_channels, cfg_.hash_channel);
             gid_buf = ctx_->alloc((size_t)in.n * 4);
-            gbh_->get_group_ids(keys, hashes, in.n, gid_buf->as<int32_t>());
+            // a page that takes the group-by's run route brings along what the accumulate side would otherwise read back for itself: that its
+            // ids ascend (no sort check) and, for the page that crosses the mode prefix, the number of groups in front of the mark
+            GbhRunInfo run;
+            run.prefix_rows = prefix_rows_in(in.n);
+            gbh_->get_group_ids(keys, hashes, in.n, gid_buf->as<int32_t>(), nullptr, false, nullptr, nullptr, nullptr, nullptr, &run);
             gids = gid_buf->as<int32_t>();
-            if (hold_back(in, gid_buf, nullptr, /*lowcard_max_groups=*/0)) return;
+            ascending = run.by_runs;
+            if (hold_back(in, gid_buf, nullptr, /*lowcard_max_groups=*/0, &run)) return;
         }
-        accumulate_page(gids, in);
+        accumulate_page(gids, in, ascending);
     }
 
-    void accumulate_page(const int32_t *gids, const DevicePage &in)
+    void accumulate_page(const int32_t *gids, const DevicePage &in, bool gids_ascending = false)
     {
         const int64_t groups = gbh_ ? gbh_->group_count() : 1;
-        if (cfg_.step == TGPU_STEP_FINAL) accs_->add_intermediate(gids, in.n, in, groups);
-        else accs_->add_input(gids, in.n, in, groups);
+        if (cfg_.step == TGPU_STEP_FINAL) accs_->add_intermediate(gids, in.n, in, groups, gids_ascending);
+        else accs_->add_input(gids, in.n, in, groups, gids_ascending);
     }
 
     // ---- the DOUBLE mode is decided from the first kModePrefixRows rows of the stream, however they are cut into pages (agg.h) ----------------
@@ -526,11 +532,23 @@ protected:
     struct HeldPage {
         DevicePage page;
         BufferPtr gids, gids8;
+        bool ascending = false;   // the ids came from the group-by's run route
     };
-    bool hold_back(const DevicePage &in, const BufferPtr &gids, const BufferPtr &gids8, int64_t lowcard_max_groups)
+    static int64_t mode_prefix_rows()
+    {
+        return getenv("TGPU_MODE_PREFIX_ROWS") ? atoll(getenv("TGPU_MODE_PREFIX_ROWS")) : GroupedAccumulators::kModePrefixRows;   // (tests shorten it)
+    }
+    // how many rows of a page of n rows belong to the mode prefix when the page is the one that crosses the mark (hold_back's m); else 0
+    int64_t prefix_rows_in(int64_t n) const
+    {
+        if (!accs_ || accs_->decided()) return 0;
+        const int64_t prefix = mode_prefix_rows();
+        return rows_seen_ + n < prefix ? 0 : std::max<int64_t>(prefix - rows_seen_, 1);
+    }
+    bool hold_back(const DevicePage &in, const BufferPtr &gids, const BufferPtr &gids8, int64_t lowcard_max_groups, const GbhRunInfo *run = nullptr)
     {
         if (accs_->decided()) return false;
-        const int64_t prefix = getenv("TGPU_MODE_PREFIX_ROWS") ? atoll(getenv("TGPU_MODE_PREFIX_ROWS")) : GroupedAccumulators::kModePrefixRows;   // (tests shorten it)
+        const int64_t prefix = mode_prefix_rows();
         if (rows_seen_ + in.n < prefix) {
             HeldPage h;
             h.page = in;
@@ -538,13 +556,17 @@ protected:
             own_borrowed_columns(ctx_, h.page);
             h.gids = gids;
             h.gids8 = gids8;
+            h.ascending = run != nullptr && run->by_runs;
             held_.push_back(std::move(h));
             rows_seen_ += in.n;
             groups_in_prefix_ = gbh_->group_count();
             return true;
         }
         const int64_t m = prefix - rows_seen_;
-        const int64_t here = GroupedAccumulators::groups_among(ctx_, gids8 ? nullptr : gids->as<int32_t>(), gids8 ? gids8->as<uint8_t>() : nullptr, std::max<int64_t>(m, 1));
+        // a run-route page has the count already: its ids ascend, so the groups among its first m rows are id[m - 1] + 1
+        const bool known = run != nullptr && run->by_runs && run->prefix_rows == std::max<int64_t>(m, 1);
+        const int64_t here = known ? run->prefix_groups
+                                   : GroupedAccumulators::groups_among(ctx_, gids8 ? nullptr : gids->as<int32_t>(), gids8 ? gids8->as<uint8_t>() : nullptr, std::max<int64_t>(m, 1));
         accs_->decide(std::max(groups_in_prefix_, here), lowcard_max_groups);
         rows_seen_ += in.n;
         release_held();
@@ -561,7 +583,7 @@ protected:
     {
         std::vector<HeldPage> held = std::move(held_);
         held_.clear();
-        for (HeldPage &h : held) accumulate_page(h.gids ? h.gids->as<int32_t>() : nullptr, h.page);
+        for (HeldPage &h : held) accumulate_page(h.gids ? h.gids->as<int32_t>() : nullptr, h.page, h.ascending);
     }
 
 public:
