@@ -26,6 +26,7 @@
  *   - tgpu_set_builder_* / tgpu_hash_semi_join_* <-> M/operator/SetBuilderOperator.java:39-233, HashSemiJoinOperator.java:44-218, ChannelSet.java:62-108
  *   - tgpu_mark_distinct_* / tgpu_distinct_limit_* <-> M/operator/MarkDistinctOperator.java:37-203, MarkDistinctHash.java:31-87, DistinctLimitOperator.java:40-263
  *   - tgpu_row_number_* / tgpu_limit_* <-> M/operator/RowNumberOperator.java:43-364, LimitOperator.java:25-120
+ *   - tgpu_top_n_ranking_*       <-> M/operator/TopNRankingOperator.java:42-310, GroupedTopNRowNumberBuilder.java:99-188, GroupedTopNRankBuilder.java
  *   - tgpu_serialize_page / tgpu_deserialize_page <-> M/execution/buffer/PagesSerde.java:64-160, PagesSerdeUtil.java:45-71,
  *                                    S/block/{LongArray,IntArray,ByteArray,VariableWidth,RunLength,Dictionary}BlockEncoding.java, EncoderUtil.java:33-118
  *   - tgpu_exchange_*            <-> M/operator/PartitionedOutputOperator.java:406-476 -> M/operator/ExchangeOperator.java (the hop between
@@ -371,6 +372,30 @@ int32_t tgpu_row_number_factory_create(tgpu_context *ctx, int32_t operator_id, i
  * limit < 0 is TGPU_ERR_INVALID_ARGUMENT (:70). */
 int32_t tgpu_limit_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int64_t limit,
                                   tgpu_operator_factory **out);
+
+/* ---- row_number() / rank() OVER (PARTITION BY k ORDER BY x) <= n (LocalExecutionPlanner.visitTopNRanking) ---- */
+/* TopNRankingOperator.TopNRankingOperatorFactory (M/operator/TopNRankingOperator.java:42-156, :170-310; GroupedTopNRowNumberBuilder.java:99-188,
+ * GroupedTopNRankBuilder.java; row order = SimplePageWithPositionComparator.java:58-79, sort_orders as for tgpu_top_n_factory_create): the
+ * operator consumes pages until finish() (needs_input = not finishing) and then hands out ONE page, none for empty input: the output
+ * channels in the given order, then -- unless `partial` (generateRanking = !partial, :99) -- one BIGINT channel without nulls, the ranking.
+ * Partitions (the rows that agree on the partition channels; a null key is a value like any other; no partition channel = one partition,
+ * no hash) come out in the order of their keys' first arrival, the rows of a partition in the order of the sort channels, rows that
+ * compare equal in arrival order across all pages.  TGPU_RANKING_ROW_NUMBER keeps the first max_rank_per_partition rows of every
+ * partition in that order, numbered from 1.  TGPU_RANKING_RANK keeps every row whose rank (1 + the rows of its partition that sort
+ * strictly before it) is <= max_rank_per_partition: ties at the boundary are all kept, peers (rows the comparator calls equal: null =
+ * null, NaN = NaN, -0.0 before +0.0) carry the same rank.  TGPU_RANKING_DENSE_RANK (UnsupportedOperationException, :235-236), an unknown
+ * ranking type, max_rank_per_partition <= 0 or > 2^31 - 1 (a Java int, :96), expected_positions <= 0 (:98), no sort channel or more
+ * than 8, more than 8 partition channels, a channel or sort order out of range, a hash channel that is not BIGINT or comes without
+ * partition channels: TGPU_ERR_INVALID_ARGUMENT.  memory_bytes = the hash's estimated size + the candidate rows held (within a
+ * constant factor of partitions x max_rank_per_partition, plus one page), their group ids and one cutoff per partition. */
+typedef enum tgpu_ranking_type { TGPU_RANKING_ROW_NUMBER = 0, TGPU_RANKING_RANK = 1, TGPU_RANKING_DENSE_RANK = 2 } tgpu_ranking_type;
+int32_t tgpu_top_n_ranking_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t ranking_type,
+                                          int32_t type_count, const int32_t *types,
+                                          int32_t output_channel_count, const int32_t *output_channels,
+                                          int32_t partition_channel_count, const int32_t *partition_channels,
+                                          int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                          int64_t max_rank_per_partition, int32_t partial,
+                                          int32_t hash_channel /* -1 = none */, int32_t expected_positions, tgpu_operator_factory **out);
 
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of

@@ -121,6 +121,8 @@ public final class GpuNative
     public static native long createDistinctLimitFactory(long context, int operatorId, int[] types, int[] distinctChannels, long limit, int hashChannel);
     /** RowNumberOperatorFactory (tgpu_row_number_factory_create): the output channels + the BIGINT row number; maxRowsPerPartition -1 = none, hashChannel -1 = none */
     public static native long createRowNumberFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] partitionChannels, long maxRowsPerPartition, int hashChannel, int expectedPositions);
+    /** TopNRankingOperatorFactory (tgpu_top_n_ranking_factory_create): the output channels + (unless partial) the BIGINT ranking; rankingType / sortOrders are the enums' ordinals, hashChannel -1 = none */
+    public static native long createTopNRankingFactory(long context, int operatorId, int rankingType, int[] types, int[] outputChannels, int[] partitionChannels, int[] sortChannels, int[] sortOrders, long maxRankPerPartition, boolean partial, int hashChannel, int expectedPositions);
     /** LimitOperatorFactory (tgpu_limit_factory_create): the first limit rows of the stream */
     public static native long createLimitFactory(long context, int operatorId, int[] types, long limit);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);

@@ -10,6 +10,7 @@ import io.trino.spi.connector.SortOrder;
 import io.trino.spi.type.Type;
 import io.trino.sql.planner.plan.AggregationNode.Step;
 import io.trino.sql.planner.plan.PlanNodeId;
+import io.trino.sql.planner.plan.TopNRankingNode.RankingType;
 import io.trino.sql.relational.RowExpression;
 
 import java.util.List;
@@ -400,6 +401,30 @@ public final class GpuOperatorFactories
         long factory = GpuNative.createRowNumberFactory(context, operatorId, codes, ints(outputChannels), ints(partitionChannels),
                 maxRowsPerPartition.map(Integer::longValue).orElse(-1L), hashChannel.orElse(-1), expectedPositions);
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuRowNumberOperator", sourceTypes, poller, factory));
+    }
+
+    /**
+     * TopNRankingOperator.TopNRankingOperatorFactory (operator/TopNRankingOperator.java:67-104; LocalExecutionPlanner.visitTopNRanking): row_number() / rank() OVER
+     * (PARTITION BY .. ORDER BY ..) <= maxRankPerPartition.  The output channels, then (unless partial) the BIGINT ranking.  DENSE_RANK stays with the reference's
+     * operator, which throws UnsupportedOperationException for it (:235-236).
+     */
+    public Optional<OperatorFactory> topNRanking(int operatorId, PlanNodeId planNodeId, RankingType rankingType, List<Type> sourceTypes, List<Integer> outputChannels,
+            List<Integer> partitionChannels, List<Integer> sortChannels, List<SortOrder> sortOrders, int maxRankPerPartition, boolean partial, OptionalInt hashChannel,
+            int expectedPositions)
+    {
+        if (rankingType == RankingType.DENSE_RANK) {
+            return Optional.empty();
+        }
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createTopNRankingFactory(context, operatorId, rankingType.ordinal(), codes, ints(outputChannels), ints(partitionChannels), ints(sortChannels),
+                sortOrders.stream().mapToInt(SortOrder::ordinal).toArray(), maxRankPerPartition, partial, hashChannel.orElse(-1), expectedPositions);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuTopNRankingOperator", sourceTypes, poller, factory));
     }
 
     /** LimitOperator.LimitOperatorFactory (operator/LimitOperator.java:34-39; LocalExecutionPlanner.visitLimit) */

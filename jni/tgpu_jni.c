@@ -677,6 +677,58 @@ JFN(jlong, createRowNumberFactory)(JNIEnv *env, jclass c, jlong ctx, jint operat
     return factory_result(env, rc, f);
 }
 
+/* TopNRankingOperatorFactory (operator/TopNRankingOperator.java:42-156): row_number() / rank() OVER (PARTITION BY .. ORDER BY ..) <= maxRankPerPartition; the
+ * output channels + (unless partial) the BIGINT ranking.  rankingType: tgpu_ranking_type = RankingType's ordinal; sortOrders: SortOrder's ordinal.
+ * Checked in front of the library: ROW_NUMBER or RANK, every output / partition / sort channel in [0, types), 1 .. 8 sort channels with as many
+ * sort orders in [0, 3], at most 8 partition channels, hashChannel -1 or a BIGINT channel and only with partition channels,
+ * 0 < maxRankPerPartition <= 2^31 - 1, expectedPositions > 0 */
+JFN(jlong, createTopNRankingFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jint rankingType, jintArray types, jintArray outputChannels,
+                                     jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders, jlong maxRankPerPartition, jboolean partial,
+                                     jint hashChannel, jint expectedPositions)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types), oc = ints_get(env, outputChannels), pc = ints_get(env, partitionChannels), sc = ints_get(env, sortChannels),
+         so = ints_get(env, sortOrders);
+    const char *bad = NULL;
+    if (rankingType == TGPU_RANKING_DENSE_RANK) bad = "dense_rank is not supported";
+    else if (rankingType != TGPU_RANKING_ROW_NUMBER && rankingType != TGPU_RANKING_RANK) bad = "unknown ranking type";
+    if (!bad && t.n <= 0) bad = "empty type array";
+    for (jsize i = 0; !bad && i < oc.n; i++)
+        if (oc.p[i] < 0 || oc.p[i] >= t.n) bad = "output channel out of range";
+    if (!bad && pc.n > 8) bad = "more than 8 partition channels";
+    for (jsize i = 0; !bad && i < pc.n; i++)
+        if (pc.p[i] < 0 || pc.p[i] >= t.n) bad = "partition channel out of range";
+    if (!bad && sc.n != so.n) bad = "sort channels and sort orders differ in length";
+    if (!bad && (sc.n <= 0 || sc.n > 8)) bad = "1 to 8 sort channels";
+    for (jsize i = 0; !bad && i < sc.n; i++) {
+        if (sc.p[i] < 0 || sc.p[i] >= t.n) bad = "sort channel out of range";
+        else if (so.p[i] < TGPU_SORT_ASC_NULLS_FIRST || so.p[i] > TGPU_SORT_DESC_NULLS_LAST) bad = "sort order out of range";
+    }
+    if (!bad && (hashChannel < -1 || hashChannel >= t.n)) bad = "hash channel out of range";
+    if (!bad && hashChannel >= 0 && pc.n <= 0) bad = "hash channel without partition channels";
+    if (!bad && hashChannel >= 0 && t.p[hashChannel] != TGPU_BIGINT) bad = "hash channel is not BIGINT";
+    if (!bad && (maxRankPerPartition <= 0 || maxRankPerPartition > 0x7fffffffLL)) bad = "max rank per partition must be a positive int";
+    if (!bad && expectedPositions <= 0) bad = "expected positions must be positive";
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad)
+        rc = tgpu_top_n_ranking_factory_create(H(tgpu_context, ctx), operatorId, rankingType, t.n, (const int32_t *)t.p, oc.n, (const int32_t *)oc.p, pc.n,
+                                               (const int32_t *)pc.p, sc.n, (const int32_t *)sc.p, (const int32_t *)so.p, maxRankPerPartition, partial ? 1 : 0,
+                                               hashChannel, expectedPositions, &f);
+    ints_release(env, &so);
+    ints_release(env, &sc);
+    ints_release(env, &pc);
+    ints_release(env, &oc);
+    ints_release(env, &t);
+    if (bad) {
+        char message[96];
+        snprintf(message, sizeof(message), "top n ranking: %s", bad);
+        throw_native_message(env, TGPU_ERR_INVALID_ARGUMENT, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
+
 /* LimitOperatorFactory (operator/LimitOperator.java:26-60): the first `limit` rows of the stream */
 JFN(jlong, createLimitFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong limit)
 {

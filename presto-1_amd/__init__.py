@@ -11,5 +11,6 @@ from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_
                         LookupJoinOperatorFactory, LookupOuterOperatorFactory, Operator, OperatorFactory, page_processor_source, fused_probe_launch_counts, precompile_fused_aggregation, precompile_fused_probe, precompile_page_processor, to_pages,
                         SET_BITMAP, SET_GENERIC, SET_HASH, HashSemiJoinOperatorFactory, SetBuilderOperatorFactory, SetSupplier,
                         DistinctLimitOperatorFactory, MarkDistinctOperatorFactory,
-                        LimitOperatorFactory, RowNumberOperatorFactory)
+                        LimitOperatorFactory, RowNumberOperatorFactory,
+                        DENSE_RANK, RANK, ROW_NUMBER, TopNRankingOperatorFactory)
 from .spi import (BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR, Block, DeviceBlock, DictionaryBlock, LazyBlock, OutputPage, Page, RunLengthEncodedBlock)

@@ -179,6 +179,7 @@ SYMBOLS = {
     "tgpu_set_supplier_destroy": (None, [vp]),
     "tgpu_mark_distinct_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(vp)]),
     "tgpu_distinct_limit_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i64, i32, P(vp)]),
+    "tgpu_top_n_ranking_factory_create": (i32, [vp, i32, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, P(i32), P(i32), i64, i32, i32, i32, P(vp)]),
     "tgpu_row_number_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), i64, i32, i32, P(vp)]),
     "tgpu_limit_factory_create": (i32, [vp, i32, i32, P(i32), i64, P(vp)]),
     "tgpu_merge_pages_factory_create": (i32, [vp, i32, i32, P(i32), i64, i32, i64, P(vp)]),

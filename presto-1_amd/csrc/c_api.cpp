@@ -1228,6 +1228,20 @@ int32_t tgpu_distinct_limit_factory_create(tgpu_context *ctx, int32_t operator_i
     });
 }
 
+int32_t tgpu_top_n_ranking_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t ranking_type, int32_t type_count, const int32_t *types,
+                                          int32_t output_channel_count, const int32_t *output_channels, int32_t partition_channel_count,
+                                          const int32_t *partition_channels, int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                          int64_t max_rank_per_partition, int32_t partial, int32_t hash_channel, int32_t expected_positions, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        make_factory<TopNRankingOperatorFactory>(ctx, out, operator_id,
+                                                 TopNRankingConfig{ranking_type, vec(types, type_count), vec(output_channels, output_channel_count),
+                                                                   vec(partition_channels, partition_channel_count), vec(sort_channels, sort_channel_count),
+                                                                   vec(sort_orders, sort_channel_count), max_rank_per_partition, partial != 0, hash_channel,
+                                                                   expected_positions});
+    });
+}
+
 int32_t tgpu_row_number_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t output_channel_count,
                                        const int32_t *output_channels, int32_t partition_channel_count, const int32_t *partition_channels,
                                        int64_t max_rows_per_partition, int32_t hash_channel, int32_t expected_positions, tgpu_operator_factory **out)

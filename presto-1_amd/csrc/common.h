@@ -174,6 +174,9 @@ public:
     void profile_end();
     bool in_profile_scope() const { return cur_name_ != nullptr; }
     void profile_collect();
+    // a pseudo entry of the profile that is no time (rows an operator dropped, the size of a store): count += value, max_ms = the largest
+    // value noted.  Nothing while profiling is off.
+    void profile_note(const char *name, int64_t value);
     std::string profile_json();
 
     int cu_count() const { return cu_count_; }

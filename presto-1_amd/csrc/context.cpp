@@ -525,6 +525,16 @@ void Context::profile_end()
     if (pending_.size() > 4096) profile_collect();
 }
 
+void Context::profile_note(const char *name, int64_t value)
+{
+    if (!profiling_) return;
+    std::lock_guard<std::recursive_mutex> io(io_mu_);
+    KernelStat &s = stats_[name];
+    s.count += value;
+    s.min_ms = 0;
+    if ((double)value > s.max_ms) s.max_ms = (double)value;
+}
+
 void Context::profile_collect()
 {
     std::lock_guard<std::recursive_mutex> io(io_mu_);

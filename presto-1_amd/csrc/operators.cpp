@@ -2450,6 +2450,83 @@ static void validate(Context *, const RowNumberConfig &cfg)
 }
 
 // =====================================================================================================================
+// TopNRankingOperator (M/operator/TopNRankingOperator.java:170-310): row_number() / rank() OVER (PARTITION BY k ORDER BY x) <= n.  Consumes
+// pages until finish() (needsInput :261-266), then hands out the kept rows as ONE page (as TopNOperator and OrderByOperator do here):
+// the output channels, then -- unless partial -- the BIGINT ranking (generateRanking, :99).  The work is GroupedTopNGpu's
+// (topn_ranking.hip); rows that compare equal rank in arrival order.
+// =====================================================================================================================
+class TopNRankingOperator : public Operator {
+public:
+    TopNRankingOperator(Context *ctx, int32_t id, const TopNRankingConfig &cfg)
+        : Operator(ctx, id), cfg_(cfg),
+          top_(ctx, cfg.types, cfg.partition_channels, cfg.sort_channels, cfg.sort_orders, cfg.ranking_type, cfg.max_rank_per_partition, cfg.hash_channel,
+               cfg.expected_positions)
+    {
+        // Switches, read here (as TGPU_ROW_NUMBER_PATH is): TGPU_TOP_N_RANKING_PREFILTER=off keeps every row of a page for the selection,
+        // TGPU_TOP_N_RANKING_COMPACT_ROWS=<k> replaces the floor below which the store is not compacted.  The baselines of
+        // tools/exp_top_n_ranking.py; the tests reach every path with small inputs through them.
+        const char *e = getenv("TGPU_TOP_N_RANKING_PREFILTER");
+        top_.set_prefilter(!(e != nullptr && !strcmp(e, "off")));
+        e = getenv("TGPU_TOP_N_RANKING_COMPACT_ROWS");
+        if (e != nullptr && *e) top_.set_compact_floor(std::max<int64_t>(1, strtoll(e, nullptr, 10)));
+        e = getenv("TGPU_TOP_N_RANKING_SLICE_ROWS");   // a third one, for the tests alone: the slice length of GroupedTopNGpu::kSliceRows
+        if (e != nullptr && *e) top_.set_slice_rows(std::max<int64_t>(1, strtoll(e, nullptr, 10)));
+    }
+
+    bool needs_input() override { return !finishing_; }   // :261-266
+
+    void add_input(const tgpu_page *page) override
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        top_.add_page(ingest_page(ctx_, page));
+    }
+
+    std::unique_ptr<OutputPage> get_output() override
+    {
+        if (!finishing_ || finished_) return nullptr;
+        finished_ = true;
+        DeviceColumn ranking;
+        DevicePage all = top_.result(&ranking);
+        if (all.n == 0) return nullptr;
+        DevicePage out;
+        out.n = all.n;
+        for (int32_t ch : cfg_.output_channels) out.cols.push_back(all.cols[(size_t)ch]);
+        if (!cfg_.partial) out.cols.push_back(std::move(ranking));
+        return wrap(std::move(out));
+    }
+
+    void finish() override { finishing_ = true; }
+    bool is_finished() override { return finished_ || (finishing_ && top_.position_count() == 0); }
+    int64_t memory_bytes() override { return top_.estimated_size(); }
+
+private:
+    TopNRankingConfig cfg_;
+    GroupedTopNGpu top_;
+    bool finishing_ = false, finished_ = false;
+};
+
+static void validate(Context *, const TopNRankingConfig &cfg)
+{
+    const int nt = (int)cfg.types.size();
+    TG_CHECK_ARG(cfg.ranking_type != TGPU_RANKING_DENSE_RANK, "dense_rank is not supported");   // UnsupportedOperationException, TopNRankingOperator.java:235-236
+    TG_CHECK_ARG(cfg.ranking_type == TGPU_RANKING_ROW_NUMBER || cfg.ranking_type == TGPU_RANKING_RANK, "unknown ranking type");
+    TG_CHECK_ARG(!cfg.types.empty(), "top n ranking needs at least one source channel");
+    for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown type");
+    for (int32_t ch : cfg.output_channels) TG_CHECK_ARG(ch >= 0 && ch < nt, "output channel out of range");
+    TG_CHECK_ARG((int)cfg.partition_channels.size() <= kMaxKeyChannels, "at most 8 partition channels are supported");
+    for (int32_t ch : cfg.partition_channels) TG_CHECK_ARG(ch >= 0 && ch < nt, "partition channel out of range");
+    TG_CHECK_ARG(!cfg.sort_channels.empty() && cfg.sort_channels.size() == cfg.sort_orders.size(), "sort channels and sort orders: at least one, equally many");
+    TG_CHECK_ARG((int)cfg.sort_channels.size() <= kMaxKeyChannels, "at most 8 sort channels are supported");
+    for (int32_t ch : cfg.sort_channels) TG_CHECK_ARG(ch >= 0 && ch < nt, "sort channel out of range");
+    for (int32_t o : cfg.sort_orders) TG_CHECK_ARG(o >= TGPU_SORT_ASC_NULLS_FIRST && o <= TGPU_SORT_DESC_NULLS_LAST, "unknown sort order");
+    TG_CHECK_ARG(cfg.max_rank_per_partition > 0 && cfg.max_rank_per_partition <= 0x7fffffffLL, "max rank per partition must be a positive int");   // :96, :199
+    TG_CHECK_ARG(cfg.expected_positions > 0, "expected positions must be positive");
+    TG_CHECK_ARG(cfg.hash_channel >= -1 && cfg.hash_channel < nt, "hash channel out of range");
+    TG_CHECK_ARG(cfg.hash_channel < 0 || !cfg.partition_channels.empty(), "a hash channel needs partition channels");
+    TG_CHECK_ARG(cfg.hash_channel < 0 || cfg.types[(size_t)cfg.hash_channel] == TGPU_BIGINT, "hash channel must be BIGINT");
+}
+
+// =====================================================================================================================
 // LimitOperator (M/operator/LimitOperator.java:62-119): whole pages pass through while they fit, the crossing page is a region of its
 // first `remaining` rows, finish() zeroes the remainder.  No kernel.
 // =====================================================================================================================
@@ -2792,6 +2869,7 @@ template class SimpleOperatorFactory<MarkDistinctConfig, MarkDistinctOperator>;
 template class SimpleOperatorFactory<DistinctLimitConfig, DistinctLimitOperator>;
 template class SimpleOperatorFactory<RowNumberConfig, RowNumberOperator>;
 template class SimpleOperatorFactory<LimitConfig, LimitOperator>;
+template class SimpleOperatorFactory<TopNRankingConfig, TopNRankingOperator>;
 template class SimpleOperatorFactory<MergePagesConfig, MergePagesOperator>;
 template class SimpleOperatorFactory<PartitionedOutputConfig, PartitionedOutputOperator>;
 

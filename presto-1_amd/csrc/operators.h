@@ -14,6 +14,7 @@
 #include "join.h"
 #include "semijoin.h"
 #include "topn.h"
+#include "topn_ranking.h"
 
 namespace tgpu {
 
@@ -406,6 +407,16 @@ struct LimitConfig {
     int64_t limit = 0;
 };
 using LimitOperatorFactory = SimpleOperatorFactory<LimitConfig, class LimitOperator>;   // duplicate(): LimitOperator.java:55-59
+
+// ---- TopNRankingOperator (M/operator/TopNRankingOperator.java:42-156, :170-310) ---------------------------------------------------------
+struct TopNRankingConfig {
+    int32_t ranking_type = TGPU_RANKING_ROW_NUMBER;
+    std::vector<int32_t> types, output_channels, partition_channels, sort_channels, sort_orders;
+    int64_t max_rank_per_partition = 0;
+    bool partial = false;   // generateRanking = !partial (:99)
+    int32_t hash_channel = -1, expected_positions = 10;
+};
+using TopNRankingOperatorFactory = SimpleOperatorFactory<TopNRankingConfig, class TopNRankingOperator>;   // duplicate(): TopNRankingOperator.java:135-155
 
 // ---- TopNOperator (M/operator/TopNOperator.java:47-62,135-225) ----------------------------------------------------------
 struct TopNConfig {

@@ -817,6 +817,30 @@ class RowNumberOperatorFactory(OperatorFactory):
         super().__init__(h)
 
 
+ROW_NUMBER, RANK, DENSE_RANK = 0, 1, 2   # tgpu_ranking_type = TopNRankingNode.RankingType's ordinal
+
+
+class TopNRankingOperatorFactory(OperatorFactory):
+    """TopNRankingOperator.TopNRankingOperatorFactory (M/operator/TopNRankingOperator.java:42-156): row_number() / rank() OVER (PARTITION BY
+    `partition_channels` ORDER BY `sort_channels`) <= `max_rank_per_partition`.  One output page after finish(): `output_channels`, then
+    -- unless `partial` -- the BIGINT ranking; partitions in the order of their keys' first arrival, rows that compare equal in arrival
+    order.  RANK keeps every tie at the boundary; DENSE_RANK is an invalid argument, as in the reference."""
+
+    def __init__(self, ctx: Context, operator_id, ranking_type, types, output_channels, partition_channels, sort_channels, sort_orders, max_rank_per_partition,
+                 partial=False, hash_channel=-1, expected_positions=10):
+        if len(sort_channels) != len(sort_orders):
+            raise ValueError("sort channels and sort orders differ in length")
+        t, nt = _i32(types)
+        o, no = _i32(output_channels)
+        p, np_ = _i32(partition_channels)
+        sc, ns = _i32(sort_channels)
+        so, _ = _i32(sort_orders)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_top_n_ranking_factory_create(ctx.handle, operator_id, int(ranking_type), nt, t, no, o, np_, p, ns, sc, so, int(max_rank_per_partition),
+                                                                1 if partial else 0, int(hash_channel), int(expected_positions), C.byref(h)))
+        super().__init__(h)
+
+
 class LimitOperatorFactory(OperatorFactory):
     """LimitOperator.LimitOperatorFactory (M/operator/LimitOperator.java:27-60): the first `limit` rows of the stream; whole pages pass
     through, the crossing page is cut."""
