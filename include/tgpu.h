@@ -27,6 +27,7 @@
  *   - tgpu_mark_distinct_* / tgpu_distinct_limit_* <-> M/operator/MarkDistinctOperator.java:37-203, MarkDistinctHash.java:31-87, DistinctLimitOperator.java:40-263
  *   - tgpu_row_number_* / tgpu_limit_* <-> M/operator/RowNumberOperator.java:43-364, LimitOperator.java:25-120
  *   - tgpu_top_n_ranking_*       <-> M/operator/TopNRankingOperator.java:42-310, GroupedTopNRowNumberBuilder.java:99-188, GroupedTopNRankBuilder.java
+ *   - tgpu_window_*              <-> M/operator/WindowOperator.java:205-310,844-855, M/operator/window/WindowPartition.java:184-345, the function classes of M/operator/window
  *   - tgpu_serialize_page / tgpu_deserialize_page <-> M/execution/buffer/PagesSerde.java:64-160, PagesSerdeUtil.java:45-71,
  *                                    S/block/{LongArray,IntArray,ByteArray,VariableWidth,RunLength,Dictionary}BlockEncoding.java, EncoderUtil.java:33-118
  *   - tgpu_exchange_*            <-> M/operator/PartitionedOutputOperator.java:406-476 -> M/operator/ExchangeOperator.java (the hop between
@@ -396,6 +397,63 @@ int32_t tgpu_top_n_ranking_factory_create(tgpu_context *ctx, int32_t operator_id
                                           int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
                                           int64_t max_rank_per_partition, int32_t partial,
                                           int32_t hash_channel /* -1 = none */, int32_t expected_positions, tgpu_operator_factory **out);
+
+/* ---- window functions: f(..) OVER (PARTITION BY k ORDER BY x <frame>) (LocalExecutionPlanner.visitWindow) ---- */
+/* WindowOperator.WindowOperatorFactory (M/operator/WindowOperator.java:205-310; the row loop of M/operator/window/WindowPartition.java:184-214).
+ * The operator consumes pages until finish() (needs_input = not finishing) and then hands out ONE page, none for empty input: the output
+ * channels in the given order, then one channel per window function in the given order.
+ * ROW ORDER.  With at least one partition or sort channel the rows come out in PagesIndex.sort order (sortPagesIndexIfNecessary, :844-855): sort keys
+ * = the partition channels, each ASC_NULLS_LAST, then the sort channels with their sort orders (:254); rows that compare equal on all of them keep
+ * their arrival order across pages (the reference's quicksort leaves it open; OrderBy, TopN and TopNRanking fix it the same way here).  With neither,
+ * nothing is sorted: the input is one partition in arrival order and every row is a peer of every other.  Partition + sort channels: at most 8.
+ * PARTITIONS AND PEERS are maximal runs of ADJACENT rows of that order that are NOT DISTINCT on the partition channels / on the sort channels
+ * (updatePeerGroup, WindowPartition.java:238-247; PagesIndex.positionNotDistinctFromPosition): null = null, NaN = NaN and -0.0 = +0.0, although
+ * the sort puts -0.0 first -- not the comparator's "== 0" that tgpu_top_n_ranking_factory_create uses.  A partition head is also a peer head.
+ * FRAMES (WindowPartition.java:281-345), the three that need no offset; the frame of every one of them starts at the partition's first row:
+ *   TGPU_FRAME_PARTITION          UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING (RANGE or ROWS): ends at the partition's last row (default without ORDER BY)
+ *   TGPU_FRAME_RANGE_TO_CURRENT   RANGE UNBOUNDED PRECEDING .. CURRENT ROW: ends at the last peer of the current row (default with ORDER BY)
+ *   TGPU_FRAME_ROWS_TO_CURRENT    ROWS UNBOUNDED PRECEDING .. CURRENT ROW: ends at the current row
+ * FUNCTIONS (the classes of M/operator/window).  The ranking functions and lag / lead ignore the frame.
+ *   ROW_NUMBER, RANK, DENSE_RANK  BIGINT, never null (RowNumberFunction, RankFunction, DenseRankFunction); no argument
+ *   PERCENT_RANK                  DOUBLE: 0.0 in a partition of one row, else (double) (rank - 1) / (partition rows - 1) (PercentRankFunction.java)
+ *   CUME_DIST                     DOUBLE: (double) (rows up to the current row's last peer) / (partition rows) (CumulativeDistributionFunction.java)
+ *   LAG, LEAD                     1 to 3 argument channels: the value (any type), a BIGINT offset, a default of the value's type (LagFunction.java,
+ *                                 LeadFunction.java).  A null offset gives null; no offset channel means 1; p = current -/+ offset in Java long
+ *                                 arithmetic, in partition-relative positions; lag takes the value at p if 0 <= p <= current, lead if 0 <= p <
+ *                                 partition rows; otherwise the default channel's cell of the CURRENT row, or null.  A negative offset fails
+ *                                 get_output with TGPU_ERR_INVALID_ARGUMENT, "Offset must be at least 0".
+ *   FIRST_VALUE, LAST_VALUE       one value channel of any type: the cell at the frame's first / last row (FirstValueFunction.java, LastValueFunction.java)
+ *   AGGREGATE                     agg_function over the frame (AggregateWindowFunction.java): COUNT_ALL (no argument), COUNT_COLUMN (one channel of any
+ *                                 type), SUM_BIGINT / MIN_BIGINT / MAX_BIGINT (one BIGINT channel), MIN_DOUBLE / MAX_DOUBLE (one DOUBLE channel); values
+ *                                 as tgpu_agg_function documents them.  Counts are never null; sum / min / max are null while the frame holds no
+ *                                 non-null input.  sum(bigint): the reference adds the partition's non-null values left to right with addExact over a
+ *                                 frame that only ever grows, so get_output fails with TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "bigint addition overflow",
+ *                                 exactly when some prefix of a partition's non-null values in sorted order leaves the int64 range.
+ * TGPU_ERR_NOT_SUPPORTED: ignore_nulls != 0; SUM_DOUBLE / AVG_* (the reference accumulates them in a double left to right: a parallel scan cannot
+ * give its bits).  TGPU_ERR_INVALID_ARGUMENT: an unknown function, frame or aggregate, a wrong argument count or type, a default whose type differs
+ * from the value's, a channel or sort order out of range, more than 8 key channels, no function or more than 16, expected_positions <= 0.
+ * preGroupedChannels / preSortedChannelPrefix are not part of the signature.  memory_bytes = the pages index, and once get_output ran
+ * the positions and scan arrays it took. */
+typedef enum tgpu_window_function {
+    TGPU_WINDOW_ROW_NUMBER = 0, TGPU_WINDOW_RANK = 1, TGPU_WINDOW_DENSE_RANK = 2, TGPU_WINDOW_PERCENT_RANK = 3, TGPU_WINDOW_CUME_DIST = 4,
+    TGPU_WINDOW_LAG = 5, TGPU_WINDOW_LEAD = 6, TGPU_WINDOW_FIRST_VALUE = 7, TGPU_WINDOW_LAST_VALUE = 8, TGPU_WINDOW_AGGREGATE = 9
+} tgpu_window_function;
+typedef enum tgpu_window_frame { TGPU_FRAME_PARTITION = 0, TGPU_FRAME_RANGE_TO_CURRENT = 1, TGPU_FRAME_ROWS_TO_CURRENT = 2 } tgpu_window_frame;
+#define TGPU_WINDOW_MAX_FUNCTIONS 16
+typedef struct tgpu_window_function_spec {
+    int32_t function;              /* tgpu_window_function */
+    int32_t agg_function;          /* tgpu_agg_function, read for TGPU_WINDOW_AGGREGATE only */
+    int32_t frame;                 /* tgpu_window_frame */
+    int32_t argument_count;        /* 0 .. 3 */
+    int32_t argument_channels[3];
+    int32_t ignore_nulls;          /* must be 0 */
+} tgpu_window_function_spec;
+int32_t tgpu_window_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                   int32_t output_channel_count, const int32_t *output_channels,
+                                   int32_t function_count, const tgpu_window_function_spec *functions,
+                                   int32_t partition_channel_count, const int32_t *partition_channels,
+                                   int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                   int32_t expected_positions, tgpu_operator_factory **out);
 
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of

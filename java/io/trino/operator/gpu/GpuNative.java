@@ -123,6 +123,8 @@ public final class GpuNative
     public static native long createRowNumberFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] partitionChannels, long maxRowsPerPartition, int hashChannel, int expectedPositions);
     /** TopNRankingOperatorFactory (tgpu_top_n_ranking_factory_create): the output channels + (unless partial) the BIGINT ranking; rankingType / sortOrders are the enums' ordinals, hashChannel -1 = none */
     public static native long createTopNRankingFactory(long context, int operatorId, int rankingType, int[] types, int[] outputChannels, int[] partitionChannels, int[] sortChannels, int[] sortOrders, long maxRankPerPartition, boolean partial, int hashChannel, int expectedPositions);
+    /** WindowOperatorFactory (tgpu_window_factory_create): the output channels + one channel per window function; functions = int[function][8] flattened: {function, aggFunction, frame, argumentCount, argumentChannel0, 1, 2, ignoreNulls} (GpuOperatorFactories.windowFunction); sortOrders are the enum's ordinals */
+    public static native long createWindowFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] functions, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int expectedPositions);
     /** LimitOperatorFactory (tgpu_limit_factory_create): the first limit rows of the stream */
     public static native long createLimitFactory(long context, int operatorId, int[] types, long limit);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);

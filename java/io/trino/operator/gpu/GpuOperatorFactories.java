@@ -427,6 +427,64 @@ public final class GpuOperatorFactories
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuTopNRankingOperator", sourceTypes, poller, factory));
     }
 
+    /** tgpu_window_function / tgpu_window_frame (include/tgpu.h) */
+    public static final int WINDOW_ROW_NUMBER = 0;
+    public static final int WINDOW_RANK = 1;
+    public static final int WINDOW_DENSE_RANK = 2;
+    public static final int WINDOW_PERCENT_RANK = 3;
+    public static final int WINDOW_CUME_DIST = 4;
+    public static final int WINDOW_LAG = 5;
+    public static final int WINDOW_LEAD = 6;
+    public static final int WINDOW_FIRST_VALUE = 7;
+    public static final int WINDOW_LAST_VALUE = 8;
+    public static final int WINDOW_AGGREGATE = 9;
+    public static final int FRAME_PARTITION = 0;
+    public static final int FRAME_RANGE_TO_CURRENT = 1;
+    public static final int FRAME_ROWS_TO_CURRENT = 2;
+
+    /** one window function as the eight ints of tgpu_window_function_spec; aggFunction is read for WINDOW_AGGREGATE only (the codes of aggregateSpecs) */
+    public static int[] windowFunction(int function, int aggFunction, int frame, boolean ignoreNulls, List<Integer> argumentChannels)
+    {
+        if (argumentChannels.size() > 3) {
+            throw new IllegalArgumentException("a window function takes at most 3 argument channels");
+        }
+        int[] spec = new int[8];
+        spec[0] = function;
+        spec[1] = aggFunction;
+        spec[2] = frame;
+        spec[3] = argumentChannels.size();
+        for (int i = 0; i < argumentChannels.size(); i++) {
+            spec[4 + i] = argumentChannels.get(i);
+        }
+        spec[7] = ignoreNulls ? 1 : 0;
+        return spec;
+    }
+
+    /**
+     * WindowOperator.WindowOperatorFactory (operator/WindowOperator.java:70-203; LocalExecutionPlanner.visitWindow): the window functions OVER (PARTITION BY ..
+     * ORDER BY ..).  The output channels, then one channel per function.  functions: one windowFunction(..) per WindowFunctionDefinition; the caller returns
+     * Optional.empty() itself for what include/tgpu.h rules out (frames with offsets, ntile, nth_value, IGNORE NULLS, DOUBLE sums and averages).  A node with
+     * preGroupedChannels / preSortedChannelPrefix is handed over as if it had none: the result differs in the order of the partitions only.
+     */
+    public Optional<OperatorFactory> window(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> outputChannels, List<int[]> functions,
+            List<Integer> partitionChannels, List<Integer> sortChannels, List<SortOrder> sortOrders, int expectedPositions)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        int[] flat = new int[functions.size() * 8];
+        for (int i = 0; i < functions.size(); i++) {
+            System.arraycopy(functions.get(i), 0, flat, i * 8, 8);
+        }
+        long factory = GpuNative.createWindowFactory(context, operatorId, codes, ints(outputChannels), flat, ints(partitionChannels), ints(sortChannels),
+                sortOrders.stream().mapToInt(SortOrder::ordinal).toArray(), expectedPositions);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuWindowOperator", sourceTypes, poller, factory));
+    }
+
     /** LimitOperator.LimitOperatorFactory (operator/LimitOperator.java:34-39; LocalExecutionPlanner.visitLimit) */
     public Optional<OperatorFactory> limit(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, long limit)
     {

@@ -729,6 +729,102 @@ JFN(jlong, createTopNRankingFactory)(JNIEnv *env, jclass c, jlong ctx, jint oper
     return factory_result(env, rc, f);
 }
 
+/* WindowOperatorFactory (operator/WindowOperator.java:70-203): window functions OVER (PARTITION BY .. ORDER BY ..); the output channels + one channel per function.
+ * functions: int[function][8] = {function, aggFunction, frame, argumentCount, argumentChannel0, 1, 2, ignoreNulls} flattened = tgpu_window_function_spec, the way
+ * aggregation specs cross.  Checked in front of the library, as tgpu_window_factory_create does: a non-empty type array, every output / partition / sort / argument
+ * channel in [0, types), partition + sort channels <= 8, as many sort orders in [0, 3] as sort channels, 1 .. 16 functions of 8 ints each, known function / frame /
+ * aggregate codes, argument counts and types per function, expectedPositions > 0; ignoreNulls and sum(double) / avg are NOT_SUPPORTED */
+static const char *window_function_problem(const jint *f, const ints *t, int32_t *code)
+{
+    const jint function = f[0], agg = f[1], frame = f[2], na = f[3];
+    *code = TGPU_ERR_INVALID_ARGUMENT;
+    if (function < TGPU_WINDOW_ROW_NUMBER || function > TGPU_WINDOW_AGGREGATE) return "unknown window function";
+    if (frame < TGPU_FRAME_PARTITION || frame > TGPU_FRAME_ROWS_TO_CURRENT) return "unknown window frame";
+    if (f[7] != 0) {
+        *code = TGPU_ERR_NOT_SUPPORTED;
+        return "IGNORE NULLS is not supported";
+    }
+    if (na < 0 || na > 3) return "a window function takes 0 to 3 arguments";
+    for (jint a = 0; a < na; a++)
+        if (f[4 + a] < 0 || f[4 + a] >= t->n) return "argument channel out of range";
+    switch (function) {
+    case TGPU_WINDOW_LAG:
+    case TGPU_WINDOW_LEAD:
+        if (na < 1) return "lag / lead take 1 to 3 arguments";
+        if (na > 1 && t->p[f[5]] != TGPU_BIGINT) return "the offset of lag / lead must be BIGINT";
+        if (na > 2 && t->p[f[6]] != t->p[f[4]]) return "the default of lag / lead must have the value's type";
+        return NULL;
+    case TGPU_WINDOW_FIRST_VALUE:
+    case TGPU_WINDOW_LAST_VALUE: return na == 1 ? NULL : "first_value / last_value take one argument";
+    case TGPU_WINDOW_AGGREGATE:
+        switch (agg) {
+        case TGPU_AGG_COUNT_ALL: return na == 0 ? NULL : "count(*) takes no argument";
+        case TGPU_AGG_COUNT_COLUMN: return na == 1 ? NULL : "count(x) takes one argument";
+        case TGPU_AGG_SUM_BIGINT:
+        case TGPU_AGG_MIN_BIGINT:
+        case TGPU_AGG_MAX_BIGINT: return na == 1 && t->p[f[4]] == TGPU_BIGINT ? NULL : "the aggregate takes one BIGINT argument";
+        case TGPU_AGG_MIN_DOUBLE:
+        case TGPU_AGG_MAX_DOUBLE: return na == 1 && t->p[f[4]] == TGPU_DOUBLE ? NULL : "the aggregate takes one DOUBLE argument";
+        case TGPU_AGG_SUM_DOUBLE:
+        case TGPU_AGG_AVG_BIGINT:
+        case TGPU_AGG_AVG_DOUBLE: *code = TGPU_ERR_NOT_SUPPORTED; return "sum(double) and avg are not supported as window aggregates";
+        default: return "unknown aggregate function";
+        }
+    default: return na == 0 ? NULL : "the ranking functions take no argument";
+    }
+}
+
+JFN(jlong, createWindowFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray functions,
+                                jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders, jint expectedPositions)
+{
+    UNUSED(c);
+    _Static_assert(sizeof(tgpu_window_function_spec) == 8 * sizeof(jint), "the flattened function array is read as tgpu_window_function_spec");
+    ints t = ints_get(env, types), oc = ints_get(env, outputChannels), fn = ints_get(env, functions), pc = ints_get(env, partitionChannels),
+         sc = ints_get(env, sortChannels), so = ints_get(env, sortOrders);
+    const char *bad = NULL;
+    int32_t code = TGPU_ERR_INVALID_ARGUMENT;
+    if (t.n <= 0) bad = "empty type array";
+    for (jsize i = 0; !bad && i < t.n; i++)
+        if (t.p[i] < TGPU_BIGINT || t.p[i] > TGPU_VARCHAR) bad = "unknown type";
+    for (jsize i = 0; !bad && i < oc.n; i++)
+        if (oc.p[i] < 0 || oc.p[i] >= t.n) bad = "output channel out of range";
+    if (!bad && sc.n != so.n) bad = "sort channels and sort orders differ in length";
+    if (!bad && pc.n + sc.n > 8) bad = "more than 8 partition and sort channels";
+    for (jsize i = 0; !bad && i < pc.n; i++)
+        if (pc.p[i] < 0 || pc.p[i] >= t.n) bad = "partition channel out of range";
+    for (jsize i = 0; !bad && i < sc.n; i++) {
+        if (sc.p[i] < 0 || sc.p[i] >= t.n) bad = "sort channel out of range";
+        else if (so.p[i] < TGPU_SORT_ASC_NULLS_FIRST || so.p[i] > TGPU_SORT_DESC_NULLS_LAST) bad = "sort order out of range";
+    }
+    if (!bad && fn.n % 8 != 0) bad = "malformed function array";
+    if (!bad && fn.n == 0) bad = "no window function";
+    if (!bad && fn.n / 8 > TGPU_WINDOW_MAX_FUNCTIONS) bad = "more than 16 window functions";
+    for (jsize i = 0; !bad && i < fn.n; i += 8) bad = window_function_problem(fn.p + i, &t, &code);
+    if (!bad && expectedPositions <= 0) {
+        code = TGPU_ERR_INVALID_ARGUMENT;
+        bad = "expected positions must be positive";
+    }
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad)
+        rc = tgpu_window_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, oc.n, (const int32_t *)oc.p, fn.n / 8,
+                                        (const tgpu_window_function_spec *)fn.p, pc.n, (const int32_t *)pc.p, sc.n, (const int32_t *)sc.p, (const int32_t *)so.p,
+                                        expectedPositions, &f);
+    ints_release(env, &so);
+    ints_release(env, &sc);
+    ints_release(env, &pc);
+    ints_release(env, &fn);
+    ints_release(env, &oc);
+    ints_release(env, &t);
+    if (bad) {
+        char message[128];
+        snprintf(message, sizeof(message), "window: %s", bad);
+        throw_native_message(env, code, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
+
 /* LimitOperatorFactory (operator/LimitOperator.java:26-60): the first `limit` rows of the stream */
 JFN(jlong, createLimitFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong limit)
 {

@@ -87,6 +87,11 @@ class AggSpec(C.Structure):
     _fields_ = [("function", C.c_int32), ("input_channel", C.c_int32), ("mask_channel", C.c_int32)]
 
 
+class WindowFunctionSpec(C.Structure):
+    _fields_ = [("function", C.c_int32), ("agg_function", C.c_int32), ("frame", C.c_int32), ("argument_count", C.c_int32), ("argument_channels", C.c_int32 * 3),
+                ("ignore_nulls", C.c_int32)]
+
+
 _lib = None
 
 # every symbol include/tgpu.h declares: (restype, argtypes)
@@ -180,6 +185,7 @@ SYMBOLS = {
     "tgpu_mark_distinct_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(vp)]),
     "tgpu_distinct_limit_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i64, i32, P(vp)]),
     "tgpu_top_n_ranking_factory_create": (i32, [vp, i32, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, P(i32), P(i32), i64, i32, i32, i32, P(vp)]),
+    "tgpu_window_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(WindowFunctionSpec), i32, P(i32), i32, P(i32), P(i32), i32, P(vp)]),
     "tgpu_row_number_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), i64, i32, i32, P(vp)]),
     "tgpu_limit_factory_create": (i32, [vp, i32, i32, P(i32), i64, P(vp)]),
     "tgpu_merge_pages_factory_create": (i32, [vp, i32, i32, P(i32), i64, i32, i64, P(vp)]),

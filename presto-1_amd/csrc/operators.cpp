@@ -2527,6 +2527,73 @@ static void validate(Context *, const TopNRankingConfig &cfg)
 }
 
 // =====================================================================================================================
+// WindowOperator (M/operator/WindowOperator.java:205-310): f(..) OVER (PARTITION BY k ORDER BY x <frame>).  Consumes pages into a PagesIndex
+// until finish(), then hands out ONE page (as OrderByOperator does here): the output channels in sorted order, then one channel per window
+// function.  The work is WindowGpu's (window.hip): the sort of OrderByOperator, then heads, one fused segmented scan and one launch per
+// function.
+// =====================================================================================================================
+class WindowOperator : public Operator {
+public:
+    WindowOperator(Context *ctx, int32_t id, const WindowConfig &cfg)
+        : Operator(ctx, id), cfg_(cfg), index_(ctx, cfg.types), window_(ctx, cfg.types, cfg.functions, cfg.partition_channels, cfg.sort_channels, cfg.sort_orders)
+    {
+        // TGPU_WINDOW_TILE_ROWS=<rows>, a multiple of 256, read here (as TGPU_TOP_N_RANKING_SLICE_ROWS is): the rows one workgroup of the scan
+        // owns, so that the tests reach the multi-tile paths with small inputs
+        const char *e = getenv("TGPU_WINDOW_TILE_ROWS");
+        if (e != nullptr && *e) {
+            const int64_t rows = strtoll(e, nullptr, 10);
+            TG_CHECK_ARG(rows > 0 && rows % WindowGpu::kBlock == 0, "TGPU_WINDOW_TILE_ROWS must be a positive multiple of 256");
+            window_.set_tile_rows(rows);
+        }
+    }
+
+    bool needs_input() override { return !finishing_; }
+
+    void add_input(const tgpu_page *page) override
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        DevicePage in = ingest_page(ctx_, page);
+        check_page_types(in, cfg_.types);
+        index_.add_page(in);
+    }
+
+    std::unique_ptr<OutputPage> get_output() override
+    {
+        if (!finishing_ || finished_) return nullptr;
+        finished_ = true;
+        DevicePage all;
+        all.n = index_.position_count();
+        if (all.n == 0) return nullptr;
+        for (size_t i = 0; i < cfg_.types.size(); i++) all.cols.push_back(index_.column((int)i));
+        BufferPtr pos;
+        std::vector<DeviceColumn> functions = window_.evaluate(all, &pos);
+        DevicePage out;
+        out.n = all.n;
+        for (int32_t ch : cfg_.output_channels)
+            out.cols.push_back(pos ? k::gather_column(ctx_, all.cols[(size_t)ch], pos->as<int32_t>(), all.n, false) : all.cols[(size_t)ch]);
+        for (DeviceColumn &c : functions) out.cols.push_back(std::move(c));
+        return wrap(std::move(out));
+    }
+
+    void finish() override { finishing_ = true; }
+    bool is_finished() override { return finished_ || (finishing_ && index_.position_count() == 0); }
+    int64_t memory_bytes() override { return index_.estimated_size() + window_.scratch_bytes(); }   // index + what get_output took: positions + scan arrays
+
+private:
+    WindowConfig cfg_;
+    PagesIndexGpu index_;
+    WindowGpu window_;
+    bool finishing_ = false, finished_ = false;
+};
+
+static void validate(Context *, const WindowConfig &cfg)
+{
+    WindowGpu::validate(cfg.types, cfg.functions, cfg.partition_channels, cfg.sort_channels, cfg.sort_orders);
+    for (int32_t ch : cfg.output_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)cfg.types.size(), "output channel out of range");
+    TG_CHECK_ARG(cfg.expected_positions > 0, "expected positions must be positive");   // WindowOperator.java:120
+}
+
+// =====================================================================================================================
 // LimitOperator (M/operator/LimitOperator.java:62-119): whole pages pass through while they fit, the crossing page is a region of its
 // first `remaining` rows, finish() zeroes the remainder.  No kernel.
 // =====================================================================================================================
@@ -2870,6 +2937,7 @@ template class SimpleOperatorFactory<DistinctLimitConfig, DistinctLimitOperator>
 template class SimpleOperatorFactory<RowNumberConfig, RowNumberOperator>;
 template class SimpleOperatorFactory<LimitConfig, LimitOperator>;
 template class SimpleOperatorFactory<TopNRankingConfig, TopNRankingOperator>;
+template class SimpleOperatorFactory<WindowConfig, WindowOperator>;
 template class SimpleOperatorFactory<MergePagesConfig, MergePagesOperator>;
 template class SimpleOperatorFactory<PartitionedOutputConfig, PartitionedOutputOperator>;
 

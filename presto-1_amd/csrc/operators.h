@@ -15,6 +15,7 @@
 #include "semijoin.h"
 #include "topn.h"
 #include "topn_ranking.h"
+#include "window.h"
 
 namespace tgpu {
 
@@ -417,6 +418,15 @@ struct TopNRankingConfig {
     int32_t hash_channel = -1, expected_positions = 10;
 };
 using TopNRankingOperatorFactory = SimpleOperatorFactory<TopNRankingConfig, class TopNRankingOperator>;   // duplicate(): TopNRankingOperator.java:135-155
+
+// ---- WindowOperator (M/operator/WindowOperator.java:205-310) ------------------------------------------------------------------------------
+struct WindowConfig {
+    std::vector<int32_t> types, output_channels;
+    std::vector<WindowFunctionSpec> functions;
+    std::vector<int32_t> partition_channels, sort_channels, sort_orders;
+    int32_t expected_positions = 10;
+};
+using WindowOperatorFactory = SimpleOperatorFactory<WindowConfig, class WindowOperator>;   // duplicate(): WindowOperator.java:170
 
 // ---- TopNOperator (M/operator/TopNOperator.java:47-62,135-225) ----------------------------------------------------------
 struct TopNConfig {

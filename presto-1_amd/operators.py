@@ -841,6 +841,51 @@ class TopNRankingOperatorFactory(OperatorFactory):
         super().__init__(h)
 
 
+# tgpu_window_function / tgpu_window_frame
+WINDOW_ROW_NUMBER, WINDOW_RANK, WINDOW_DENSE_RANK, WINDOW_PERCENT_RANK, WINDOW_CUME_DIST = 0, 1, 2, 3, 4
+WINDOW_LAG, WINDOW_LEAD, WINDOW_FIRST_VALUE, WINDOW_LAST_VALUE, WINDOW_AGGREGATE = 5, 6, 7, 8, 9
+FRAME_PARTITION, FRAME_RANGE_TO_CURRENT, FRAME_ROWS_TO_CURRENT = 0, 1, 2
+
+
+class WindowFunction:
+    """One window function of a WindowOperatorFactory (tgpu_window_function_spec): `function` = a WINDOW_* code, `argument_channels` = its 0 to 3
+    source channels (lag / lead: value, offset, default), `frame` = a FRAME_* code (read by the aggregates and first / last value),
+    `agg_function` = the aggregate of WINDOW_AGGREGATE (COUNT_ALL, COUNT_COLUMN, SUM_BIGINT, MIN_* / MAX_*)."""
+
+    def __init__(self, function, argument_channels=(), frame=FRAME_RANGE_TO_CURRENT, agg_function=0, ignore_nulls=False):
+        self.function, self.argument_channels, self.frame = int(function), tuple(int(c) for c in argument_channels), int(frame)
+        self.agg_function, self.ignore_nulls = int(agg_function), bool(ignore_nulls)
+
+    def spec(self):
+        if len(self.argument_channels) > 3:
+            raise ValueError("a window function takes at most 3 argument channels")
+        channels = self.argument_channels + (0,) * (3 - len(self.argument_channels))
+        return _lib.WindowFunctionSpec(self.function, self.agg_function, self.frame, len(self.argument_channels), (C.c_int32 * 3)(*channels),
+                                       1 if self.ignore_nulls else 0)
+
+
+class WindowOperatorFactory(OperatorFactory):
+    """WindowOperator.WindowOperatorFactory (M/operator/WindowOperator.java:71-203): `functions` OVER (PARTITION BY `partition_channels` ORDER BY
+    `sort_channels`).  One output page after finish(): `output_channels`, then one channel per function; rows in the order of the partition
+    channels (ASC_NULLS_LAST) and the sort channels, rows that compare equal in arrival order; without either, arrival order and one partition
+    of peers.  Partitions and peers are decided by IS NOT DISTINCT FROM."""
+
+    def __init__(self, ctx: Context, operator_id, types, output_channels, functions, partition_channels, sort_channels, sort_orders, expected_positions=10):
+        if len(sort_channels) != len(sort_orders):
+            raise ValueError("sort channels and sort orders differ in length")
+        functions = list(functions)
+        t, nt = _i32(types)
+        o, no = _i32(output_channels)
+        p, np_ = _i32(partition_channels)
+        sc, ns = _i32(sort_channels)
+        so, _ = _i32(sort_orders)
+        specs = (_lib.WindowFunctionSpec * max(1, len(functions)))(*[f.spec() for f in functions])
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_window_factory_create(ctx.handle, operator_id, nt, t, no, o, len(functions), specs, np_, p, ns, sc, so, int(expected_positions),
+                                                         C.byref(h)))
+        super().__init__(h)
+
+
 class LimitOperatorFactory(OperatorFactory):
     """LimitOperator.LimitOperatorFactory (M/operator/LimitOperator.java:27-60): the first `limit` rows of the stream; whole pages pass
     through, the crossing page is cut."""
