@@ -409,7 +409,7 @@ int32_t tgpu_top_n_ranking_factory_create(tgpu_context *ctx, int32_t operator_id
  * PARTITIONS AND PEERS are maximal runs of ADJACENT rows of that order that are NOT DISTINCT on the partition channels / on the sort channels
  * (updatePeerGroup, WindowPartition.java:238-247; PagesIndex.positionNotDistinctFromPosition): null = null, NaN = NaN and -0.0 = +0.0, although
  * the sort puts -0.0 first -- not the comparator's "== 0" that tgpu_top_n_ranking_factory_create uses.  A partition head is also a peer head.
- * FRAMES (WindowPartition.java:281-345), the three that need no offset; the frame of every one of them starts at the partition's first row:
+ * FRAMES (WindowPartition.java:281-345), the three that need no offset (frames with offsets: tgpu_window_factory_create_framed below); the frame of every one of them starts at the partition's first row:
  *   TGPU_FRAME_PARTITION          UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING (RANGE or ROWS): ends at the partition's last row (default without ORDER BY)
  *   TGPU_FRAME_RANGE_TO_CURRENT   RANGE UNBOUNDED PRECEDING .. CURRENT ROW: ends at the last peer of the current row (default with ORDER BY)
  *   TGPU_FRAME_ROWS_TO_CURRENT    ROWS UNBOUNDED PRECEDING .. CURRENT ROW: ends at the current row
@@ -436,7 +436,8 @@ int32_t tgpu_top_n_ranking_factory_create(tgpu_context *ctx, int32_t operator_id
  * the positions and scan arrays it took. */
 typedef enum tgpu_window_function {
     TGPU_WINDOW_ROW_NUMBER = 0, TGPU_WINDOW_RANK = 1, TGPU_WINDOW_DENSE_RANK = 2, TGPU_WINDOW_PERCENT_RANK = 3, TGPU_WINDOW_CUME_DIST = 4,
-    TGPU_WINDOW_LAG = 5, TGPU_WINDOW_LEAD = 6, TGPU_WINDOW_FIRST_VALUE = 7, TGPU_WINDOW_LAST_VALUE = 8, TGPU_WINDOW_AGGREGATE = 9
+    TGPU_WINDOW_LAG = 5, TGPU_WINDOW_LEAD = 6, TGPU_WINDOW_FIRST_VALUE = 7, TGPU_WINDOW_LAST_VALUE = 8, TGPU_WINDOW_AGGREGATE = 9,
+    TGPU_WINDOW_NTH_VALUE = 10, TGPU_WINDOW_NTILE = 11   /* tgpu_window_factory_create_framed only */
 } tgpu_window_function;
 typedef enum tgpu_window_frame { TGPU_FRAME_PARTITION = 0, TGPU_FRAME_RANGE_TO_CURRENT = 1, TGPU_FRAME_ROWS_TO_CURRENT = 2 } tgpu_window_frame;
 #define TGPU_WINDOW_MAX_FUNCTIONS 16
@@ -454,6 +455,53 @@ int32_t tgpu_window_factory_create(tgpu_context *ctx, int32_t operator_id, int32
                                    int32_t partition_channel_count, const int32_t *partition_channels,
                                    int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
                                    int32_t expected_positions, tgpu_operator_factory **out);
+
+/* The same operator with the frames of M/operator/window/FrameInfo.java: ROWS / GROUPS with k PRECEDING / k FOLLOWING bounds, and the functions
+ * nth_value and ntile.  The arguments are those of tgpu_window_factory_create plus frames[function_count] behind `functions`; the `frame` field
+ * of a function spec is NOT read, frames[f] is function f's frame.  tgpu_window_factory_create is this entry point with TGPU_FRAME_PARTITION =
+ * RANGE UNBOUNDED_PRECEDING .. UNBOUNDED_FOLLOWING, TGPU_FRAME_RANGE_TO_CURRENT = RANGE UNBOUNDED_PRECEDING .. CURRENT_ROW, TGPU_FRAME_ROWS_TO_CURRENT =
+ * ROWS UNBOUNDED_PRECEDING .. CURRENT_ROW, and those three frames given here take the same path and give the same page, errors included.
+ * BOUNDS.  start is UNBOUNDED_PRECEDING, PRECEDING, CURRENT_ROW or FOLLOWING; end is PRECEDING, CURRENT_ROW, FOLLOWING or UNBOUNDED_FOLLOWING; a CURRENT_ROW
+ * start does not end PRECEDING, a FOLLOWING start ends FOLLOWING or UNBOUNDED_FOLLOWING (the analyzer's rules); anything else is
+ * TGPU_ERR_INVALID_ARGUMENT.  start_channel / end_channel are read for a PRECEDING / FOLLOWING bound only: a BIGINT or INTEGER source channel whose cell
+ * in the CURRENT row is the offset (getFrameValue, WindowPartition.java:591-607).  A null offset in any row fails get_output with
+ * TGPU_ERR_INVALID_ARGUMENT, "Window frame starting offset must not be null" / "Window frame ending offset must not be null", a negative one with
+ * "Window frame offset must not be negative" (the value is left out of the message), before any other error of the page.
+ * FRAMES, with r = the row's position in its partition, E = the partition's last position, G = the row's peer group in its partition, L = the last:
+ *   ROWS    WindowPartition.java:281-323.  a PRECEDING = max(r - a, 0), a FOLLOWING = min(r + a, E), for every int64 a >= 0.  Empty (:541-573) for
+ *           UNBOUNDED_PRECEDING .. b PRECEDING with b > r; a FOLLOWING .. UNBOUNDED_FOLLOWING with a > E - r; both PRECEDING with a < b, or a > r and
+ *           b > r; both FOLLOWING with a > b or a > E - r.
+ *   GROUPS  :609-694.  start: the first row of group G - a (the partition's first row below group 0) / of group G + a (behind the partition above
+ *           L) / of G; end: the last row of group G - b (-1 below group 0) / of G + b (E above L) / of G.  Empty when start > end, start > E or
+ *           end < 0.  An offset of 2^31 or more is "beyond every group" (the reference's toIntExact throws there).
+ *   RANGE   by peers only (:327-344): the four combinations of UNBOUNDED_PRECEDING / CURRENT_ROW with CURRENT_ROW / UNBOUNDED_FOLLOWING.  RANGE with a
+ *           PRECEDING / FOLLOWING bound is TGPU_ERR_NOT_SUPPORTED: it needs the planner's computed comparison channels and a value search.
+ * FUNCTIONS under a frame [s, e].  The ranking functions, lag, lead and ntile ignore it.
+ *   FIRST_VALUE, LAST_VALUE   the cell at s / at e; null for an empty frame
+ *   NTH_VALUE                 two channels, the value (any type) and a BIGINT offset (NthValueFunction.java:41-77): null for an empty frame or a null
+ *                             offset, else the cell at s + offset - 1 if that is <= e, else null; an offset < 1 in a row with a frame fails get_output
+ *                             with TGPU_ERR_INVALID_ARGUMENT, "Offset must be at least 1"
+ *   NTILE                     one BIGINT channel, the buckets (NTileFunction.java:45-74): BIGINT; null for null buckets; buckets <= 0 fail with
+ *                             TGPU_ERR_INVALID_ARGUMENT, "Buckets must be greater than 0"; else the bucket number from 1, the partition's remainder
+ *                             rows going to the first buckets one each; more buckets than rows: the row's position + 1
+ *   AGGREGATE                 the seven aggregates of tgpu_window_factory_create.  Counts over an empty frame are 0; sum / min / max are null over an
+ *                             empty frame or one without a non-null input.  sum(bigint) is the exact sum of the frame; get_output fails with
+ *                             TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "bigint addition overflow", exactly when some row's frame sum leaves int64 (a
+ *                             partition prefix may).  The reference slides one accumulator from frame to frame with addExact / subtractExact and can
+ *                             also throw on an intermediate that depends on the path between two frames: not reproduced.
+ * TGPU_ERR_NOT_SUPPORTED as before: ignore_nulls != 0 (nth_value too), SUM_DOUBLE / AVG_*.  memory_bytes also counts the frame arrays and the
+ * range-extreme index of min / max. */
+typedef enum tgpu_frame_type { TGPU_FRAME_TYPE_RANGE = 0, TGPU_FRAME_TYPE_ROWS = 1, TGPU_FRAME_TYPE_GROUPS = 2 } tgpu_frame_type;   /* sql/tree/WindowFrame.Type ordinals */
+typedef enum tgpu_frame_bound {
+    TGPU_BOUND_UNBOUNDED_PRECEDING = 0, TGPU_BOUND_PRECEDING = 1, TGPU_BOUND_CURRENT_ROW = 2, TGPU_BOUND_FOLLOWING = 3, TGPU_BOUND_UNBOUNDED_FOLLOWING = 4
+} tgpu_frame_bound;                                                                                                                  /* sql/tree/FrameBound.Type ordinals */
+typedef struct tgpu_window_frame_spec { int32_t type, start_type, start_channel, end_type, end_channel; } tgpu_window_frame_spec;   /* M/operator/window/FrameInfo.java */
+int32_t tgpu_window_factory_create_framed(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                          int32_t output_channel_count, const int32_t *output_channels,
+                                          int32_t function_count, const tgpu_window_function_spec *functions, const tgpu_window_frame_spec *frames,
+                                          int32_t partition_channel_count, const int32_t *partition_channels,
+                                          int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                          int32_t expected_positions, tgpu_operator_factory **out);
 
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of

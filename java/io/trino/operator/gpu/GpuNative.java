@@ -125,6 +125,9 @@ public final class GpuNative
     public static native long createTopNRankingFactory(long context, int operatorId, int rankingType, int[] types, int[] outputChannels, int[] partitionChannels, int[] sortChannels, int[] sortOrders, long maxRankPerPartition, boolean partial, int hashChannel, int expectedPositions);
     /** WindowOperatorFactory (tgpu_window_factory_create): the output channels + one channel per window function; functions = int[function][8] flattened: {function, aggFunction, frame, argumentCount, argumentChannel0, 1, 2, ignoreNulls} (GpuOperatorFactories.windowFunction); sortOrders are the enum's ordinals */
     public static native long createWindowFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] functions, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int expectedPositions);
+
+    /** WindowOperatorFactory with FrameInfo frames (tgpu_window_factory_create_framed): createWindowFactory plus frames = int[function][5] flattened: {type, startType, startChannel, endType, endChannel} (GpuOperatorFactories.windowFrame); the frame field of a function is not read; nth_value and ntile exist here only */
+    public static native long createFramedWindowFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] functions, int[] frames, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int expectedPositions);
     /** LimitOperatorFactory (tgpu_limit_factory_create): the first limit rows of the stream */
     public static native long createLimitFactory(long context, int operatorId, int[] types, long limit);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);

@@ -5,6 +5,7 @@ import io.trino.metadata.Split;
 import io.trino.operator.LookupJoinOperators.JoinType;
 import io.trino.operator.OperatorFactory;
 import io.trino.operator.SourceOperatorFactory;
+import io.trino.operator.window.FrameInfo;
 import io.trino.spi.connector.ConnectorPageSource;
 import io.trino.spi.connector.SortOrder;
 import io.trino.spi.type.Type;
@@ -441,6 +442,17 @@ public final class GpuOperatorFactories
     public static final int FRAME_PARTITION = 0;
     public static final int FRAME_RANGE_TO_CURRENT = 1;
     public static final int FRAME_ROWS_TO_CURRENT = 2;
+    /** framedWindow(..) only: two more functions, tgpu_frame_type = WindowFrame.Type's ordinal, tgpu_frame_bound = FrameBound.Type's ordinal */
+    public static final int WINDOW_NTH_VALUE = 10;
+    public static final int WINDOW_NTILE = 11;
+    public static final int FRAME_TYPE_RANGE = 0;
+    public static final int FRAME_TYPE_ROWS = 1;
+    public static final int FRAME_TYPE_GROUPS = 2;
+    public static final int BOUND_UNBOUNDED_PRECEDING = 0;
+    public static final int BOUND_PRECEDING = 1;
+    public static final int BOUND_CURRENT_ROW = 2;
+    public static final int BOUND_FOLLOWING = 3;
+    public static final int BOUND_UNBOUNDED_FOLLOWING = 4;
 
     /** one window function as the eight ints of tgpu_window_function_spec; aggFunction is read for WINDOW_AGGREGATE only (the codes of aggregateSpecs) */
     public static int[] windowFunction(int function, int aggFunction, int frame, boolean ignoreNulls, List<Integer> argumentChannels)
@@ -463,7 +475,7 @@ public final class GpuOperatorFactories
     /**
      * WindowOperator.WindowOperatorFactory (operator/WindowOperator.java:70-203; LocalExecutionPlanner.visitWindow): the window functions OVER (PARTITION BY ..
      * ORDER BY ..).  The output channels, then one channel per function.  functions: one windowFunction(..) per WindowFunctionDefinition; the caller returns
-     * Optional.empty() itself for what include/tgpu.h rules out (frames with offsets, ntile, nth_value, IGNORE NULLS, DOUBLE sums and averages).  A node with
+     * Optional.empty() itself for what include/tgpu.h rules out (IGNORE NULLS, DOUBLE sums and averages), and calls framedWindow(..) for frames with offsets, ntile and nth_value.  A node with
      * preGroupedChannels / preSortedChannelPrefix is handed over as if it had none: the result differs in the order of the partitions only.
      */
     public Optional<OperatorFactory> window(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> outputChannels, List<int[]> functions,
@@ -481,6 +493,51 @@ public final class GpuOperatorFactories
             System.arraycopy(functions.get(i), 0, flat, i * 8, 8);
         }
         long factory = GpuNative.createWindowFactory(context, operatorId, codes, ints(outputChannels), flat, ints(partitionChannels), ints(sortChannels),
+                sortOrders.stream().mapToInt(SortOrder::ordinal).toArray(), expectedPositions);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuWindowOperator", sourceTypes, poller, factory));
+    }
+
+    /** one frame as the five ints of tgpu_window_frame_spec, from the fields of a FrameInfo (operator/window/FrameInfo.java); the channels are read for PRECEDING / FOLLOWING bounds only */
+    public static int[] windowFrame(FrameInfo frame)
+    {
+        return new int[] {frame.getType().ordinal(), frame.getStartType().ordinal(), frame.getStartChannel(), frame.getEndType().ordinal(), frame.getEndChannel()};
+    }
+
+    private static boolean hasOffset(int bound)
+    {
+        return bound == BOUND_PRECEDING || bound == BOUND_FOLLOWING;
+    }
+
+    /**
+     * window(..) with the frames of FrameInfo: ROWS / GROUPS frames with k PRECEDING / k FOLLOWING bounds, RANGE frames by peers, and the functions nth_value and
+     * ntile.  functions: one windowFunction(..) per WindowFunctionDefinition (its frame int is not read); frames: one windowFrame(..) per function.
+     * Optional.empty() for what the library refuses: a type without a code, and RANGE with a PRECEDING / FOLLOWING bound; the caller returns it itself for
+     * IGNORE NULLS and DOUBLE sums and averages, as for window(..).
+     */
+    public Optional<OperatorFactory> framedWindow(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> outputChannels, List<int[]> functions,
+            List<int[]> frames, List<Integer> partitionChannels, List<Integer> sortChannels, List<SortOrder> sortOrders, int expectedPositions)
+    {
+        if (frames.size() != functions.size()) {
+            throw new IllegalArgumentException("one frame per window function");
+        }
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        int[] flat = new int[functions.size() * 8];
+        int[] flatFrames = new int[frames.size() * 5];
+        for (int i = 0; i < functions.size(); i++) {
+            System.arraycopy(functions.get(i), 0, flat, i * 8, 8);
+            int[] frame = frames.get(i);
+            if (frame[0] == FRAME_TYPE_RANGE && (hasOffset(frame[1]) || hasOffset(frame[3]))) {
+                return Optional.empty();
+            }
+            System.arraycopy(frame, 0, flatFrames, i * 5, 5);
+        }
+        long factory = GpuNative.createFramedWindowFactory(context, operatorId, codes, ints(outputChannels), flat, flatFrames, ints(partitionChannels), ints(sortChannels),
                 sortOrders.stream().mapToInt(SortOrder::ordinal).toArray(), expectedPositions);
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuWindowOperator", sourceTypes, poller, factory));
     }

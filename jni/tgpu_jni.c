@@ -734,12 +734,13 @@ JFN(jlong, createTopNRankingFactory)(JNIEnv *env, jclass c, jlong ctx, jint oper
  * aggregation specs cross.  Checked in front of the library, as tgpu_window_factory_create does: a non-empty type array, every output / partition / sort / argument
  * channel in [0, types), partition + sort channels <= 8, as many sort orders in [0, 3] as sort channels, 1 .. 16 functions of 8 ints each, known function / frame /
  * aggregate codes, argument counts and types per function, expectedPositions > 0; ignoreNulls and sum(double) / avg are NOT_SUPPORTED */
-static const char *window_function_problem(const jint *f, const ints *t, int32_t *code)
+static const char *window_function_problem_of(const jint *f, const ints *t, int32_t *code, int framed)
 {
     const jint function = f[0], agg = f[1], frame = f[2], na = f[3];
     *code = TGPU_ERR_INVALID_ARGUMENT;
-    if (function < TGPU_WINDOW_ROW_NUMBER || function > TGPU_WINDOW_AGGREGATE) return "unknown window function";
-    if (frame < TGPU_FRAME_PARTITION || frame > TGPU_FRAME_ROWS_TO_CURRENT) return "unknown window frame";
+    /* framed: the frame field is not read (the frame array is checked by window_frame_problem), and nth_value / ntile exist */
+    if (function < TGPU_WINDOW_ROW_NUMBER || function > (framed ? TGPU_WINDOW_NTILE : TGPU_WINDOW_AGGREGATE)) return "unknown window function";
+    if (!framed && (frame < TGPU_FRAME_PARTITION || frame > TGPU_FRAME_ROWS_TO_CURRENT)) return "unknown window frame";
     if (f[7] != 0) {
         *code = TGPU_ERR_NOT_SUPPORTED;
         return "IGNORE NULLS is not supported";
@@ -756,6 +757,8 @@ static const char *window_function_problem(const jint *f, const ints *t, int32_t
         return NULL;
     case TGPU_WINDOW_FIRST_VALUE:
     case TGPU_WINDOW_LAST_VALUE: return na == 1 ? NULL : "first_value / last_value take one argument";
+    case TGPU_WINDOW_NTH_VALUE: return na == 2 && t->p[f[5]] == TGPU_BIGINT ? NULL : "nth_value takes a value and a BIGINT offset";
+    case TGPU_WINDOW_NTILE: return na == 1 && t->p[f[4]] == TGPU_BIGINT ? NULL : "ntile takes one BIGINT argument";
     case TGPU_WINDOW_AGGREGATE:
         switch (agg) {
         case TGPU_AGG_COUNT_ALL: return na == 0 ? NULL : "count(*) takes no argument";
@@ -772,6 +775,95 @@ static const char *window_function_problem(const jint *f, const ints *t, int32_t
         }
     default: return na == 0 ? NULL : "the ranking functions take no argument";
     }
+}
+
+static const char *window_function_problem(const jint *f, const ints *t, int32_t *code) { return window_function_problem_of(f, t, code, 0); }
+
+/* one frame of createFramedWindowFactory: {type, startType, startChannel, endType, endChannel} = tgpu_window_frame_spec */
+static const char *window_frame_problem(const jint *w, const ints *t, int32_t *code)
+{
+    const jint type = w[0], start = w[1], end = w[3];
+    *code = TGPU_ERR_INVALID_ARGUMENT;
+    if (type < TGPU_FRAME_TYPE_RANGE || type > TGPU_FRAME_TYPE_GROUPS) return "unknown window frame type";
+    if (start < TGPU_BOUND_UNBOUNDED_PRECEDING || start > TGPU_BOUND_UNBOUNDED_FOLLOWING) return "unknown window frame bound";
+    if (end < TGPU_BOUND_UNBOUNDED_PRECEDING || end > TGPU_BOUND_UNBOUNDED_FOLLOWING) return "unknown window frame bound";
+    if (start == TGPU_BOUND_UNBOUNDED_FOLLOWING || end == TGPU_BOUND_UNBOUNDED_PRECEDING || (start == TGPU_BOUND_CURRENT_ROW && end == TGPU_BOUND_PRECEDING) ||
+        (start == TGPU_BOUND_FOLLOWING && end != TGPU_BOUND_FOLLOWING && end != TGPU_BOUND_UNBOUNDED_FOLLOWING))
+        return "invalid window frame bounds";
+    int offsets = 0;
+    for (int side = 0; side < 2; side++) {
+        const jint bound = side == 0 ? start : end, channel = side == 0 ? w[2] : w[4];
+        if (bound != TGPU_BOUND_PRECEDING && bound != TGPU_BOUND_FOLLOWING) continue;
+        offsets++;
+        if (channel < 0 || channel >= t->n) return "frame offset channel out of range";
+        if (t->p[channel] != TGPU_BIGINT && t->p[channel] != TGPU_INTEGER) return "a frame offset must be BIGINT or INTEGER";
+    }
+    if (type == TGPU_FRAME_TYPE_RANGE && offsets > 0) {
+        *code = TGPU_ERR_NOT_SUPPORTED;
+        return "RANGE frames with an offset are not supported";
+    }
+    return NULL;
+}
+
+/* WindowOperatorFactory with FrameInfo frames (tgpu_window_factory_create_framed): createWindowFactory's arguments plus frames = int[function][5] flattened behind
+ * `functions`; the frame field of a function is not read.  The same checks in front of the library, plus: 5 ints per frame, as many frames as functions, known frame
+ * types and bounds, the analyzer's bound combinations, offset channels in range and BIGINT / INTEGER; RANGE with an offset is NOT_SUPPORTED */
+JFN(jlong, createFramedWindowFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray functions, jintArray frames,
+                                      jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders, jint expectedPositions)
+{
+    UNUSED(c);
+    _Static_assert(sizeof(tgpu_window_function_spec) == 8 * sizeof(jint), "the flattened function array is read as tgpu_window_function_spec");
+    _Static_assert(sizeof(tgpu_window_frame_spec) == 5 * sizeof(jint), "the flattened frame array is read as tgpu_window_frame_spec");
+    ints t = ints_get(env, types), oc = ints_get(env, outputChannels), fn = ints_get(env, functions), fr = ints_get(env, frames), pc = ints_get(env, partitionChannels),
+         sc = ints_get(env, sortChannels), so = ints_get(env, sortOrders);
+    const char *bad = NULL;
+    int32_t code = TGPU_ERR_INVALID_ARGUMENT;
+    if (t.n <= 0) bad = "empty type array";
+    for (jsize i = 0; !bad && i < t.n; i++)
+        if (t.p[i] < TGPU_BIGINT || t.p[i] > TGPU_VARCHAR) bad = "unknown type";
+    for (jsize i = 0; !bad && i < oc.n; i++)
+        if (oc.p[i] < 0 || oc.p[i] >= t.n) bad = "output channel out of range";
+    if (!bad && sc.n != so.n) bad = "sort channels and sort orders differ in length";
+    if (!bad && pc.n + sc.n > 8) bad = "more than 8 partition and sort channels";
+    for (jsize i = 0; !bad && i < pc.n; i++)
+        if (pc.p[i] < 0 || pc.p[i] >= t.n) bad = "partition channel out of range";
+    for (jsize i = 0; !bad && i < sc.n; i++) {
+        if (sc.p[i] < 0 || sc.p[i] >= t.n) bad = "sort channel out of range";
+        else if (so.p[i] < TGPU_SORT_ASC_NULLS_FIRST || so.p[i] > TGPU_SORT_DESC_NULLS_LAST) bad = "sort order out of range";
+    }
+    if (!bad && fn.n % 8 != 0) bad = "malformed function array";
+    if (!bad && fn.n == 0) bad = "no window function";
+    if (!bad && fn.n / 8 > TGPU_WINDOW_MAX_FUNCTIONS) bad = "more than 16 window functions";
+    if (!bad && fr.n % 5 != 0) bad = "malformed frame array";
+    if (!bad && fr.n / 5 != fn.n / 8) bad = "frame array and function array differ in length";
+    for (jsize i = 0; !bad && i < fn.n / 8; i++) {
+        bad = window_function_problem_of(fn.p + 8 * i, &t, &code, 1);
+        if (!bad) bad = window_frame_problem(fr.p + 5 * i, &t, &code);
+    }
+    if (!bad && expectedPositions <= 0) {
+        code = TGPU_ERR_INVALID_ARGUMENT;
+        bad = "expected positions must be positive";
+    }
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad)
+        rc = tgpu_window_factory_create_framed(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, oc.n, (const int32_t *)oc.p, fn.n / 8,
+                                               (const tgpu_window_function_spec *)fn.p, (const tgpu_window_frame_spec *)fr.p, pc.n, (const int32_t *)pc.p, sc.n,
+                                               (const int32_t *)sc.p, (const int32_t *)so.p, expectedPositions, &f);
+    ints_release(env, &so);
+    ints_release(env, &sc);
+    ints_release(env, &pc);
+    ints_release(env, &fr);
+    ints_release(env, &fn);
+    ints_release(env, &oc);
+    ints_release(env, &t);
+    if (bad) {
+        char message[128];
+        snprintf(message, sizeof(message), "window: %s", bad);
+        throw_native_message(env, code, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
 }
 
 JFN(jlong, createWindowFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray functions,

@@ -92,6 +92,10 @@ class WindowFunctionSpec(C.Structure):
                 ("ignore_nulls", C.c_int32)]
 
 
+class WindowFrameSpec(C.Structure):
+    _fields_ = [("type", C.c_int32), ("start_type", C.c_int32), ("start_channel", C.c_int32), ("end_type", C.c_int32), ("end_channel", C.c_int32)]
+
+
 _lib = None
 
 # every symbol include/tgpu.h declares: (restype, argtypes)
@@ -186,6 +190,8 @@ SYMBOLS = {
     "tgpu_distinct_limit_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i64, i32, P(vp)]),
     "tgpu_top_n_ranking_factory_create": (i32, [vp, i32, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, P(i32), P(i32), i64, i32, i32, i32, P(vp)]),
     "tgpu_window_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(WindowFunctionSpec), i32, P(i32), i32, P(i32), P(i32), i32, P(vp)]),
+    "tgpu_window_factory_create_framed": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(WindowFunctionSpec), P(WindowFrameSpec), i32, P(i32), i32, P(i32), P(i32), i32,
+                                                P(vp)]),
     "tgpu_row_number_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), i64, i32, i32, P(vp)]),
     "tgpu_limit_factory_create": (i32, [vp, i32, i32, P(i32), i64, P(vp)]),
     "tgpu_merge_pages_factory_create": (i32, [vp, i32, i32, P(i32), i64, i32, i64, P(vp)]),

@@ -12,6 +12,10 @@ struct WindowFunctionSpec {
     int32_t function = 0, agg_function = 0, frame = 0;
     std::vector<int32_t> argument_channels;
     int32_t ignore_nulls = 0;
+    // tgpu_window_factory_create_framed: `frame` is not read, the five fields below are the frame (tgpu_window_frame_spec).  The constructor turns
+    // the three frames the old entry point knows back into their `frame` code (general = 0), so that they take the old path bit for bit.
+    int32_t general = 0;
+    int32_t frame_type = 0, start_type = 0, start_channel = -1, end_type = 0, end_channel = -1;
 };
 
 class WindowGpu {
@@ -30,7 +34,7 @@ public:
     // `all` = every source channel of the whole input.  *positions = its rows in output order (null: arrival order, nothing was sorted);
     // the result = one column per function, in output order.  Raises the sum overflow / negative offset errors.
     std::vector<DeviceColumn> evaluate(const DevicePage &all, BufferPtr *positions);
-    int64_t scratch_bytes() const { return scratch_bytes_; }   // positions + scan arrays of the last evaluate()
+    int64_t scratch_bytes() const { return scratch_bytes_; }   // positions + scan arrays + frame arrays + range-extreme index of the last evaluate()
 
 private:
     Context *ctx_;

@@ -29,6 +29,20 @@
 //                  which k::gather_column turns into the column.  lag / lead with a default channel gather from the value column with the
 //                  default column appended behind it (one PagesIndexGpu of two pages): "the default of the current row" is row N + positions[i],
 //                  so every type, VARCHAR included, takes the one gather.
+// Frames with offsets (tgpu_window_factory_create_framed; ROWS / GROUPS with k PRECEDING / k FOLLOWING, RANGE by peers) add, between 4 and 5:
+//   4a. FRAMES     window_frame_bounds_kernel, once per distinct frame: frame_start[i] / frame_end[i] as indices of the sorted order (-1 = empty),
+//                  the offsets read through positions at the current row (getFrameValue, WindowPartition.java:601-607).  GROUPS finds group g of a
+//                  partition by index in the scattered peer heads.  A null / negative offset raises a bit of error word 2.
+//   4b. EXTREMES   min / max over a frame [s, e] that does not start at its partition's first row is a range-maximum query over the per-row order
+//                  codes (launch 1 leaves them in `raw`), answered from an index of 4 n words + (n / 64) log2(n / 64) words built by
+//                  window_extreme_chunks_kernel (one wave per chunk of 64 rows) and one window_extreme_level_kernel launch per level:
+//                    pre[i], suf[i]   the maximum from the chunk's first row to i / from i to the chunk's last row (one wave-shuffle scan each)
+//                    mask[i]          bit j: row j of the chunk is greater than every row of (j, i] -- the stack of candidates; the maximum of
+//                                     [s, i] inside one chunk is the row of the lowest set bit at or above s
+//                    top[k][c]        the maximum of chunks c .. c + 2^k - 1 (a sparse table)
+//                  so a query reads two to four words, whatever the frame's width.  Frames never cross a partition: nothing is segmented.
+//                  count and sum take the difference of the running arrays at e and s - 1; the sum's running value is kept in both words (`hi`),
+//                  and launch 3 raises no prefix overflow for it: only a frame's own sum outside int64 does, in the evaluate kernel.
 #include "window.h"
 #include "kernels.h"
 #include "topn.h"
@@ -57,6 +71,9 @@ struct ScanAgg {
     int op, function;          // kOp*, tgpu_agg_function
     long long *cnt;            // [n] launch 1: the row's own count, launch 3: the running count
     unsigned long long *val;   // [n] the sum's low word / the extreme's order code (nullptr for the counts)
+    unsigned long long *hi;    // [n] launch 3: the running sum's high word (nullptr: not kept)
+    unsigned long long *raw;   // [n] launch 1: the row's own order code again, which launch 3 leaves alone (nullptr: not kept)
+    int check_prefix;          // launch 3 raises the overflow word for a running sum outside int64 (the frames that grow from the partition's start)
 };
 template <int K> struct ScanArgs {
     ScanAgg a[K > 0 ? K : 1];
@@ -210,6 +227,7 @@ __global__ void __launch_bounds__(kBlock) window_scan_tiles_kernel(ScanArgs<K> a
                     s.w0[k] = w;
                     a.cnt[i] = s.cnt[k];
                     if (a.val) a.val[i] = w;
+                    if (a.raw) a.raw[i] = w;
                 }
             }
             else {
@@ -241,8 +259,9 @@ __global__ void __launch_bounds__(kBlock) window_scan_tiles_kernel(ScanArgs<K> a
                 if (!a.cnt) continue;
                 a.cnt[i] = s.cnt[k];
                 if (a.val) a.val[i] = s.w0[k];
+                if (a.hi) a.hi[i] = s.w1[k];
                 // the prefix of the partition's non-null values up to this row does not fit an int64 (addExact would have thrown)
-                if (a.op == kOpSum && s.w1[k] != (unsigned long long)((long long)s.w0[k] >> 63)) atomicOr(&errors[0], 1u);
+                if (a.op == kOpSum && a.check_prefix && s.w1[k] != (unsigned long long)((long long)s.w0[k] >> 63)) atomicOr(&errors[0], 1u);
             }
         }
     }
@@ -276,8 +295,172 @@ __global__ void __launch_bounds__(kBlock) window_ends_kernel(ScanBounds b, int64
     }
 }
 
+// ---- frames with offsets ----------------------------------------------------------------------------------------------------------------------
+enum { kErrNullStart = 1, kErrNullEnd = 2, kErrNegative = 4 };      // error word 2
+enum { kErrNthOffset = 1, kErrBuckets = 2 };                        // error word 3
+
+struct FrameArgs {
+    int type, start_type, end_type;      // tgpu_frame_type, tgpu_frame_bound
+    TgColView start_offset, end_offset;  // BIGINT or INTEGER, in arrival order; read for PRECEDING / FOLLOWING only
+    const int32_t *positions;
+    const int32_t *part_start, *peer_start, *peer_ord, *peer_heads, *part_end, *peer_end;
+    int32_t *frame_start, *frame_end;    // [n] indices of the sorted order; frame_start = -1: the frame is empty
+    unsigned int *errors;
+};
+
+__device__ __forceinline__ bool bound_has_offset(int t) { return t == TGPU_BOUND_PRECEDING || t == TGPU_BOUND_FOLLOWING; }
+
+// the offset of row r; false: null
+__device__ __forceinline__ bool read_offset(const TgColView &c, long long r, long long &v)
+{
+    if (c.nulls && c.nulls[r]) return false;
+    v = c.type == TGPU_BIGINT ? ((const long long *)c.values)[r] : (long long)((const int *)c.values)[r];
+    return true;
+}
+
+__global__ void __launch_bounds__(kBlock) window_frame_bounds_kernel(FrameArgs f, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        int64_t ps = f.part_start[i];
+        ps = ps < 0 ? 0 : (ps > i ? i : ps);
+        int64_t pe = f.part_end[i];
+        pe = pe < i ? i : (pe > n - 1 ? n - 1 : pe);
+        const long long row = f.positions ? f.positions[i] : i;
+        long long a = 0, b = 0;
+        unsigned int bad = 0;
+        if (bound_has_offset(f.start_type)) {
+            if (!read_offset(f.start_offset, row, a)) bad |= kErrNullStart;
+            else if (a < 0) bad |= kErrNegative;
+        }
+        if (bound_has_offset(f.end_type)) {
+            if (!read_offset(f.end_offset, row, b)) bad |= kErrNullEnd;
+            else if (b < 0) bad |= kErrNegative;
+        }
+        int64_t s = -1, e = -1;
+        bool empty = bad != 0;
+        if (bad) {
+            atomicOr(&f.errors[2], bad);
+        }
+        else if (f.type == TGPU_FRAME_TYPE_ROWS) {
+            // WindowPartition.java:281-323 with emptyFrame :541-573; every comparison is between an offset and a distance: nothing is added to an offset
+            const long long r = i - ps, left = pe - i;   // rows before / behind the current one
+            const int st = f.start_type, et = f.end_type;
+            if (st == TGPU_BOUND_UNBOUNDED_PRECEDING && et == TGPU_BOUND_PRECEDING) empty = b > r;
+            else if (st == TGPU_BOUND_FOLLOWING && et == TGPU_BOUND_UNBOUNDED_FOLLOWING) empty = a > left;
+            else if (st == TGPU_BOUND_PRECEDING && et == TGPU_BOUND_PRECEDING) empty = a < b || (a > r && b > r);
+            else if (st == TGPU_BOUND_FOLLOWING && et == TGPU_BOUND_FOLLOWING) empty = a > b || a > left;
+            s = st == TGPU_BOUND_UNBOUNDED_PRECEDING ? ps : (st == TGPU_BOUND_PRECEDING ? (a > r ? ps : i - a) : (st == TGPU_BOUND_FOLLOWING ? (a > left ? pe : i + a) : i));
+            e = et == TGPU_BOUND_UNBOUNDED_FOLLOWING ? pe : (et == TGPU_BOUND_PRECEDING ? (b > r ? ps : i - b) : (et == TGPU_BOUND_FOLLOWING ? (b > left ? pe : i + b) : i));
+        }
+        else {
+            // GROUPS (:609-694), and RANGE by peers (:327-344) = GROUPS without offsets.  Peer groups are numbered through the whole input:
+            // group g starts at peer_heads[g] and ends in front of peer_heads[g + 1] or at the partition's end
+            const int64_t g = (int64_t)f.peer_ord[i] - 1, first = (int64_t)f.peer_ord[ps] - 1, last = (int64_t)f.peer_ord[pe] - 1;
+            const long long before = g - first, behind = last - g;   // groups of the partition before / behind the current one
+            const bool sane = first >= 0 && first <= g && g <= last && last < n;
+            auto group_start = [&](int64_t x) { return (int64_t)f.peer_heads[x]; };
+            auto group_end = [&](int64_t x) { return x < last ? (int64_t)f.peer_heads[x + 1] - 1 : pe; };
+            if (!sane) {
+                empty = true;   // (never: the scan numbers the heads)
+            }
+            else {
+                switch (f.start_type) {
+                case TGPU_BOUND_UNBOUNDED_PRECEDING: s = ps; break;
+                case TGPU_BOUND_PRECEDING: s = a > before ? ps : group_start(g - a); break;
+                case TGPU_BOUND_FOLLOWING: s = a > behind ? pe + 1 : group_start(g + a); break;   // behind the partition
+                default: s = f.peer_start[i]; break;
+                }
+                switch (f.end_type) {
+                case TGPU_BOUND_UNBOUNDED_FOLLOWING: e = pe; break;
+                case TGPU_BOUND_PRECEDING: e = b > before ? ps - 1 : group_end(g - b); break;
+                case TGPU_BOUND_FOLLOWING: e = b > behind ? pe : group_end(g + b); break;
+                default: e = f.peer_end[i]; break;
+                }
+                empty = s > e || s > pe || e < ps;   // emptyFrame(Range), :523-528
+            }
+        }
+        // a frame lies inside its partition; held to that here, so that no later kernel indexes with anything else
+        if (!empty && (s < ps || e > pe || s > e)) empty = true;
+        f.frame_start[i] = empty ? -1 : (int)s;
+        f.frame_end[i] = empty ? -1 : (int)e;
+    }
+}
+
+// the range-maximum index over one function's per-row order codes (see the head of this file); all arrays [n] but top [levels][chunks]
+struct ExtremeIndex {
+    const unsigned long long *raw, *pre, *suf, *mask, *top;
+    long long chunks;
+};
+
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+__global__ void __launch_bounds__(kBlock) window_extreme_chunks_kernel(const unsigned long long *__restrict__ raw, int64_t n, int64_t chunks, unsigned long long *__restrict__ pre,
+                                                                       unsigned long long *__restrict__ suf, unsigned long long *__restrict__ mask,
+                                                                       unsigned long long *__restrict__ top0)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t chunk = (int64_t)blockIdx.x * kWaves + wave; chunk < chunks; chunk += (int64_t)gridDim.x * kWaves) {   // the same for every lane of a wave
+        const int64_t i = chunk * 64 + lane;
+        const bool live = i < n;
+        const unsigned long long v = live ? raw[i] : 0ULL;   // 0 = below or equal to every code
+        unsigned long long p = v, q = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long up = __shfl_up(p, d, 64), down = __shfl_down(q, d, 64);
+            if (lane >= d) p = umax64(p, up);
+            if (lane + d < 64) q = umax64(q, down);
+        }
+        // the candidates of [.., lane]: walking left from the lane, the rows that beat everything between them and the lane
+        unsigned long long m = 1ULL << lane, running = v;
+        for (int d = 1; d < 64; d++) {
+            const unsigned long long o = __shfl_up(v, d, 64);
+            if (lane >= d) {
+                if (o > running) m |= 1ULL << (lane - d);
+                running = umax64(running, o);
+            }
+        }
+        if (live) {
+            pre[i] = p;
+            suf[i] = q;
+            mask[i] = m;
+        }
+        const unsigned long long all = __shfl(p, 63, 64);
+        if (lane == 0) top0[chunk] = all;
+    }
+}
+
+// level[c] = the maximum of chunks c .. c + 2 * half - 1 (cut at the last chunk) from the level below
+__global__ void __launch_bounds__(kBlock) window_extreme_level_kernel(const unsigned long long *__restrict__ below, unsigned long long *__restrict__ level, int64_t chunks,
+                                                                      int64_t half)
+{
+    for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * kBlock)
+        level[c] = c + half < chunks ? umax64(below[c], below[c + half]) : below[c];
+}
+
+// the maximum of raw[s .. e], 0 <= s <= e < n
+__device__ __forceinline__ unsigned long long range_extreme(const ExtremeIndex &x, int64_t s, int64_t e)
+{
+    const int64_t cs = s >> 6, ce = e >> 6;
+    if (cs == ce) {
+        const unsigned long long bits = x.mask[e] & (~0ULL << (s & 63));   // bit (e & 63) is always set
+        return bits ? x.raw[(cs << 6) + (__ffsll((unsigned long long)bits) - 1)] : x.raw[e];
+    }
+    unsigned long long r = umax64(x.suf[s], x.pre[e]);
+    const long long between = ce - cs - 1;
+    if (between > 0) {
+        const int k = 63 - __clzll(between);
+        const unsigned long long *level = x.top + (long long)k * x.chunks;
+        r = umax64(r, umax64(level[cs + 1], level[ce - (1LL << k)]));
+    }
+    return r;
+}
+
 struct EvalArgs {
     int function, agg_function, frame;
+    int general;                         // the frame is frame_start / frame_end
+    const int32_t *frame_start, *frame_end;
+    const unsigned long long *hi;        // general sum: the running sum's high word
+    ExtremeIndex extremes;               // general min / max whose frame may start behind the partition's first row (raw == nullptr: it cannot)
     int has_offset, has_default;
     TgColView offset;                    // lag / lead: the BIGINT offset channel in arrival order
     const int32_t *positions;            // nullptr: the identity
@@ -288,7 +471,7 @@ struct EvalArgs {
     unsigned char *out_nulls;
     int32_t *out_row;                    // value functions: the source row per output row; -1 = null; source_rows + r = row r of the default column
     long long source_rows;
-    unsigned int *errors;                // [0] sum overflow, [1] negative offset
+    unsigned int *errors;                // [0] sum overflow, [1] negative lag / lead offset, [2] kErrNullStart .., [3] kErrNthOffset ..
 };
 
 __global__ void __launch_bounds__(kBlock) window_evaluate_kernel(EvalArgs e, int64_t n)
@@ -313,6 +496,34 @@ __global__ void __launch_bounds__(kBlock) window_evaluate_kernel(EvalArgs e, int
             break;
         }
         case TGPU_WINDOW_AGGREGATE: {
+            if (e.general) {
+                const bool counts = e.agg_function == TGPU_AGG_COUNT_ALL || e.agg_function == TGPU_AGG_COUNT_COLUMN;
+                const int64_t s = e.frame_start[i], at = e.frame_end[i];
+                if (s < 0) {   // empty: 0 / null
+                    e.out[i] = 0;
+                    if (!counts) e.out_nulls[i] = 1;
+                    break;
+                }
+                // the running arrays restart at the partition's first row: nothing to take off there
+                const long long c = e.cnt[at] - (s > ps ? e.cnt[s - 1] : 0);
+                if (counts) {
+                    e.out[i] = c;
+                    break;
+                }
+                unsigned long long w;
+                if (e.agg_function == TGPU_AGG_SUM_BIGINT) {
+                    const unsigned long long lo1 = e.val[at], hi1 = e.hi[at], lo0 = s > ps ? e.val[s - 1] : 0ULL, hi0 = s > ps ? e.hi[s - 1] : 0ULL;
+                    w = lo1 - lo0;
+                    const unsigned long long high = hi1 - hi0 - (lo1 < lo0 ? 1ULL : 0ULL);
+                    if (high != (unsigned long long)((long long)w >> 63)) atomicOr(&e.errors[0], 1u);   // this frame's sum does not fit an int64
+                }
+                else {
+                    w = s <= ps || !e.extremes.raw ? e.val[at] : range_extreme(e.extremes, s, at);
+                }
+                e.out_nulls[i] = c == 0;
+                e.out[i] = c == 0 ? 0 : (e.agg_function == TGPU_AGG_SUM_BIGINT ? (long long)w : (long long)tg_minmax_decode(e.agg_function, w));
+                break;
+            }
             const int64_t at = e.frame == TGPU_FRAME_PARTITION ? pe : (e.frame == TGPU_FRAME_RANGE_TO_CURRENT ? (int64_t)e.peer_end[i] : i);
             const long long c = e.cnt[at];
             if (e.agg_function == TGPU_AGG_COUNT_ALL || e.agg_function == TGPU_AGG_COUNT_COLUMN) {
@@ -324,8 +535,53 @@ __global__ void __launch_bounds__(kBlock) window_evaluate_kernel(EvalArgs e, int
             e.out[i] = c == 0 ? 0 : (e.agg_function == TGPU_AGG_SUM_BIGINT ? (long long)w : (long long)tg_minmax_decode(e.agg_function, w));
             break;
         }
-        case TGPU_WINDOW_FIRST_VALUE: e.out_row[i] = e.positions ? e.positions[ps] : (int)ps; break;   // all three frames start at the partition's first row
+        case TGPU_WINDOW_FIRST_VALUE:
+            if (e.general) {
+                const int64_t s = e.frame_start[i];
+                e.out_row[i] = s < 0 ? -1 : (e.positions ? e.positions[s] : (int)s);
+                break;
+            }
+            e.out_row[i] = e.positions ? e.positions[ps] : (int)ps;   // all three frames start at the partition's first row
+            break;
+        case TGPU_WINDOW_NTH_VALUE: {   // NthValueFunction.java:41-77; always under frame_start / frame_end
+            const int64_t s = e.frame_start[i], at = e.frame_end[i], r = e.positions ? e.positions[i] : i;
+            int64_t row = -1;
+            if (s >= 0 && !(e.offset.nulls && e.offset.nulls[r])) {
+                const long long offset = ((const long long *)e.offset.values)[r];
+                if (offset < 1) atomicOr(&e.errors[3], (unsigned int)kErrNthOffset);
+                else if (offset - 1 <= at - s) row = e.positions ? e.positions[s + (offset - 1)] : s + (offset - 1);
+            }
+            e.out_row[i] = (int)row;
+            break;
+        }
+        case TGPU_WINDOW_NTILE: {       // NTileFunction.java:45-74; ignores the frame
+            const int64_t r = e.positions ? e.positions[i] : i;
+            const bool null_buckets = e.offset.nulls && e.offset.nulls[r];
+            const long long buckets = null_buckets ? 1 : ((const long long *)e.offset.values)[r];
+            long long bucket = 0;
+            if (buckets <= 0) {
+                atomicOr(&e.errors[3], (unsigned int)kErrBuckets);
+            }
+            else {
+                const long long current = i - ps, rows = pe - ps + 1;
+                if (rows < buckets) {
+                    bucket = current;
+                }
+                else {
+                    const long long remainder = rows % buckets, per = rows / buckets;   // the remainder rows go to the first buckets, one each
+                    bucket = current < (per + 1) * remainder ? current / (per + 1) : (current - remainder) / per;
+                }
+            }
+            e.out_nulls[i] = null_buckets;
+            e.out[i] = null_buckets ? 0 : bucket + 1;
+            break;
+        }
         case TGPU_WINDOW_LAST_VALUE: {
+            if (e.general) {
+                const int64_t at = e.frame_end[i];   // -1 with frame_start
+                e.out_row[i] = at < 0 ? -1 : (e.positions ? e.positions[at] : (int)at);
+                break;
+            }
             const int64_t at = e.frame == TGPU_FRAME_PARTITION ? pe : (e.frame == TGPU_FRAME_RANGE_TO_CURRENT ? (int64_t)e.peer_end[i] : i);
             e.out_row[i] = e.positions ? e.positions[at] : (int)at;
             break;
@@ -385,7 +641,22 @@ void run_scan(Context *ctx, const ScanAgg *aggs, int count, const unsigned char 
     check_launch("window_scan_final");
 }
 
-bool is_value_function(int32_t f) { return f == TGPU_WINDOW_LAG || f == TGPU_WINDOW_LEAD || f == TGPU_WINDOW_FIRST_VALUE || f == TGPU_WINDOW_LAST_VALUE; }
+bool is_value_function(int32_t f)
+{
+    return f == TGPU_WINDOW_LAG || f == TGPU_WINDOW_LEAD || f == TGPU_WINDOW_FIRST_VALUE || f == TGPU_WINDOW_LAST_VALUE || f == TGPU_WINDOW_NTH_VALUE;
+}
+// the functions that read their frame
+bool reads_frame(int32_t f) { return f == TGPU_WINDOW_AGGREGATE || f == TGPU_WINDOW_FIRST_VALUE || f == TGPU_WINDOW_LAST_VALUE || f == TGPU_WINDOW_NTH_VALUE; }
+bool has_offset(int32_t bound) { return bound == TGPU_BOUND_PRECEDING || bound == TGPU_BOUND_FOLLOWING; }
+
+// the tgpu_window_frame code of a general frame that is one of the three old frames, or -1
+int old_frame_code(const WindowFunctionSpec &f)
+{
+    if (f.start_type != TGPU_BOUND_UNBOUNDED_PRECEDING) return -1;
+    if (f.end_type == TGPU_BOUND_UNBOUNDED_FOLLOWING && f.frame_type != TGPU_FRAME_TYPE_GROUPS) return TGPU_FRAME_PARTITION;
+    if (f.end_type != TGPU_BOUND_CURRENT_ROW) return -1;
+    return f.frame_type == TGPU_FRAME_TYPE_RANGE ? TGPU_FRAME_RANGE_TO_CURRENT : (f.frame_type == TGPU_FRAME_TYPE_ROWS ? TGPU_FRAME_ROWS_TO_CURRENT : -1);
+}
 
 }  // namespace
 
@@ -403,8 +674,30 @@ void WindowGpu::validate(const std::vector<int32_t> &types, const std::vector<Wi
     TG_CHECK_ARG(!functions.empty(), "window needs at least one function");
     TG_CHECK_ARG((int)functions.size() <= TGPU_WINDOW_MAX_FUNCTIONS, "at most 16 window functions are supported");
     for (const WindowFunctionSpec &f : functions) {
-        TG_CHECK_ARG(f.function >= TGPU_WINDOW_ROW_NUMBER && f.function <= TGPU_WINDOW_AGGREGATE, "unknown window function");
-        TG_CHECK_ARG(f.frame >= TGPU_FRAME_PARTITION && f.frame <= TGPU_FRAME_ROWS_TO_CURRENT, "unknown window frame");
+        // nth_value and ntile come with the framed entry point only
+        TG_CHECK_ARG(f.function >= TGPU_WINDOW_ROW_NUMBER && f.function <= (f.general ? TGPU_WINDOW_NTILE : TGPU_WINDOW_AGGREGATE), "unknown window function");
+        if (!f.general) {
+            TG_CHECK_ARG(f.frame >= TGPU_FRAME_PARTITION && f.frame <= TGPU_FRAME_ROWS_TO_CURRENT, "unknown window frame");
+        }
+        else {
+            TG_CHECK_ARG(f.frame_type >= TGPU_FRAME_TYPE_RANGE && f.frame_type <= TGPU_FRAME_TYPE_GROUPS, "unknown window frame type");
+            TG_CHECK_ARG(f.start_type >= TGPU_BOUND_UNBOUNDED_PRECEDING && f.start_type <= TGPU_BOUND_UNBOUNDED_FOLLOWING, "unknown window frame bound");
+            TG_CHECK_ARG(f.end_type >= TGPU_BOUND_UNBOUNDED_PRECEDING && f.end_type <= TGPU_BOUND_UNBOUNDED_FOLLOWING, "unknown window frame bound");
+            // the analyzer's rules (sql/analyzer/ExpressionAnalyzer: frame start / end)
+            const bool combination = f.start_type != TGPU_BOUND_UNBOUNDED_FOLLOWING && f.end_type != TGPU_BOUND_UNBOUNDED_PRECEDING &&
+                                     !(f.start_type == TGPU_BOUND_CURRENT_ROW && f.end_type == TGPU_BOUND_PRECEDING) &&
+                                     !(f.start_type == TGPU_BOUND_FOLLOWING && f.end_type != TGPU_BOUND_FOLLOWING && f.end_type != TGPU_BOUND_UNBOUNDED_FOLLOWING);
+            TG_CHECK_ARG(combination, "invalid window frame bounds");
+            for (int side = 0; side < 2; side++) {
+                if (!has_offset(side == 0 ? f.start_type : f.end_type)) continue;
+                const int32_t ch = side == 0 ? f.start_channel : f.end_channel;
+                TG_CHECK_ARG(ch >= 0 && ch < nt, "frame offset channel out of range");
+                TG_CHECK_ARG(types[(size_t)ch] == TGPU_BIGINT || types[(size_t)ch] == TGPU_INTEGER, "a frame offset must be BIGINT or INTEGER");
+            }
+            // the reference compares the sort key with computed bound channels there: a value search, not a count of rows
+            if (f.frame_type == TGPU_FRAME_TYPE_RANGE && (has_offset(f.start_type) || has_offset(f.end_type)))
+                fail(TGPU_ERR_NOT_SUPPORTED, "RANGE frames with an offset are not supported");
+        }
         if (f.ignore_nulls != 0) fail(TGPU_ERR_NOT_SUPPORTED, "IGNORE NULLS is not supported");
         const int na = (int)f.argument_channels.size();
         for (int32_t ch : f.argument_channels) TG_CHECK_ARG(ch >= 0 && ch < nt, "argument channel out of range");
@@ -418,6 +711,8 @@ void WindowGpu::validate(const std::vector<int32_t> &types, const std::vector<Wi
             break;
         case TGPU_WINDOW_FIRST_VALUE:
         case TGPU_WINDOW_LAST_VALUE: TG_CHECK_ARG(na == 1, "first_value / last_value take one argument"); break;
+        case TGPU_WINDOW_NTH_VALUE: TG_CHECK_ARG(na == 2 && type_of(1) == TGPU_BIGINT, "nth_value takes a value and a BIGINT offset"); break;
+        case TGPU_WINDOW_NTILE: TG_CHECK_ARG(na == 1 && type_of(0) == TGPU_BIGINT, "ntile takes one BIGINT argument"); break;
         case TGPU_WINDOW_AGGREGATE:
             switch (f.agg_function) {
             case TGPU_AGG_COUNT_ALL: TG_CHECK_ARG(na == 0, "count(*) takes no argument"); break;
@@ -446,6 +741,18 @@ WindowGpu::WindowGpu(Context *ctx, std::vector<int32_t> types, std::vector<Windo
       sort_channels_(std::move(sort_channels)), sort_orders_(std::move(sort_orders))
 {
     validate(types_, functions_, partition_channels_, sort_channels_, sort_orders_);
+    for (WindowFunctionSpec &f : functions_) {
+        if (!f.general) continue;
+        const int code = old_frame_code(f);
+        if (!reads_frame(f.function)) {   // the frame is ignored
+            f.general = 0;
+            f.frame = TGPU_FRAME_PARTITION;
+        }
+        else if (code >= 0 && f.function != TGPU_WINDOW_NTH_VALUE) {
+            f.general = 0;
+            f.frame = code;
+        }
+    }
 }
 
 std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *positions_out)
@@ -489,13 +796,13 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
         check_launch("window_heads");
     }
     // 3. the scan
-    BufferPtr errors = ctx_->alloc_zero(8);
+    BufferPtr errors = ctx_->alloc_zero(16);
     BufferPtr index_arrays = scratch((size_t)n * 4 * 8);
     int32_t *ia = index_arrays->as<int32_t>();
     const ScanBounds bounds{ia, ia + n, ia + 2 * n, ia + 3 * n, ia + 4 * n, ia + 5 * n};
     int32_t *part_end = ia + 6 * n, *peer_end = ia + 7 * n;
     std::vector<ScanAgg> aggs;
-    std::vector<BufferPtr> cnt_bufs(functions_.size()), val_bufs(functions_.size());
+    std::vector<BufferPtr> cnt_bufs(functions_.size()), val_bufs(functions_.size()), hi_bufs(functions_.size()), raw_bufs(functions_.size());
     for (size_t f = 0; f < functions_.size(); f++) {
         const WindowFunctionSpec &spec = functions_[f];
         if (spec.function != TGPU_WINDOW_AGGREGATE) continue;
@@ -509,6 +816,15 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
         if (!count) {
             val_bufs[f] = scratch((size_t)n * 8);
             a.val = val_bufs[f]->as<unsigned long long>();
+        }
+        a.check_prefix = !spec.general;
+        if (spec.general && a.op == kOpSum) {
+            hi_bufs[f] = scratch((size_t)n * 8);
+            a.hi = hi_bufs[f]->as<unsigned long long>();
+        }
+        if (spec.general && a.op == kOpMax && spec.start_type != TGPU_BOUND_UNBOUNDED_PRECEDING) {
+            raw_bufs[f] = scratch((size_t)n * 8);
+            a.raw = raw_bufs[f]->as<unsigned long long>();
         }
         aggs.push_back(a);
     }
@@ -528,13 +844,73 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
         } while (done < aggs.size());
         ctx_->profile_note("window_scan_rows", n);
     }
+    // 4a. + 4b. frames with offsets: the bounds per distinct frame, the range-extreme index per min / max that needs one
+    bool any_general = false;
+    for (const WindowFunctionSpec &spec : functions_) any_general = any_general || spec.general;
+    std::vector<BufferPtr> frame_bufs(functions_.size());   // [2][n]: frame_start, frame_end; shared by the functions of one frame
+    std::vector<BufferPtr> index_bufs(functions_.size());   // [3][n] pre, suf, mask, then [levels][chunks]
+    const int64_t chunks = ceil_div(n, 64);
+    if (any_general) {
+        {
+            ProfileScope ps(ctx_, "window_frames");
+            window_ends_kernel<<<g, kBlock, 0, ctx_->stream()>>>(bounds, n, part_end, peer_end);
+            check_launch("window_ends");
+            for (size_t f = 0; f < functions_.size(); f++) {
+                const WindowFunctionSpec &spec = functions_[f];
+                if (!spec.general) continue;
+                for (size_t o = 0; o < f && !frame_bufs[f]; o++) {
+                    const WindowFunctionSpec &other = functions_[o];
+                    const bool same = other.general && other.frame_type == spec.frame_type && other.start_type == spec.start_type && other.end_type == spec.end_type &&
+                                      (!has_offset(spec.start_type) || other.start_channel == spec.start_channel) &&
+                                      (!has_offset(spec.end_type) || other.end_channel == spec.end_channel);
+                    if (same) frame_bufs[f] = frame_bufs[o];
+                }
+                if (frame_bufs[f]) continue;
+                frame_bufs[f] = scratch((size_t)n * 2 * 4);
+                FrameArgs fa{};
+                fa.type = spec.frame_type;
+                fa.start_type = spec.start_type;
+                fa.end_type = spec.end_type;
+                if (has_offset(spec.start_type)) fa.start_offset = view_of(all.cols[(size_t)spec.start_channel]);
+                if (has_offset(spec.end_type)) fa.end_offset = view_of(all.cols[(size_t)spec.end_channel]);
+                fa.positions = pos;
+                fa.part_start = bounds.part_start;
+                fa.peer_start = bounds.peer_start;
+                fa.peer_ord = bounds.peer_ord;
+                fa.peer_heads = bounds.peer_heads;
+                fa.part_end = part_end;
+                fa.peer_end = peer_end;
+                fa.frame_start = frame_bufs[f]->as<int32_t>();
+                fa.frame_end = fa.frame_start + n;
+                fa.errors = errors->as<unsigned int>();
+                window_frame_bounds_kernel<<<g, kBlock, 0, ctx_->stream()>>>(fa, n);
+                check_launch("window_frame_bounds");
+            }
+        }
+        ProfileScope ps(ctx_, "window_extremes");
+        int levels = 1;
+        while ((1LL << levels) <= chunks) levels++;   // level k spans 2^k chunks
+        for (size_t f = 0; f < functions_.size(); f++) {
+            if (!raw_bufs[f]) continue;
+            index_bufs[f] = scratch(((size_t)n * 3 + (size_t)levels * (size_t)chunks) * 8);
+            unsigned long long *x = index_bufs[f]->as<unsigned long long>(), *top = x + 3 * n;
+            window_extreme_chunks_kernel<<<grid_for(ctx_, chunks, kWaves), kBlock, 0, ctx_->stream()>>>(raw_bufs[f]->as<unsigned long long>(), n, chunks, x, x + n, x + 2 * n, top);
+            check_launch("window_extreme_chunks");
+            for (int k = 1; k < levels; k++) {
+                window_extreme_level_kernel<<<grid_for(ctx_, chunks), kBlock, 0, ctx_->stream()>>>(top + (size_t)(k - 1) * chunks, top + (size_t)k * chunks, chunks, 1LL << (k - 1));
+                check_launch("window_extreme_level");
+            }
+        }
+    }
     // 4. + 5. ends, then one launch per function
     std::vector<DeviceColumn> result(functions_.size());
     std::vector<BufferPtr> rows(functions_.size());
     {
         ProfileScope ps(ctx_, "window_evaluate");
-        window_ends_kernel<<<g, kBlock, 0, ctx_->stream()>>>(bounds, n, part_end, peer_end);
-        check_launch("window_ends");
+        if (!any_general) {
+            window_ends_kernel<<<g, kBlock, 0, ctx_->stream()>>>(bounds, n, part_end, peer_end);
+            check_launch("window_ends");
+        }
         for (size_t f = 0; f < functions_.size(); f++) {
             const WindowFunctionSpec &spec = functions_[f];
             EvalArgs e{};
@@ -549,6 +925,16 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
             e.peer_end = peer_end;
             e.source_rows = n;
             e.errors = errors->as<unsigned int>();
+            e.general = spec.general;
+            if (spec.general) {
+                e.frame_start = frame_bufs[f]->as<int32_t>();
+                e.frame_end = e.frame_start + n;
+                if (hi_bufs[f]) e.hi = hi_bufs[f]->as<unsigned long long>();
+                if (index_bufs[f]) {
+                    const unsigned long long *x = index_bufs[f]->as<unsigned long long>();
+                    e.extremes = ExtremeIndex{raw_bufs[f]->as<unsigned long long>(), x, x + n, x + 2 * n, x + 3 * n, (long long)chunks};
+                }
+            }
             if (is_value_function(spec.function)) {
                 e.has_offset = spec.argument_channels.size() > 1;
                 e.has_default = spec.argument_channels.size() > 2;
@@ -574,14 +960,25 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
                         e.out_nulls = c.nulls_buf->as<uint8_t>();
                     }
                 }
+                else if (spec.function == TGPU_WINDOW_NTILE) {
+                    e.offset = view_of(all.cols[(size_t)spec.argument_channels[0]]);
+                    c.nulls_buf = ctx_->alloc((size_t)n);
+                    c.nulls = c.nulls_buf->as<uint8_t>();
+                    e.out_nulls = c.nulls_buf->as<uint8_t>();
+                }
             }
             window_evaluate_kernel<<<g, kBlock, 0, ctx_->stream()>>>(e, n);
             check_launch("window_evaluate");
         }
     }
-    // the two error words, before anything is gathered for rows that must not be
-    unsigned int err[2] = {0, 0};
+    // the error words, before anything is gathered for rows that must not be
+    unsigned int err[4] = {0, 0, 0, 0};
     ctx_->download(err, errors->ptr(), sizeof(err));
+    if (err[2] & kErrNullStart) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame starting offset must not be null");   // getFrameValue, WindowPartition.java:601-607
+    if (err[2] & kErrNullEnd) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame ending offset must not be null");
+    if (err[2] & kErrNegative) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame offset must not be negative");
+    if (err[3] & kErrNthOffset) fail(TGPU_ERR_INVALID_ARGUMENT, "Offset must be at least 1");                       // NthValueFunction.java:49
+    if (err[3] & kErrBuckets) fail(TGPU_ERR_INVALID_ARGUMENT, "Buckets must be greater than 0");                   // NTileFunction.java:52
     if (err[0]) fail(TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "bigint addition overflow");   // BigintOperators.add under LongSumAggregation
     if (err[1]) fail(TGPU_ERR_INVALID_ARGUMENT, "Offset must be at least 0");            // LagFunction.java / LeadFunction.java checkCondition
     {

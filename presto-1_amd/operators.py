@@ -845,23 +845,60 @@ class TopNRankingOperatorFactory(OperatorFactory):
 WINDOW_ROW_NUMBER, WINDOW_RANK, WINDOW_DENSE_RANK, WINDOW_PERCENT_RANK, WINDOW_CUME_DIST = 0, 1, 2, 3, 4
 WINDOW_LAG, WINDOW_LEAD, WINDOW_FIRST_VALUE, WINDOW_LAST_VALUE, WINDOW_AGGREGATE = 5, 6, 7, 8, 9
 FRAME_PARTITION, FRAME_RANGE_TO_CURRENT, FRAME_ROWS_TO_CURRENT = 0, 1, 2
+# tgpu_window_factory_create_framed: two more functions, tgpu_frame_type / tgpu_frame_bound
+WINDOW_NTH_VALUE, WINDOW_NTILE = 10, 11
+FRAME_TYPE_RANGE, FRAME_TYPE_ROWS, FRAME_TYPE_GROUPS = 0, 1, 2
+BOUND_UNBOUNDED_PRECEDING, BOUND_PRECEDING, BOUND_CURRENT_ROW, BOUND_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = 0, 1, 2, 3, 4
+
+
+class WindowFrame:
+    """A frame with bounds (tgpu_window_frame_spec; M/operator/window/FrameInfo.java): `type` = a FRAME_TYPE_* code, `start_type` / `end_type` =
+    BOUND_* codes, `start_channel` / `end_channel` = the BIGINT or INTEGER source channel of a PRECEDING / FOLLOWING bound's offset, read per row."""
+
+    def __init__(self, type, start_type, end_type, start_channel=-1, end_channel=-1):
+        self.type, self.start_type, self.end_type = int(type), int(start_type), int(end_type)
+        self.start_channel, self.end_channel = int(start_channel), int(end_channel)
+
+    def spec(self):
+        return _lib.WindowFrameSpec(self.type, self.start_type, self.start_channel, self.end_type, self.end_channel)
+
+
+# the three frames of tgpu_window_factory_create as the framed entry point takes them
+_OLD_FRAMES = {FRAME_PARTITION: (FRAME_TYPE_RANGE, BOUND_UNBOUNDED_PRECEDING, BOUND_UNBOUNDED_FOLLOWING),
+               FRAME_RANGE_TO_CURRENT: (FRAME_TYPE_RANGE, BOUND_UNBOUNDED_PRECEDING, BOUND_CURRENT_ROW),
+               FRAME_ROWS_TO_CURRENT: (FRAME_TYPE_ROWS, BOUND_UNBOUNDED_PRECEDING, BOUND_CURRENT_ROW)}
 
 
 class WindowFunction:
     """One window function of a WindowOperatorFactory (tgpu_window_function_spec): `function` = a WINDOW_* code, `argument_channels` = its 0 to 3
-    source channels (lag / lead: value, offset, default), `frame` = a FRAME_* code (read by the aggregates and first / last value),
-    `agg_function` = the aggregate of WINDOW_AGGREGATE (COUNT_ALL, COUNT_COLUMN, SUM_BIGINT, MIN_* / MAX_*)."""
+    source channels (lag / lead: value, offset, default; nth_value: value, offset; ntile: buckets), `frame` = a FRAME_* code or a WindowFrame (read
+    by the aggregates and first / last / nth value), `agg_function` = the aggregate of WINDOW_AGGREGATE (COUNT_ALL, COUNT_COLUMN, SUM_BIGINT,
+    MIN_* / MAX_*)."""
 
     def __init__(self, function, argument_channels=(), frame=FRAME_RANGE_TO_CURRENT, agg_function=0, ignore_nulls=False):
-        self.function, self.argument_channels, self.frame = int(function), tuple(int(c) for c in argument_channels), int(frame)
+        self.function, self.argument_channels = int(function), tuple(int(c) for c in argument_channels)
+        self.frame = frame if isinstance(frame, WindowFrame) else int(frame)
         self.agg_function, self.ignore_nulls = int(agg_function), bool(ignore_nulls)
+
+    def framed(self):
+        """needs tgpu_window_factory_create_framed"""
+        return isinstance(self.frame, WindowFrame) or self.function > WINDOW_AGGREGATE
 
     def spec(self):
         if len(self.argument_channels) > 3:
             raise ValueError("a window function takes at most 3 argument channels")
         channels = self.argument_channels + (0,) * (3 - len(self.argument_channels))
-        return _lib.WindowFunctionSpec(self.function, self.agg_function, self.frame, len(self.argument_channels), (C.c_int32 * 3)(*channels),
+        frame = 0 if isinstance(self.frame, WindowFrame) else self.frame
+        return _lib.WindowFunctionSpec(self.function, self.agg_function, frame, len(self.argument_channels), (C.c_int32 * 3)(*channels),
                                        1 if self.ignore_nulls else 0)
+
+    def frame_spec(self):
+        if isinstance(self.frame, WindowFrame):
+            return self.frame.spec()
+        if self.frame not in _OLD_FRAMES:
+            raise ValueError("unknown window frame")
+        t, s, e = _OLD_FRAMES[self.frame]
+        return _lib.WindowFrameSpec(t, s, -1, e, -1)
 
 
 class WindowOperatorFactory(OperatorFactory):
@@ -881,8 +918,13 @@ class WindowOperatorFactory(OperatorFactory):
         so, _ = _i32(sort_orders)
         specs = (_lib.WindowFunctionSpec * max(1, len(functions)))(*[f.spec() for f in functions])
         h = C.c_void_p()
-        _lib.check(_lib.lib().tgpu_window_factory_create(ctx.handle, operator_id, nt, t, no, o, len(functions), specs, np_, p, ns, sc, so, int(expected_positions),
-                                                         C.byref(h)))
+        if any(f.framed() for f in functions):
+            frames = (_lib.WindowFrameSpec * max(1, len(functions)))(*[f.frame_spec() for f in functions])
+            _lib.check(_lib.lib().tgpu_window_factory_create_framed(ctx.handle, operator_id, nt, t, no, o, len(functions), specs, frames, np_, p, ns, sc, so,
+                                                                    int(expected_positions), C.byref(h)))
+        else:
+            _lib.check(_lib.lib().tgpu_window_factory_create(ctx.handle, operator_id, nt, t, no, o, len(functions), specs, np_, p, ns, sc, so, int(expected_positions),
+                                                             C.byref(h)))
         super().__init__(h)
 
 
