@@ -108,6 +108,7 @@ SYMBOLS = {
     "tgpu_last_error": (cp, []),
     "tgpu_version": (cp, []),
     "tgpu_fused_probe_launch_counts": (i32, [P(i64)]),
+    "tgpu_fused_probe_depth_counts": (i32, [P(i64)]),
     "tgpu_set_resource_dir": (i32, [cp]),
     "tgpu_context_set_double_sum_order": (i32, [vp, i32]),
     "tgpu_context_set_device_input_stable": (i32, [vp, i32]),

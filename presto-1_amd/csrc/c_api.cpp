@@ -172,6 +172,13 @@ int32_t tgpu_fused_probe_launch_counts(int64_t out[3])
     tgpu::fused_probe_launch_counts(out);
     return TGPU_OK;
 }
+// ... and by the row sets pass 1 keeps in flight -- out[0] one (FJ_DEPTH 1), out[1] two (FJ_DEPTH 2: whole-table launches only)
+int32_t tgpu_fused_probe_depth_counts(int64_t out[2])
+{
+    if (!out) return TGPU_ERR_INVALID_ARGUMENT;
+    tgpu::fused_probe_depth_counts(out);
+    return TGPU_OK;
+}
 
 int32_t tgpu_set_resource_dir(const char *dir)
 {

@@ -958,7 +958,7 @@ std::string spec_key(const char *what, const std::vector<int32_t> &input_types, 
     for (int32_t i = 0; i < spec->projection_count; i++) put_i32(k, spec->projection_roots[i]);
     put_i32(k, (int32_t)extra.size());
     for (int32_t v : extra) put_i32(k, v);
-    for (const char *env : {"TGPU_FG_EXP", "TGPU_FJ_EXP", "TGPU_FA_STRIPES", "TGPU_FJ_STRIPES", "TGPU_FG_STRIPES"}) {
+    for (const char *env : {"TGPU_FG_EXP", "TGPU_FJ_EXP", "TGPU_FA_STRIPES", "TGPU_FJ_STRIPES", "TGPU_FG_STRIPES", "TGPU_FJ_DEPTH"}) {
         const char *v = getenv(env);
         k += '|';
         if (v) k += v;
@@ -1149,6 +1149,22 @@ struct FjArgs {
 #ifndef FJ_EPILOGUE
 #define FJ_EPILOGUE 0   // the variant for pages (few, one-tile chunks): pass 1 ends with the scan and hands its totals to the host itself
 #endif
+#ifndef FJ_DEPTH
+#define FJ_DEPTH 1      // row sets in flight: 2 = the rows of the tile after next are loaded while this iteration's look-ups are waited for
+#endif
+#if FJ_DEPTH == 2 && FJ_EPILOGUE
+#error "FJ_DEPTH 2 is a variant of the whole-table kernel only"
+#endif
+#if FJ_DEPTH == 2
+// The iteration's wait leaves the youngest row set outstanding: vmcnt counts loads AND stores on this target and retires them in order,
+// so the row loads are the last vector-memory operations an iteration issues (behind the pair stores).  FJ_ROW_LOADS = load instructions
+// per row as generated; the count is 6 bits wide, [3:0] and [15:14] of the operand (0x0F70: no wait on the other counters).  Correctness
+// does not rest on the number: the compiler adds whatever wait a register use needs.
+#define FJ_PENDING (FJ_ROW_LOADS * FJ_STRIPES > 63 ? 63 : FJ_ROW_LOADS * FJ_STRIPES)
+#define FJ_WAIT (0x0F70 | (FJ_PENDING & 15) | ((FJ_PENDING >> 4) << 14))
+#else
+#define FJ_WAIT 0x0F70  // vmcnt(0): everything the previous iteration issued (consumed right below anyway)
+#endif
 
 // rows-capacity offset of block b's private pair region: CHUNKS of 2^chunk_shift consecutive tiles are dealt round-robin, block b
 // owns ceil((chunks - b) / grid) of them
@@ -1170,6 +1186,12 @@ __device__ inline long long fj_region_base(long long b, long long tiles, long lo
 // compacts / writes the pairs of tile it-3, whose slots arrived during the previous iteration.  One memory round trip per
 // iteration instead of three (vmcnt is in-order on CDNA: a wait for a dependent load would also wait for every prefetch
 // issued before it, so "prefetch, then probe" inside one iteration cannot overlap).
+//
+// FJ_DEPTH 2 (whole-table launches): a second set of row registers.  Iteration `it` issues the rows of tile it+1 -- as its LAST
+// vector-memory operations, behind the pair stores -- and waits at its top for everything but that youngest set, so a wave always has a
+// tile's rows in flight, also while it waits for its look-ups.  Stage B of iteration `it` consumes the set issued by iteration it-2 (tile
+// it-1; the prologue issues tile 0).  The two sets alternate by writing the loop body twice per trip, never by copying registers (a copy
+// from a register with a pending load waits for the load).  Rows per lane, compaction order and pairs are those of depth 1.
 __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned int bid, const unsigned int nblk) {
   const FpArgs& A = J.fp;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1214,7 +1236,11 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
   long long tN0 = pt0[pN];
 #endif
   long long chunk_local0 = 0;   // `local` at the start of the chunk being compacted
+#if FJ_DEPTH == 2
+  TgRow rwa[FJ_STRIPES], rwb[FJ_STRIPES];                                                                          // stage A -> B: tiles of even / odd j
+#else
   TgRow rw[FJ_STRIPES];                                                                                            // stage A -> B
+#endif
   long long pkey[FJ_STRIPES]; unsigned int psidx[FJ_STRIPES]; unsigned long long pbw[FJ_STRIPES];                      // B -> C
 #if FJ_PF == 2
   unsigned long long pbits[FJ_STRIPES];     // Bloom mask of the key
@@ -1240,13 +1266,29 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
 #endif
 #pragma unroll
   for (int s = 0; s < FJ_STRIPES; s++) {
+#if FJ_DEPTH == 2
+    tg_zero_row(rwa[s]); tg_zero_row(rwb[s]);
+#else
     tg_zero_row(rw[s]);
+#endif
     pkey[s] = 0; psidx[s] = 0; pbits[s] = 0; pbw[s] = 0; pfl[s] = 0;
     skey[s] = 0; ssidx[s] = 0; sfl[s] = 0; ssl[s].key = 0; ssl[s].head = -1; ssl[s].count = 0;
   }
-  for (long long it = 0; it < my_tiles + 3; it++) {
-    const long long jD = it - 3, jC = it - 2, jB = it - 1, jA = it;
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): everything the previous iteration issued (consumed right below anyway)
+#if FJ_DEPTH == 2
+  // whole trips of two iterations: an exit between the two instances of the body would be one more way into the loop header for the compiler's
+  // wait-count bookkeeping, with the other row set pending there.  The odd iteration out is idle (every tile at or past my_tiles is past J.tiles).
+  const long long n_it = (my_tiles + 4) & ~1LL;
+#else
+  const long long n_it = my_tiles + 3;
+#endif
+@FJ_LOOP@
+)SRC";
+
+// One iteration of fj_probe_body's loop.  generate() instantiates it with the row set the iteration works on in place of @RW@ (stage B reads
+// it, stage A then loads it again) and kFjRowLoads in place of @ROW_LOADS@: once at depth 1, twice per trip at depth 2.
+const char *kFjLoopBody = R"SRC(
+    const long long jD = it - 3, jC = it - 2, jB = it - 1, jA = it + (FJ_DEPTH - 1);
+    __builtin_amdgcn_s_waitcnt(FJ_WAIT);
     // stage D, part 1: resolve tile jD from the slots loaded by the previous iteration; only a collision with another key
     // walks further
     int head[FJ_STRIPES];
@@ -1387,13 +1429,13 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
         const unsigned int row = row0 + s * 64;
         bool sel = false, passed = false;
         long long key = 0;
-        if (row < n_rows && tg_filter(AB, row, rw[s])) {
+        if (row < n_rows && tg_filter(AB, row, @RW@[s])) {
           selected++;
           passed = true;
-          const bool kn = tg_key(AB, row, rw[s], key);   // JoinProbe.java:87-97: a null probe key never matches
+          const bool kn = tg_key(AB, row, @RW@[s], key);   // JoinProbe.java:87-97: a null probe key never matches
           sel = !kn;
 #if FJ_CARRY
-          tg_carry_eval(AB, row, rw[s], pov[s]);
+          tg_carry_eval(AB, row, @RW@[s], pov[s]);
 #endif
         }
         bidx[s] = 0;
@@ -1445,6 +1487,21 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
       pbw[s] = ~0ULL;
 #endif
     }
+#if FJ_DEPTH != 2
+@ROW_LOADS@
+#endif
+    __builtin_amdgcn_sched_barrier(0);
+@STAGE_D2@
+#if FJ_DEPTH == 2
+    // the rows of tile jA = it + 1: the youngest vector-memory operations of the iteration, behind stage D's stores (see FJ_WAIT)
+    __builtin_amdgcn_sched_barrier(0);
+@ROW_LOADS@
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+)SRC";
+
+// stage A of an iteration (and of the depth-2 prologue): the rows of tile jA into the set @RW@
+const char *kFjRowLoads = R"SRC(
     {
 #if FJ_EPILOGUE == 2
       // this iteration's page was fetched by the previous one (idle stage: the same page again, its first tile)
@@ -1471,17 +1528,20 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
 #endif
       if (tile_row0 + FJ_TILE <= n_rows) {   // interior tile: one address per column, the stripes are constant offsets from it
 #pragma unroll
-        for (int s = 0; s < FJ_STRIPES; s++) tg_load_row(AA, row0 + s * 64, rw[s]);
+        for (int s = 0; s < FJ_STRIPES; s++) tg_load_row(AA, row0 + s * 64, @RW@[s]);
       }
       else {
 #pragma unroll
         for (int s = 0; s < FJ_STRIPES; s++) {
           const unsigned int row = row0 + s * 64;
-          tg_load_row(AA, row < n_rows ? row : n_rows - 1, rw[s]);
+          tg_load_row(AA, row < n_rows ? row : n_rows - 1, @RW@[s]);
         }
       }
     }
-    __builtin_amdgcn_sched_barrier(0);
+)SRC";
+
+// stage D, part 2 of an iteration (the variants that do not run it in front of stage C)
+const char *kFjStageD2 = R"SRC(
 #if FJ_CARRY != 1
     // stage D, part 2: compact the pairs of tile jD in input order and append them to the block's region
     if (doD) {
@@ -1528,7 +1588,10 @@ __device__ __forceinline__ void fj_probe_body(const FjArgs& J, const unsigned in
       }
     }
 #endif
-  }
+)SRC";
+
+// fj_probe_body behind its loop, and the other kernels
+const char *kFjKernelsTail = R"SRC(
   // rows that passed the filter: ONE atomic per workgroup, spread over FJ_COUNT_SLOTS words on separate cache lines (the host adds
   // them up).  One atomic per wave onto a single word serialised at ~13 ns each: 50 us for the 1024 workgroups of a 2^20-row page,
   // 80 us at the end of every full-size launch.
@@ -1750,9 +1813,27 @@ static std::atomic<int64_t> g_fj_launches[3];
 // only free channel; it is HBM-bound, its emit pass moves only 3 M pairs, and carrying the key raises fj_probe_direct from 66 to 86 VGPRs
 // (7 -> 5 waves per SIMD) -- registers for almost nothing (DESIGN.md §5 "Partial carry").  TGPU_FJ_CARRY_RULE overrides it for kernel studies.
 constexpr int kFjFreeRule = 1;
+// ... and by the row sets pass 1 keeps in flight {FJ_DEPTH 1, FJ_DEPTH 2} (tgpu_fused_probe_depth_counts)
+static std::atomic<int64_t> g_fj_depth_launches[2];
+// Which whole-table launches load their rows two tiles ahead (FJ_DEPTH 2), by carry mode {two-pass gather, full carry, partial carry}:
+// a static rule chosen by measurement (DESIGN.md §5 "Row loads two tiles ahead"): Q3's lineitem launch (no carry, 66 -> 68 VGPRs, still 7
+// waves per SIMD) gains 0.02-0.05 ms of 1.45, its orders launch (partial carry, 78 -> 81 VGPRs, 6 -> 5 waves) 0.055 ms of 0.74 in every
+// round -- it waits for look-ups, and now has the next rows in flight meanwhile.  The opt-in full carry was not measured and stays at 1.
+// The page and multi-page variants always run depth 1.  TGPU_FJ_DEPTH overrides the rule for kernel studies and tests.
+constexpr int kFjDepthByCarry[3] = {2, 1, 2};
+static int fj_depth_for(int carry, int epilogue)
+{
+    if (epilogue != 0) return 1;
+    if (const char *e = getenv("TGPU_FJ_DEPTH")) return atoi(e) == 2 ? 2 : 1;
+    return kFjDepthByCarry[carry];
+}
 void fused_probe_launch_counts(int64_t out[3])
 {
     for (int i = 0; i < 3; i++) out[i] = g_fj_launches[i].load(std::memory_order_relaxed);
+}
+void fused_probe_depth_counts(int64_t out[2])
+{
+    for (int i = 0; i < 2; i++) out[i] = g_fj_depth_launches[i].load(std::memory_order_relaxed);
 }
 
 void FusedProbeGpu::generate()
@@ -1888,6 +1969,9 @@ void FusedProbeGpu::generate()
     for (int ch : carry_only_cols) src << "  R.c" << ch << " = 0; R.n" << ch << " = 0;\n";
     src << "#endif\n";
     src << "  (void)R;\n}\n";
+    // load instructions tg_load_row issues per row (FJ_DEPTH 2 sizes its wait with it): a value per column, a null byte where the page may have
+    // null vectors; the partial carry reads none of the carry-only columns, so their loads fold away
+    src << "#define FJ_ROW_LOADS ((" << gr.reg_cols.size() << " + (FJ_CARRY == 1 ? " << carry_only_cols.size() << " : 0)) * (FJ_NO_NULLS ? 1 : 2))\n";
     const std::string rc = cols_decl(gr), mc = cols_decl(gm);
     for (auto &b : reg_bodies) src << splice(b, rc);
     for (auto &b : mem_bodies) src << splice(b, mc);
@@ -1939,7 +2023,18 @@ void FusedProbeGpu::generate()
     // experiment switches for kernel studies (tools/exp_fused.py); never set in production
     if (const char *exp = getenv("TGPU_FJ_EXP")) src << "#define FJ_EXP_" << exp << " 1\n";
     {
-        std::string kernels = kFjKernels;
+        auto replace_all = [](std::string t, const std::string &tag, const std::string &with) {
+            for (size_t p = t.find(tag); p != std::string::npos; p = t.find(tag, p + with.size())) t.replace(p, tag.size(), with);
+            return t;
+        };
+        // the loop of fj_probe_body: the body once per trip, or -- two row sets -- twice, each instance naming its set (no register copies);
+        // the depth-2 prologue issues tile 0's rows, so the loop is entered in the pending state its back edge has
+        const std::string body = replace_all(replace_all(kFjLoopBody, "@STAGE_D2@", kFjStageD2), "@ROW_LOADS@", kFjRowLoads);
+        const std::string loop = std::string("#if FJ_DEPTH == 2\n  {\n    const long long jA = 0;\n    const bool doA = jA < my_tiles && tile_of(jA) < J.tiles;\n") +
+                                 replace_all(kFjRowLoads, "@RW@", "rwa") + "  }\n  for (long long it = 0; it < n_it;) {\n    {\n" + replace_all(body, "@RW@", "rwb") +
+                                 "    }\n    ++it;\n    {\n" + replace_all(body, "@RW@", "rwa") + "    }\n    ++it;\n  }\n#else\n" +
+                                 "  for (long long it = 0; it < n_it; it++) {\n" + replace_all(body, "@RW@", "rw") + "  }\n#endif\n";
+        std::string kernels = replace_all(kFjKernels, "@FJ_LOOP@", loop) + kFjKernelsTail;
         const std::string tag = "@FJ_STRIPES@";
         kernels.replace(kernels.find(tag), tag.size(), std::to_string(fj_stripes()));
         const std::string ctag = "@CARRY_FUNCS@";
@@ -1958,8 +2053,8 @@ static std::string prefilter_source(const std::string &src, int variant)
     // statistics then keep the DIRECT-layout launches (TPCH keys) apart from the open-address ones
     static const char *layout[4] = {"plain", "bitmap", "bloom", "direct"};
     const std::string l = layout[variant % 4];
-    return "#define FJ_PF " + std::to_string(variant % 4) + "\n#define FJ_NO_NULLS " + std::to_string((variant / 4) % 2) + "\n#define FJ_CARRY " + std::to_string(variant / 24) +
-           "\n#define FJ_EPILOGUE " + std::to_string((variant / 8) % 3) + "\n#define fj_pair fj_pair_" + l + "\n#define fj_probe fj_probe_" + l +
+    return "#define FJ_PF " + std::to_string(variant % 4) + "\n#define FJ_NO_NULLS " + std::to_string((variant / 4) % 2) + "\n#define FJ_CARRY " + std::to_string((variant / 24) % 3) +
+           "\n#define FJ_DEPTH " + std::to_string(variant / 72 + 1) + "\n#define FJ_EPILOGUE " + std::to_string((variant / 8) % 3) + "\n#define fj_pair fj_pair_" + l + "\n#define fj_probe fj_probe_" + l +
            "\n#define fj_emit fj_emit_" + l + "\n" + src;
 }
 
@@ -1967,17 +2062,20 @@ void FusedProbeGpu::precompile()
 {
     if (!supported_) return;
     for (int variant = 0; variant < 24; variant++) {   // layout x null vectors x {whole table, one page, a list of pages}
-        (void)code_object_for(prefilter_source(source_, variant));
+        const int epilogue = variant / 8;
+        (void)code_object_for(prefilter_source(source_, variant + 72 * (fj_depth_for(0, epilogue) - 1)));
         // the default of the exact-bitmap and DIRECT layouts when a channel is free: partial carry (a list of pages never carries)
-        if (partial_supported_ && (variant % 4 == 1 || variant % 4 == 3) && variant / 8 < 2) (void)code_object_for(prefilter_source(source_, 48 + variant));
+        if (partial_supported_ && (variant % 4 == 1 || variant % 4 == 3) && epilogue < 2)
+            (void)code_object_for(prefilter_source(source_, 48 + variant + 72 * (fj_depth_for(2, epilogue) - 1)));
     }
     // (the opt-in full carry variants, 24 + ..., are compiled on first use)
 }
 
-JitModule *FusedProbeGpu::module_for(int kind, bool no_nulls, int carry, int epilogue)
+JitModule *FusedProbeGpu::module_for(int kind, bool no_nulls, int carry, int epilogue, int depth)
 {
     std::lock_guard<std::mutex> lk(mu_);
-    const int variant = kind + (no_nulls ? 4 : 0) + epilogue * 8 + carry * 24;   // epilogue: 0 plain, 1 page, 2 list of pages; carry: 0 none, 1 full, 2 partial
+    // epilogue: 0 plain, 1 page, 2 list of pages; carry: 0 none, 1 full, 2 partial; depth: row sets in flight, 1 or 2
+    const int variant = kind + (no_nulls ? 4 : 0) + epilogue * 8 + carry * 24 + (depth - 1) * 72;
     if (!modules_[variant]) modules_[variant] = load_module(prefilter_source(source_, variant));
     return modules_[variant].get();
 }
@@ -2075,7 +2173,8 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     // the hand-over of the totals; whole tables keep the variant without it (measured on the SF100 tables: the epilogue's write-through
     // count stores and its extra state cost the lineitem launch 1.50 -> 1.82 ms)
     const bool page_variant = multi || (ceil_div(n, tile_rows) <= kFjEpilogueMaxChunks && getenv("TGPU_DISABLE_PROBE_EPILOGUE") == nullptr);
-    JitModule *module = module_for(tv.rank_base ? 3 : (tv.bitmap ? 1 : (tv.bloom ? 2 : 0)), !any_nulls, carry, multi ? 2 : (page_variant ? 1 : 0));
+    const int depth = fj_depth_for(carry, multi ? 2 : (page_variant ? 1 : 0));
+    JitModule *module = module_for(tv.rank_base ? 3 : (tv.bitmap ? 1 : (tv.bloom ? 2 : 0)), !any_nulls, carry, multi ? 2 : (page_variant ? 1 : 0), depth);
     std::shared_ptr<Pending> pend = std::make_shared<Pending>();
     pend->col_nulls = col_nulls;
     pend->kernel_variant = multi ? 2 : (page_variant ? 1 : 0);
@@ -2121,7 +2220,9 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     // persistent workgroups: exactly as many as are resident at once (a second round of workgroups would only add a tail)
     const int pf_kind = tv.rank_base ? 3 : (tv.bitmap ? 1 : (tv.bloom ? 2 : 0));
     static const char *probe_names[4] = {"fj_probe_plain", "fj_probe_bitmap", "fj_probe_bloom", "fj_probe_direct"};
-    const int64_t resident = (int64_t)ctx->cu_count() * module->blocks_per_cu(probe_names[pf_kind]);
+    int64_t resident = (int64_t)ctx->cu_count() * module->blocks_per_cu(probe_names[pf_kind]);
+    // (tests: with a few workgroups a few thousand rows give each of them many tiles and chunks of several tiles)
+    if (const char *cap = getenv("TGPU_FJ_MAX_BLOCKS")) resident = std::min<int64_t>(resident, std::max(1, atoi(cap)));
     // chunks of consecutive tiles per workgroup (fj_probe): up to 64 tiles, but at least ~4 chunks per resident workgroup
     int chunk_shift = 0;
     const int max_chunk_shift = getenv("TGPU_FJ_CHUNK_SHIFT") ? atoi(getenv("TGPU_FJ_CHUNK_SHIFT")) : 6;
@@ -2206,6 +2307,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     pend->tile_cnt = tile_cnt; pend->tile_src = tile_src; pend->tile_dst = tile_dst; pend->misc = misc; pend->pair_probe = pair_probe; pend->pair_build = pair_build;
     // (launch == false: the caller puts pass 1 into one launch with another page's pass 2, launch_pair; only the page variant can)
     g_fj_launches[carry].fetch_add(1, std::memory_order_relaxed);
+    g_fj_depth_launches[depth - 1].fetch_add(1, std::memory_order_relaxed);
     if (launch || !epilogue) launch_probe(ctx, pend);
     signal_guard.armed = false;
     return pend;

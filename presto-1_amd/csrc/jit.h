@@ -146,6 +146,7 @@ constexpr int64_t kFjEpilogueMaxChunks = 2048;   // probe launches of up to 2048
 
 class LookupSourceGpu;
 void fused_probe_launch_counts(int64_t out[3]);
+void fused_probe_depth_counts(int64_t out[2]);   // launches by row sets in flight {FJ_DEPTH 1, FJ_DEPTH 2}
 
 class FusedProbeGpu {
 public:
@@ -188,7 +189,7 @@ public:
 
 private:
     void generate();
-    struct JitModule *module_for(int prefilter_kind, bool no_nulls, int carry, int epilogue);
+    struct JitModule *module_for(int prefilter_kind, bool no_nulls, int carry, int epilogue, int depth);
     std::mutex mu_;
     std::vector<int32_t> input_types_;
     std::vector<tgpu_expr_node> nodes_;
@@ -198,7 +199,7 @@ private:
     int32_t join_channel_;
     bool supported_ = false;
     std::string source_;
-    std::shared_ptr<JitModule> modules_[72];   // layout (4) x no-null-vectors (2) x {whole table, one page with the epilogue, list of pages} (3) x carry {none, full, partial} (3)
+    std::shared_ptr<JitModule> modules_[144];  // layout (4) x no-null-vectors (2) x {whole table, one page with the epilogue, list of pages} (3) x carry {none, full, partial} (3) x row sets in flight (2)
     bool carry_supported_ = false;
     bool partial_supported_ = false, key_can_raise_ = false;
     std::vector<bool> free_out_;   // per output channel: pass 1 holds what it needs (partial carry, generate() (d))

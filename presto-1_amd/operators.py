@@ -588,6 +588,13 @@ def fused_probe_launch_counts():
     return tuple(int(v) for v in out)
 
 
+def fused_probe_depth_counts():
+    """(depth 1, depth 2): fused probe launches prepared so far in this process, by the row sets pass 1 keeps in flight (jit.cpp FJ_DEPTH)"""
+    out = (C.c_int64 * 2)()
+    _lib.check(_lib.lib().tgpu_fused_probe_depth_counts(out))
+    return tuple(int(v) for v in out)
+
+
 class GroupByHash:
     """GroupByHash.createGroupByHash (M/operator/GroupByHash.java:45-59) over the GPU table."""
 
