@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 from gpu_common import drive_with_revokes as _drive_with_revokes
-from gpu_common import ocol, rand_block, run_agg, ulp_diff
+from gpu_common import outer_join as _outer_join
+from gpu_common import ocol, rand_block, run_agg, run_join, ulp_diff
 from seqpages import sequence_page, sequence_values
 
 pytestmark = pytest.mark.gpu
@@ -383,30 +384,6 @@ def test_global_aggregation_and_default_output(pkg, ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # hash join
 # ---------------------------------------------------------------------------------------------------------------------
-def run_join(pkg, ctx, build_pages, probe_pages, types_b, types_p, key_b, key_p, hash_b=-1, hash_p=-1, join_type=0, out_b=None, out_p=None):
-    out_b = list(range(len(types_b))) if out_b is None else out_b
-    bf = pkg.HashBuilderOperatorFactory(ctx, 1, types_b, out_b, key_b, precomputed_hash_channel=hash_b)
-    jf = pkg.LookupJoinOperatorFactory(ctx, 2, bf.lookup_source_factory, types_p, key_p, probe_hash_channel=hash_p, probe_output_channels=out_p, join_type=join_type)
-    build = bf.createOperator()
-    probe = jf.createOperator()
-    assert probe.isBlocked() and not probe.needsInput()  # waits on the lookup source future (LookupJoinOperator.java:235-243)
-    for p in build_pages:
-        assert build.needsInput()
-        build.addInput(p)
-    build.finish()
-    assert not probe.isBlocked()
-    out = pkg.to_pages(probe, probe_pages)
-    stats = bf.lookup_source_factory.stats()
-    probe.close()
-    jf.noMoreOperators()
-    assert build.isFinished()
-    build.close()
-    rows = []
-    for p in out:
-        rows.extend(p.rows())
-    return rows, stats
-
-
 def test_hash_join_empty_probe_and_blocking_lookup_source_golden(pkg, ctx):
     """T/operator/TestHashJoinOperator.java:1200-1238 testInnerJoinWithNonEmptyLookupSourceAndEmptyProbe (build rows a, b, null, c; no probe page:
     no output), :1241-1259 testInnerJoinWithBlockingLookupSourceAndEmptyProbe (the build never finishes: the probe operator does not need input;
@@ -2263,42 +2240,6 @@ def test_merge_pages_argument_checks(pkg, ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # LOOKUP_OUTER / FULL_OUTER joins + LookupOuterOperator against the oracle's pair list + visited set
 # ---------------------------------------------------------------------------------------------------------------------
-def _outer_join(pkg, ctx, build_pages, probe_page_lists, types_b, types_p, key_b, key_p, join_type, out_b, out_p, fused=None):
-    """several probe operators over one lookup source, then the outer operator; returns (probe rows per operator, outer rows)"""
-    bf = pkg.HashBuilderOperatorFactory(ctx, 1, types_b, out_b, key_b)
-    if fused is None:
-        jf = pkg.LookupJoinOperatorFactory(ctx, 2, bf.lookup_source_factory, types_p, key_p, probe_output_channels=out_p, join_type=join_type)
-    else:
-        jf = pkg.FilterProjectLookupJoinOperatorFactory(ctx, 2, bf.lookup_source_factory, types_p, fused[0], fused[1], key_p, probe_output_channels=out_p, join_type=join_type)
-    of = pkg.LookupOuterOperatorFactory(ctx, 3, bf.lookup_source_factory, [types_p[c] for c in out_p] if fused is None else fused[2])
-    build = bf.createOperator()
-    probes = [jf.createOperator() for _ in probe_page_lists]
-    outer = of.createOperator()
-    assert outer.isBlocked() and not outer.needsInput() and outer.getOutput() is None
-    for p in build_pages:
-        build.addInput(p)
-    build.finish()
-    assert outer.isBlocked()   # the probes are not done yet (PartitionedLookupSourceFactory.java:259-297)
-    probe_rows = []
-    for op, pages in zip(probes, probe_page_lists):
-        rows = []
-        for pg in pkg.to_pages(op, pages):
-            rows.extend(pg.rows())
-        probe_rows.append(rows)
-        op.close()
-        assert outer.isBlocked()   # ... and the factory may still create more probe operators
-    jf.noMoreOperators()
-    assert not outer.isBlocked() and not build.isFinished()   # the table stays alive for the outer operator
-    o = outer.getOutput()
-    outer_rows = o.to_host().rows() if o is not None else []
-    if o is not None:
-        o.release()
-    assert outer.isFinished() and outer.getOutput() is None
-    assert build.isFinished()
-    build.close(); outer.close(); jf.close(); of.close(); bf.close()
-    return probe_rows, outer_rows
-
-
 @pytest.mark.parametrize("join_type", ["LOOKUP_OUTER", "FULL_OUTER"])
 @pytest.mark.parametrize("key_type,domain", [("BIGINT", (0, 3000)), ("VARCHAR", (0, 400)), ("BIGINT", (10**12, 10**12 + 50))])
 def test_outer_joins_vs_oracle(pkg, ctx, oracle, join_type, key_type, domain):
