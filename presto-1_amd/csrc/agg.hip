@@ -962,26 +962,33 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
         for (int k = 0; k < kMaxAggs; k++) plan.slot[k] = (k < args.n_aggs && args.a[k].dsum) ? doubles++ : -1;
         const int64_t ids = group_count > 0 ? group_count : 1;
         const bool chained = doubles <= TG_ORD_MAX_DOUBLES && ids <= ord_chain_max_groups() && n >= ids * kOrdChainMinRows && getenv("TGPU_DISABLE_ORDERED_CHAIN") == nullptr;
-        ProfileScope ps(ctx_, chained ? "agg_accumulate_ordered_chain" : "agg_accumulate_ordered");
         BufferPtr keys, rows;
-        sort_rows_by_group(gids, n, group_count, keys, rows, gids_ascending);
-        if (chained) {
-            BufferPtr stretches = group_stretches(keys->as<unsigned int>(), n, ids);
-            agg_ordered_chain_kernel<<<(int)ids, TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(args, plan, stretches->as<int>(), keys->as<unsigned int>(), rows->as<int>(), n, nullptr,
-                                                                                          nullptr);
-            check_launch("agg_accumulate_ordered_chain");
-            return;
-        }
         // one lane per group; a group of more than kOrdHandoffRows rows (one key far more frequent than the others) goes to the chained
         // kernel after that many rows
         const int64_t long_groups = n / kOrdHandoffRows;   // at most this many groups can be that long
-        const bool handoff = long_groups > 0 && doubles <= TG_ORD_MAX_DOUBLES && getenv("TGPU_DISABLE_ORDERED_CHAIN") == nullptr;
-        BufferPtr list = handoff ? ctx_->alloc((size_t)long_groups * 16) : nullptr, list_count = handoff ? ctx_->alloc_zero(8) : nullptr;
-        agg_ordered_kernel<false><<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(args, keys->as<unsigned int>(), rows->as<int>(), n, error_->as<unsigned int>(),
-                                                                                      handoff ? kOrdHandoffRows : 0, handoff ? list->as<long long>() : nullptr,
-                                                                                      handoff ? list_count->as<unsigned int>() : nullptr);
-        check_launch("agg_accumulate_ordered");
-        if (handoff) {
+        const bool handoff = !chained && long_groups > 0 && doubles <= TG_ORD_MAX_DOUBLES && getenv("TGPU_DISABLE_ORDERED_CHAIN") == nullptr;
+        BufferPtr list, list_count;
+        {
+            ProfileScope ps(ctx_, chained ? "agg_accumulate_ordered_chain" : "agg_accumulate_ordered");
+            sort_rows_by_group(gids, n, group_count, keys, rows, gids_ascending);
+            if (chained) {
+                BufferPtr stretches = group_stretches(keys->as<unsigned int>(), n, ids);
+                agg_ordered_chain_kernel<<<(int)ids, TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(args, plan, stretches->as<int>(), keys->as<unsigned int>(), rows->as<int>(), n,
+                                                                                              nullptr, nullptr);
+                check_launch("agg_accumulate_ordered_chain");
+                return;
+            }
+            if (handoff) {
+                list = ctx_->alloc((size_t)long_groups * 16);
+                list_count = ctx_->alloc_zero(8);
+            }
+            agg_ordered_kernel<false><<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(args, keys->as<unsigned int>(), rows->as<int>(), n, error_->as<unsigned int>(),
+                                                                                          handoff ? kOrdHandoffRows : 0, handoff ? list->as<long long>() : nullptr,
+                                                                                          handoff ? list_count->as<unsigned int>() : nullptr);
+            check_launch("agg_accumulate_ordered");
+        }
+        if (handoff) {   // (a scope of its own, like the fused operator's: a profile tells the two launches apart)
+            ProfileScope ps(ctx_, "agg_accumulate_ordered_handoff");
             agg_ordered_chain_kernel<<<(int)std::min<int64_t>(long_groups, ctx_->cu_count()), TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(
                 args, plan, nullptr, keys->as<unsigned int>(), rows->as<int>(), n, list->as<long long>(), list_count->as<unsigned int>());
             check_launch("agg_accumulate_ordered_handoff");

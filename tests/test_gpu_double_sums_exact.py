@@ -5,18 +5,18 @@ mixed size into one state, global aggregation, PARTIAL -> FINAL, spilled runs, a
 import numpy as np
 import pytest
 
+from agg_paths import (PATHS, assert_profile, drive, final_aggs, is_fused, late_group_first_row, max_lowcard_groups_fused, max_lowcard_groups_plain,
+                       page_sizes, run_final, run_partials)
 from exact_sum import FAMILIES, bits_equal, exact_double_sum, make_stream
-from gpu_common import drive_with_revokes, run_agg
 
 pytestmark = pytest.mark.gpu
 
-PATHS = ("general", "lowcard", "lowcard_multi", "global", "fused", "fused_onepass", "fused_onepass_batch1", "partial_final", "spilled",
-         "java_order", "java_order_fused")
 # the most groups that still decide EXACT on the lane-private path: 160 KiB of LDS / the bytes of one group's lane-private states --
 # plain operator (agg.hip lowcard_bytes_per_group: 5 sums x 2 x 256 x 8 + 7 counts x 256 x 4), fused operator (jit.cpp: the sums over
 # the same input and mask share a slot: 4 x 2 x 256 x 8 + (5 counts + the row count) x 256 x 4, 64 bytes of headroom)
-MAX_EXACT_PLAIN = (160 * 1024) // (5 * 2 * 256 * 8 + 7 * 256 * 4)
-MAX_EXACT_FUSED = (160 * 1024 - 64) // (4 * 2 * 256 * 8 + 6 * 256 * 4)
+MAX_EXACT_PLAIN = max_lowcard_groups_plain(5, 7)
+MAX_EXACT_FUSED = max_lowcard_groups_fused(4, 5)
+assert (MAX_EXACT_PLAIN, MAX_EXACT_FUSED) == ((160 * 1024) // (5 * 2 * 256 * 8 + 7 * 256 * 4), (160 * 1024 - 64) // (4 * 2 * 256 * 8 + 6 * 256 * 4))
 
 
 def aggs_of(pkg):
@@ -24,24 +24,17 @@ def aggs_of(pkg):
             (pkg.COUNT_COLUMN, 2)]
 
 
-def page_sizes(path):
-    if path == "lowcard_multi":
-        return [20_000, 1_000, 3_000, 9_000, 4095, 4096]            # both kernels into one state (asserted for the global aggregation)
-    if path.startswith("fused_onepass"):
-        return [9_000] * 8
-    if path in ("partial_final", "spilled"):
-        return [12_000, 3_000, 16_000]
-    return [40_000]
+def fused_spec(pkg):
+    f = pkg.field
+    B, D, BO = pkg.BIGINT, pkg.DOUBLE, pkg.BOOLEAN
+    return [B, D, D, BO, B, D], f(5, D) < 0.9, [f(0, B), f(1, D), f(2, D), f(3, BO), f(4, B)]
 
 
 def build(pkg, name, ngroups, path, seed):
     rng = np.random.default_rng(seed)
     sizes = page_sizes(path)
     n = sum(sizes)
-    first_row = None
-    late = path.startswith("fused_onepass") and ngroups > 1
-    if late:                                  # the last group arrives in the 6th page: that one-pass launch is dirty and re-run
-        first_row = [0] * (ngroups - 1) + [sum(sizes[:5]) + 4000]
+    first_row = late_group_first_row(path, ngroups)
     gids, vals, nulls, mask, big, filt = make_stream(name, rng, ngroups, n, first_row=first_row, with_filter=path.startswith(("fused", "java_order_fused")))
     pages, at = [], 0
     B, D, BO = pkg.BIGINT, pkg.DOUBLE, pkg.BOOLEAN
@@ -84,95 +77,31 @@ def check(rows, want, key_of=lambda r: r[0]):
     assert not bad, bad
 
 
-def run_plain(pkg, ctx, pages, ngroups, global_agg=False, step=0):
-    aggs = aggs_of(pkg)
-    if global_agg:
-        fac = pkg.HashAggregationOperatorFactory(ctx, 0, [], [], aggs, step=step)
-        op = fac.createOperator()
-        out = pkg.to_pages(op, pages)
-        op.close()
-        return [(0,) + tuple(r) for p in out for r in p.rows()]
-    return run_agg(pkg, ctx, pages, [pkg.BIGINT], [0], aggs, step=step, expected=ngroups)
-
-
-def run_fused(pkg, ctx, pages):
-    f = pkg.field
-    B, D, BO = pkg.BIGINT, pkg.DOUBLE, pkg.BOOLEAN
-    T = [B, D, D, BO, B, D]
-    fac = pkg.FilterProjectHashAggregationOperatorFactory(ctx, 0, T, f(5, D) < 0.9, [f(0, B), f(1, D), f(2, D), f(3, BO), f(4, B)], [B], [0], aggs_of(pkg))
-    return [r for p in pkg.to_pages(fac.createOperator(), pages) for r in p.rows()]
-
-
 CELLS = [(path, g) for path in PATHS for g in ([1] if path == "global" else [1, 3, "max"])]
 
 
 @pytest.mark.parametrize("path,ngroups", CELLS)
 @pytest.mark.parametrize("name", FAMILIES)
 def test_double_sums_exact(pkg, oracle, monkeypatch, name, path, ngroups):
-    fused = path.startswith("fused") or path == "java_order_fused"
     if ngroups == "max":
-        ngroups = MAX_EXACT_FUSED if fused else MAX_EXACT_PLAIN
+        ngroups = MAX_EXACT_FUSED if is_fused(path) else MAX_EXACT_PLAIN
     seed = 3000 + 100 * FAMILIES.index(name) + ngroups
     pages, sizes, rows_in = build(pkg, name, ngroups, path, seed)
-    if path == "general":
-        monkeypatch.setenv("TGPU_DISABLE_LOWCARD", "1")
-    if path == "lowcard_multi":                # (the mode is decided by the first page: the later pages are accumulated one by one)
-        monkeypatch.setenv("TGPU_MODE_PREFIX_ROWS", "5000")
-    if path == "fused":
-        monkeypatch.setenv("TGPU_DISABLE_ONEPASS", "1")
-    if path.startswith("fused_onepass"):
-        monkeypatch.setenv("TGPU_MODE_PREFIX_ROWS", "5000")
-        if path == "fused_onepass_batch1":
-            monkeypatch.setenv("TGPU_ONEPASS_BATCH_ROWS", "1")
-    ctx = pkg.Context(0)
-    ctx.profile_enable(True)
-    try:
-        want = expected(rows_in, ngroups)
-        if path in ("general", "lowcard", "lowcard_multi", "global"):
-            # (one group through lowcard_multi: a global aggregation, whose pages are accumulated one by one as they come)
-            rows = run_plain(pkg, ctx, pages, ngroups, global_agg=path == "global" or (path == "lowcard_multi" and ngroups == 1))
-        elif path in ("fused", "fused_onepass", "fused_onepass_batch1"):
-            rows = run_fused(pkg, ctx, pages)
-        elif path == "spilled":
-            op = pkg.HashAggregationOperatorFactory(ctx, 0, [pkg.BIGINT], [0], aggs_of(pkg), expected_groups=ngroups, spill_enabled=True).createOperator()
-            rows = drive_with_revokes(op, pages, True)
-            assert op.spillStats()[0] >= 1
-            op.close()
-        elif path == "partial_final":
-            rows = partial_final(pkg, ctx, pages, sizes, rows_in, ngroups)
-            want = None
-        else:
-            ctx.set_double_sum_order(pkg.SUM_ORDER_JAVA)
-            rows = run_fused(pkg, ctx, pages) if fused else run_plain(pkg, ctx, pages, ngroups)
-            want = expected(rows_in, ngroups, java=oracle)
-        prof = ctx.profile()
-    finally:
-        ctx.close()
-    if want is not None:
-        check(rows, want)
-    lowcard = "agg_accumulate_lowcard" in prof
-    if path == "general":
-        assert "agg_accumulate" in prof and not lowcard
-    if path in ("lowcard", "global", "spilled", "partial_final"):
-        assert lowcard
-    if path == "lowcard_multi":
-        assert lowcard and ("agg_accumulate" in prof or ngroups > 1), sorted(prof)
-    if path == "spilled":
-        assert "agg_merge_states" in prof
-    if path == "fused":
-        assert "fused_project_accumulate_lowcard" in prof and "fused_filter_group_accumulate_onepass" not in prof
-    if path.startswith("fused_onepass"):
-        assert "fused_filter_group_accumulate_onepass" in prof
+    want = expected(rows_in, ngroups, java=oracle if path.startswith("java_order") else None)
+    got = drive(pkg, monkeypatch, path, ngroups, pages, aggs_of(pkg), fused_spec,
+                partial_final=lambda ctx: partial_final(pkg, ctx, pages, sizes, rows_in, ngroups))
+    if got.error is not None:
+        raise got.error
+    if path != "partial_final":                # (checked against its own partials in partial_final)
+        check(got.rows, want)
+    assert_profile(path, got.profile, ngroups)
 
 
 def partial_final(pkg, ctx, pages, sizes, rows_in, ngroups):
     """each PARTIAL (one per page) equals the exact sums of its page; FINAL equals the exact sums of the rounded partials"""
     gids, vals, nulls, mask, big = rows_in
     partials, at = [], 0
-    for pg, m in zip(pages, sizes):
-        op = pkg.HashAggregationOperatorFactory(ctx, 0, [pkg.BIGINT], [0], aggs_of(pkg), step=pkg.PARTIAL, expected_groups=ngroups).createOperator()
-        out = pkg.to_pages(op, [pg])
-        op.close()
+    for out, m in zip(run_partials(pkg, ctx, [[pg] for pg in pages], ngroups, aggs_of(pkg)), sizes):
         s = slice(at, at + m)
         at += m
         cnt, sm = exact_double_sum(vals[s], gids[s], ngroups)
@@ -187,9 +116,9 @@ def partial_final(pkg, ctx, pages, sizes, rows_in, ngroups):
             if cm[g]:
                 assert bits_equal(r[6], smm[g]), (g, r, smm[g])
         partials += out
-    fin = [(pkg.SUM_DOUBLE, 1), (pkg.AVG_DOUBLE, 3), (pkg.SUM_DOUBLE, 5), (pkg.AVG_DOUBLE, 7), (pkg.AVG_BIGINT, 9), (pkg.COUNT_ALL, 11),
-           (pkg.COUNT_COLUMN, 12)]
-    rows = run_agg(pkg, ctx, partials, [pkg.BIGINT], [0], fin, step=pkg.FINAL, expected=ngroups)
+    assert final_aggs(pkg, aggs_of(pkg)) == [(pkg.SUM_DOUBLE, 1), (pkg.AVG_DOUBLE, 3), (pkg.SUM_DOUBLE, 5), (pkg.AVG_DOUBLE, 7), (pkg.AVG_BIGINT, 9),
+                                             (pkg.COUNT_ALL, 11), (pkg.COUNT_COLUMN, 12)]
+    rows = run_final(pkg, ctx, partials, ngroups, aggs_of(pkg))
     inter = [r for p in partials for r in p.rows()]
     ig = np.array([r[0] for r in inter], dtype=np.int64)
 
