@@ -166,10 +166,27 @@ typedef enum tgpu_expr_kind { TGPU_EX_INPUT = 0, TGPU_EX_CONST = 1, TGPU_EX_CALL
 typedef enum tgpu_expr_op {
     TGPU_OP_ADD = 1, TGPU_OP_SUBTRACT, TGPU_OP_MULTIPLY, TGPU_OP_DIVIDE, TGPU_OP_MODULUS, TGPU_OP_NEGATE,
     TGPU_OP_EQUAL, TGPU_OP_NOT_EQUAL, TGPU_OP_LESS_THAN, TGPU_OP_LESS_THAN_OR_EQUAL, TGPU_OP_GREATER_THAN,
-    TGPU_OP_GREATER_THAN_OR_EQUAL, TGPU_OP_NOT, TGPU_OP_CAST
+    TGPU_OP_GREATER_THAN_OR_EQUAL, TGPU_OP_NOT, TGPU_OP_CAST,
+    /* value LIKE pattern [ESCAPE escape] (M/type/LikeFunctions.java:62-118 likeVarchar / likePattern, :198-255 the pattern translation and
+     * getEscapeChar).  Result BOOLEAN, n_args 2 or 3: args[0] any VARCHAR expression, args[1] the pattern, args[2] the optional escape.  Pattern and
+     * escape must be TGPU_EX_CONST VARCHAR nodes (TGPU_ERR_NOT_SUPPORTED otherwise): the generator reads them, they are never evaluated as
+     * values.  '%' matches any run of bytes, '_' exactly one code point, everything else is a literal and the whole value must match.  Without an
+     * escape argument nothing escapes; an empty escape disables escaping; one character escapes '%', '_' and itself.  A longer escape fails with
+     * "Escape string must be a single character", an escape character followed by anything else (or ending the pattern) with "Escape character
+     * must be followed by '%', '_' or the escape character itself": both TGPU_ERR_INVALID_ARGUMENT when the factory is created.  A null value,
+     * pattern or escape gives NULL.  LIKE raises no per-row error. */
+    TGPU_OP_LIKE = 15
 } tgpu_expr_op;
 typedef enum tgpu_special_form { /* M/sql/relational/SpecialForm.java:137-152 */
-    TGPU_SF_AND = 1, TGPU_SF_OR, TGPU_SF_IF, TGPU_SF_IS_NULL, TGPU_SF_COALESCE, TGPU_SF_BETWEEN
+    TGPU_SF_AND = 1, TGPU_SF_OR, TGPU_SF_IF, TGPU_SF_IS_NULL, TGPU_SF_COALESCE, TGPU_SF_BETWEEN,
+    /* value IN (item, ...) (M/sql/gen/InCodeGenerator.java:92-121; equality is the type's EQUAL operator).  Result BOOLEAN, n_args = 1: args[0]
+     * is the value, of any of the six types.  The list is `slen` consecutive nodes starting at node index `ival` (fields that are otherwise
+     * read on CONST nodes only: every walker over args[0 .. n_args) stays correct, list items reference no channel).  Each item is a
+     * TGPU_EX_CONST of the value's type; a null item is allowed.  slen < 1, a range outside the node array, a non-constant item or an item of
+     * another type: TGPU_ERR_INVALID_ARGUMENT; more than 65,536 items: TGPU_ERR_NOT_SUPPORTED.  A null value gives NULL; otherwise TRUE when
+     * a non-null item equals the value; otherwise NULL when the list holds a null item, else FALSE.  DOUBLE compares with == (NaN matches
+     * nothing, -0.0 matches +0.0), VARCHAR by bytes. */
+    TGPU_SF_IN = 7
 } tgpu_special_form;
 
 typedef struct tgpu_expr_node {

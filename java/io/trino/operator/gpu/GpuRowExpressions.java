@@ -7,6 +7,8 @@ import io.trino.sql.relational.ConstantExpression;
 import io.trino.sql.relational.InputReferenceExpression;
 import io.trino.sql.relational.RowExpression;
 import io.trino.sql.relational.SpecialForm;
+import io.trino.type.JoniRegexp;
+import io.trino.type.LikeFunctions;
 
 import java.io.ByteArrayOutputStream;
 import java.util.ArrayList;
@@ -25,6 +27,8 @@ public final class GpuRowExpressions
     private static final String[] OPERATORS = {null, "$operator$ADD", "$operator$SUBTRACT", "$operator$MULTIPLY", "$operator$DIVIDE", "$operator$MODULUS", "$operator$NEGATION",
             "$operator$EQUAL", "$operator$NOT_EQUAL", "$operator$LESS_THAN", "$operator$LESS_THAN_OR_EQUAL", "$operator$GREATER_THAN", "$operator$GREATER_THAN_OR_EQUAL", "not",
             "$operator$CAST"};
+    private static final int OP_EQUAL = 7, OP_LIKE = 15, SF_OR = 2, SF_IN = 7;   // TGPU_OP_EQUAL, TGPU_OP_LIKE, TGPU_SF_OR, TGPU_SF_IN
+    private static final String LIKE_FUNCTION_NAME = "like";                    // LikeFunctions.likeVarchar (type/LikeFunctions.java:71-74)
 
     public static final class Program
     {
@@ -111,10 +115,16 @@ public final class GpuRowExpressions
                     return emit(p, CALL, type, op, args, false, 0, 0, 0);
                 }
             }
+            if (LIKE_FUNCTION_NAME.equalsIgnoreCase(name) && call.getArguments().size() == 2) {
+                return addLike(p, type, call.getArguments().get(0), call.getArguments().get(1));
+            }
             throw new IllegalArgumentException("function not in the GPU IR: " + name);
         }
         if (e instanceof SpecialForm) {
             SpecialForm form = (SpecialForm) e;
+            if (form.getForm() == SpecialForm.Form.IN) {
+                return addIn(p, type, form.getArguments());
+            }
             int op;
             switch (form.getForm()) {
                 case AND: op = 1; break;
@@ -133,5 +143,147 @@ public final class GpuRowExpressions
             return emit(p, SPECIAL, type, op, args, false, 0, 0, 0);
         }
         throw new IllegalArgumentException("expression not in the GPU IR: " + e);
+    }
+
+    private static int addStringConstant(Program p, int type, byte[] bytes)
+    {
+        if (bytes == null) {
+            return emit(p, CONST, type, 0, new int[0], true, 0, 0, 0);
+        }
+        int at = p.stringPool.size();
+        p.stringPool.write(bytes, 0, bytes.length);
+        return emit(p, CONST, type, 0, new int[0], false, at, 0, bytes.length);
+    }
+
+    private static byte[] constantBytes(RowExpression e)
+    {
+        if (!(e instanceof ConstantExpression)) {
+            throw new IllegalArgumentException("LIKE pattern / escape is not a constant");
+        }
+        Object value = ((ConstantExpression) e).getValue();
+        if (value != null && !(value instanceof Slice)) {
+            throw new IllegalArgumentException("LIKE pattern / escape is not a varchar constant");
+        }
+        return value == null ? null : ((Slice) value).getBytes();
+    }
+
+    /**
+     * value LIKE pattern -> TGPU_OP_LIKE(value, pattern constant [, escape constant]).  The pattern argument is either the call
+     * $like_pattern(pattern [, escape]) over constants, or what the optimizer folded it to: a ConstantExpression holding the JoniRegexp
+     * that LikeFunctions.likePattern built (type/LikeFunctions.java:198-241).  Anything else is outside the IR.
+     */
+    private static int addLike(Program p, int type, RowExpression value, RowExpression pattern)
+    {
+        int varchar = GpuPages.typeCode(value.getType());
+        int valueNode = add(p, value);
+        if (pattern instanceof CallExpression) {
+            CallExpression call = (CallExpression) pattern;
+            List<RowExpression> arguments = call.getArguments();
+            if (!LikeFunctions.LIKE_PATTERN_FUNCTION_NAME.equalsIgnoreCase(call.getResolvedFunction().getSignature().getName()) || arguments.isEmpty() || arguments.size() > 2) {
+                throw new IllegalArgumentException("LIKE pattern is not a $like_pattern call");
+            }
+            for (RowExpression argument : arguments) {
+                if (GpuPages.typeCode(argument.getType()) != varchar) {   // the char(x) flavour pads the pattern: not in the IR
+                    throw new IllegalArgumentException("LIKE pattern is not a varchar");
+                }
+            }
+            int patternNode = addStringConstant(p, varchar, constantBytes(arguments.get(0)));
+            if (arguments.size() == 1) {
+                return emit(p, CALL, type, OP_LIKE, new int[] {valueNode, patternNode}, false, 0, 0, 0);
+            }
+            int escapeNode = addStringConstant(p, varchar, constantBytes(arguments.get(1)));
+            return emit(p, CALL, type, OP_LIKE, new int[] {valueNode, patternNode, escapeNode}, false, 0, 0, 0);
+        }
+        if (pattern instanceof ConstantExpression) {
+            Object folded = ((ConstantExpression) pattern).getValue();
+            if (folded == null) {
+                int patternNode = addStringConstant(p, varchar, null);
+                return emit(p, CALL, type, OP_LIKE, new int[] {valueNode, patternNode}, false, 0, 0, 0);
+            }
+            if (folded instanceof JoniRegexp) {
+                byte[] like = likePatternOfRegex(((JoniRegexp) folded).pattern().toStringUtf8()).getBytes(java.nio.charset.StandardCharsets.UTF_8);
+                int patternNode = addStringConstant(p, varchar, like);
+                int escapeNode = addStringConstant(p, varchar, new byte[] {'\\'});
+                return emit(p, CALL, type, OP_LIKE, new int[] {valueNode, patternNode, escapeNode}, false, 0, 0, 0);
+            }
+        }
+        throw new IllegalArgumentException("LIKE pattern is not a constant");
+    }
+
+    /**
+     * The inverse of LikeFunctions.likePattern's translation: '^', then ".*" for '%', "." for '_', a backslash in front of each of
+     * \ ^ $ . * and every other character (an escaped '%' or '_' among them) as itself, then '$'.  The translation is injective, so
+     * the regex text gives back a LIKE pattern, written here with the escape character backslash.
+     */
+    static String likePatternOfRegex(String regex)
+    {
+        if (regex.length() < 2 || regex.charAt(0) != '^' || regex.charAt(regex.length() - 1) != '$') {
+            throw new IllegalArgumentException("not a regex written by LikeFunctions.likePattern");
+        }
+        StringBuilder like = new StringBuilder();
+        for (int i = 1; i < regex.length() - 1; i++) {
+            char c = regex.charAt(i);
+            if (c == '.') {
+                if (i + 1 < regex.length() - 1 && regex.charAt(i + 1) == '*') {
+                    like.append('%');
+                    i++;
+                }
+                else {
+                    like.append('_');
+                }
+                continue;
+            }
+            if (c == '\\') {
+                i++;
+                if (i >= regex.length() - 1) {
+                    throw new IllegalArgumentException("not a regex written by LikeFunctions.likePattern");
+                }
+                c = regex.charAt(i);
+            }
+            else if (c == '^' || c == '$' || c == '*') {
+                throw new IllegalArgumentException("not a regex written by LikeFunctions.likePattern");
+            }
+            if (c == '%' || c == '_' || c == '\\') {
+                like.append('\\');
+            }
+            like.append(c);
+        }
+        return like.toString();
+    }
+
+    /**
+     * value IN (items) (SpecialForm.Form.IN, sql/gen/InCodeGenerator.java:92-121) -> TGPU_SF_IN over the constant items, laid out as
+     * consecutive CONST nodes named by (ival, slen) of the IN node.  Items that are not constants become "OR value = item", which is the
+     * same in three-valued logic.
+     */
+    private static int addIn(Program p, int type, List<RowExpression> arguments)
+    {
+        if (arguments.size() < 2) {
+            throw new IllegalArgumentException("IN without items");
+        }
+        int valueType = GpuPages.typeCode(arguments.get(0).getType());
+        int valueNode = add(p, arguments.get(0));
+        List<RowExpression> constants = new ArrayList<>();
+        List<RowExpression> others = new ArrayList<>();
+        for (RowExpression item : arguments.subList(1, arguments.size())) {
+            if (GpuPages.typeCode(item.getType()) != valueType) {
+                throw new IllegalArgumentException("IN item of another type");
+            }
+            (item instanceof ConstantExpression ? constants : others).add(item);
+        }
+        int[] otherNodes = others.stream().mapToInt(item -> add(p, item)).toArray();
+        int result = -1;
+        if (!constants.isEmpty()) {
+            int first = p.nodes.size();
+            for (RowExpression item : constants) {
+                add(p, item);   // one CONST node each: the list stays consecutive
+            }
+            result = emit(p, SPECIAL, type, SF_IN, new int[] {valueNode}, false, first, 0, constants.size());
+        }
+        for (int itemNode : otherNodes) {
+            int equal = emit(p, CALL, type, OP_EQUAL, new int[] {valueNode, itemNode}, false, 0, 0, 0);
+            result = result < 0 ? equal : emit(p, SPECIAL, type, SF_OR, new int[] {result, equal}, false, 0, 0, 0);
+        }
+        return result;
     }
 }

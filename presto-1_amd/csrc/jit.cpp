@@ -307,6 +307,88 @@ const char *ctype(int32_t t)
     }
 }
 
+// Device helpers of LIKE and IN.  They join the constants of a program that uses LIKE / IN and of no other: a program without them
+// generates the source it always did.  Several generators can feed one module, hence the include guard.
+const char *kLikeInHelpers = R"SRC(
+#ifndef TG_LIKE_IN_HELPERS
+#define TG_LIKE_IN_HELPERS
+// LIKE.  A pattern segment (what stands between two '%') is a token string: 0..255 = that byte, 256 = '_', one code point (a lead byte and
+// the 10xxxxxx bytes after it).  Every function reads inside [p, e) only; a match is reported as the address after it, a miss as 0.
+__device__ inline const unsigned char* tg_lk_skip(const unsigned char* p, const unsigned char* e, int n) {
+  for (int i = 0; i < n; i++) { if (p >= e) return 0; p++; while (p < e && (*p & 0xC0) == 0x80) p++; }
+  return p;
+}
+__device__ inline const unsigned char* tg_lk_match(const unsigned char* p, const unsigned char* e, const unsigned short* s, int n) {
+  for (int i = 0; i < n; i++) {
+    if (p >= e) return 0;
+    const unsigned t = s[i];
+    if (t == 256u) { p++; while (p < e && (*p & 0xC0) == 0x80) p++; }
+    else { if (*p != t) return 0; p++; }
+  }
+  return p;
+}
+// where a segment that ends at e begins, walking back over bytes and code points, never before b (0: it does not fit)
+__device__ inline const unsigned char* tg_lk_back(const unsigned char* b, const unsigned char* e, const unsigned short* s, int n) {
+  const unsigned char* p = e;
+  for (int i = n - 1; i >= 0; i--) {
+    if (p <= b) return 0;
+    p--;
+    if (s[i] == 256u) while (p > b && (*p & 0xC0) == 0x80) p--;
+  }
+  return p;
+}
+// leftmost match in [p, e); a segment that begins with '_' is tried at code-point boundaries only (n >= 1 tokens of >= 1 byte each)
+__device__ inline const unsigned char* tg_lk_find(const unsigned char* p, const unsigned char* e, const unsigned short* s, int n) {
+  for (; e - p >= n; p++) {
+    if (s[0] == 256u && (*p & 0xC0) == 0x80) continue;
+    const unsigned char* q = tg_lk_match(p, e, s, n);
+    if (q) return q;
+  }
+  return 0;
+}
+__device__ inline const unsigned char* tg_lk_find_lit(const unsigned char* p, const unsigned char* e, const unsigned char* k, int n) {
+  const unsigned char k0 = k[0];
+  for (; e - p >= n; p++) if (*p == k0 && tg_bytes_equal(p, k, n)) return p + n;
+  return 0;
+}
+// IN over a larger list: open addressing, linear probing, at most half full.  `empty` is a word that is no item of the list.
+__device__ inline unsigned long long tg_in_mix(unsigned long long x) { x ^= x >> 32; x *= 0x9E3779B97F4A7C15ULL; x ^= x >> 29; return x; }
+__device__ inline bool tg_in_probe(const unsigned long long* t, unsigned mask, unsigned long long empty, unsigned long long x) {
+  if (x == empty) return false;
+  for (unsigned h = (unsigned)tg_in_mix(x) & mask;; h = (h + 1) & mask) {
+    const unsigned long long y = t[h];
+    if (y == x) return true;
+    if (y == empty) return false;
+  }
+}
+// DoubleType.equalOperator: NaN equals nothing, the zeros equal each other (the table holds +0.0)
+__device__ inline bool tg_in_probe_double(const unsigned long long* t, unsigned mask, unsigned long long empty, double d) {
+  if (d != d) return false;
+  if (d == 0.0) d = 0.0;
+  return tg_in_probe(t, mask, empty, (unsigned long long)__double_as_longlong(d));
+}
+__device__ inline unsigned tg_in_hash_bytes(const unsigned char* p, int n) {
+  unsigned h = 2166136261u;
+  for (int i = 0; i < n; i++) { h ^= p[i]; h *= 16777619u; }
+  return h;
+}
+// slots of (hash, offset into pool, length); length 0xFFFFFFFF = empty
+__device__ inline bool tg_in_probe_str(const unsigned* t, const unsigned char* pool, unsigned mask, const unsigned char* p, int n) {
+  const unsigned hv = tg_in_hash_bytes(p, n);
+  for (unsigned h = hv & mask;; h = (h + 1) & mask) {
+    const unsigned len = t[3 * h + 2];
+    if (len == 0xFFFFFFFFu) return false;
+    if (t[3 * h] == hv && len == (unsigned)n && tg_bytes_equal(p, pool + t[3 * h + 1], n)) return true;
+  }
+}
+#endif
+)SRC";
+
+// IN lists up to this many distinct non-null items become a chain of comparisons against immediates, longer ones a hash table in the module
+constexpr int kInSmallList = 8;
+constexpr int kInMaxItems = 65536;
+constexpr int kLikeAnyOne = 256;   // the '_' token of a LIKE segment
+
 struct Val {
     std::string v, n, len;  // value var, null-flag var, (VARCHAR) length var
     int32_t type;
@@ -427,8 +509,8 @@ struct Gen {
             }
             return r;
         }
-        case TGPU_EX_CALL: return gen_call(nd, d);
-        case TGPU_EX_SPECIAL: return gen_special(nd, d);
+        case TGPU_EX_CALL: return nd.op == TGPU_OP_LIKE ? gen_like(nd, idx, d) : gen_call(nd, d);
+        case TGPU_EX_SPECIAL: return nd.op == TGPU_SF_IN ? gen_in(nd, idx, d) : gen_special(nd, d);
         default: bad("unknown node kind");
         }
     }
@@ -664,6 +746,318 @@ struct Gen {
         }
         default: bad("unknown special form");
         }
+    }
+
+    // ---- LIKE (M/type/LikeFunctions.java) and IN (M/sql/gen/InCodeGenerator.java) ----------------------------------------------
+    bool like_in_helpers = false;
+
+    void need_like_in_helpers()
+    {
+        if (!like_in_helpers) consts << kLikeInHelpers;
+        like_in_helpers = true;
+    }
+
+    // a constant array of the module, defined once however many generators of the module name it
+    void define_const(const std::string &name, const std::string &ctype_, const std::string &body, size_t count)
+    {
+        consts << "#ifndef TG_DEF_" << name << "\n#define TG_DEF_" << name << "\n__device__ const " << ctype_ << " " << name << "[" << (count ? count : 1) << "] = {"
+               << (count ? body : "0") << "};\n#endif\n";
+    }
+
+    // the bytes at p equal k, compared as 8- / 4- / 1-byte immediates; every piece lies inside [p, p + |k|) (see varchar_equals_const)
+    static std::string bytes_at(const std::string &p, const std::string &k)
+    {
+        const int L = (int)k.size();
+        if (L == 0) return "true";
+        auto imm = [&](int at, int w) {
+            unsigned long long v = 0;
+            for (int i = w - 1; i >= 0; i--) v = (v << 8) | (unsigned char)k[(size_t)(at + i)];
+            return std::to_string(v) + (w == 8 ? "ULL" : "U");
+        };
+        auto piece = [&](int at, int w) {
+            if (w == 1) return "(unsigned)(" + p + ")[" + std::to_string(at) + "] == " + imm(at, 1);
+            return std::string(w == 8 ? "tg_load8((" : "tg_load4((") + p + ") + " + std::to_string(at) + ") == " + imm(at, w);
+        };
+        std::string e = "(";
+        int i = 0;
+        auto add = [&](const std::string &s) { e += (e.size() > 1 ? " && " : "") + s; };
+        for (; L - i >= 8; i += 8) add(piece(i, 8));
+        if (i < L) {
+            if (L >= 8) add(piece(L - 8, 8));
+            else if (L >= 4) {
+                add(piece(0, 4));
+                if (L > 4) add(piece(L - 4, 4));
+            }
+            else
+                for (; i < L; i++) add(piece(i, 1));
+        }
+        return e + ")";
+    }
+
+    struct LikeSeg {
+        std::vector<int> tok;   // 0..255 a literal byte, kLikeAnyOne = '_'
+        bool pure() const { return std::find(tok.begin(), tok.end(), kLikeAnyOne) == tok.end(); }
+        std::string lit() const { return std::string(tok.begin(), tok.end()); }
+    };
+
+    // one code point of s at `at` (-> its byte length); a byte that starts no well-formed sequence stands for itself, outside the code space
+    static unsigned decode_utf8(const std::string &s, size_t at, int &len)
+    {
+        const unsigned char c = (unsigned char)s[at];
+        int n = c < 0x80 ? 1 : (c >> 5) == 6 ? 2 : (c >> 4) == 14 ? 3 : (c >> 3) == 30 ? 4 : 0;
+        if (n == 0 || at + (size_t)n > s.size()) { len = 1; return 0x80000000u | c; }
+        unsigned cp = n == 1 ? c : (unsigned)(c & (0xff >> (n + 1)));
+        for (int i = 1; i < n; i++) {
+            const unsigned char x = (unsigned char)s[at + (size_t)i];
+            if ((x & 0xC0) != 0x80) { len = 1; return 0x80000000u | c; }
+            cp = (cp << 6) | (x & 0x3F);
+        }
+        len = n;
+        return cp;
+    }
+
+    // LikeFunctions.likePattern (:198-241) over code points: the segments between the unescaped '%'.  The escape rules, their failures
+    // and their messages are the reference's (checkEscape :192-195, getEscapeChar :244-255; a character there is one UTF-16 unit, so an
+    // escape outside the BMP is "not a single character").
+    std::vector<LikeSeg> parse_like(const std::string &pat, bool has_escape, const std::string &escape)
+    {
+        static const char *kFollow = "Escape character must be followed by '%', '_' or the escape character itself";
+        unsigned esc = 0xFFFFu;   // getEscapeChar: the empty escape disables escaping ((char) -1)
+        if (has_escape && !escape.empty()) {
+            int n = 0;
+            esc = decode_utf8(escape, 0, n);
+            if ((size_t)n != escape.size() || esc > 0xFFFFu) fail(TGPU_ERR_INVALID_ARGUMENT, "Escape string must be a single character");
+        }
+        std::vector<LikeSeg> segs(1);
+        bool escaped = false;
+        for (size_t at = 0; at < pat.size();) {
+            int n = 0;
+            const unsigned cp = decode_utf8(pat, at, n);
+            if (escaped && !(cp == '%' || cp == '_' || cp == esc)) fail(TGPU_ERR_INVALID_ARGUMENT, kFollow);
+            if (has_escape && !escaped && cp == esc) escaped = true;
+            else {
+                if (cp == '%' && !escaped) segs.emplace_back();
+                else if (cp == '_' && !escaped) segs.back().tok.push_back(kLikeAnyOne);
+                else
+                    for (int i = 0; i < n; i++) segs.back().tok.push_back((unsigned char)pat[at + (size_t)i]);
+                escaped = false;
+            }
+            at += (size_t)n;
+        }
+        if (escaped) fail(TGPU_ERR_INVALID_ARGUMENT, kFollow);
+        return segs;
+    }
+
+    std::string const_text(const tgpu_expr_node &nd)
+    {
+        if (nd.ival < 0 || nd.slen < 0 || (size_t)(nd.ival + nd.slen) > pool.size()) bad("string constant outside the pool");
+        return pool.substr((size_t)nd.ival, (size_t)nd.slen);
+    }
+
+    // value LIKE pattern: one lane per row, the code specialised to the pattern's shape.  Head segment anchored at the start, tail segment at
+    // the end, every middle segment leftmost-first in what remains (exact for '%': a later '%' absorbs what an earlier match left over).
+    Val gen_like(const tgpu_expr_node &nd, int idx, int d)
+    {
+        if (nd.n_args < 2 || nd.n_args > 3 || nd.type != TGPU_BOOLEAN) bad("LIKE takes a value, a pattern and an optional escape");
+        const tgpu_expr_node &pn = node(nd.args[1]);
+        const tgpu_expr_node *en = nd.n_args == 3 ? &node(nd.args[2]) : nullptr;
+        if (pn.kind != TGPU_EX_CONST || pn.type != TGPU_VARCHAR || (en && (en->kind != TGPU_EX_CONST || en->type != TGPU_VARCHAR)))
+            fail(TGPU_ERR_NOT_SUPPORTED, "LIKE: the pattern and the escape must be VARCHAR constants");
+        Val r = declare(TGPU_BOOLEAN, d);
+        os << ind(d) << "{\n";
+        Val a = gen(nd.args[0], d + 1);
+        if (a.type != TGPU_VARCHAR) bad("LIKE needs a VARCHAR value");
+        if (pn.is_null || (en && en->is_null)) {
+            os << ind(d + 1) << r.n << " = true;\n" << ind(d) << "}\n";
+            return r;
+        }
+        std::vector<LikeSeg> segs = parse_like(const_text(pn), en != nullptr, en ? const_text(*en) : std::string());
+        const bool percent = segs.size() > 1;
+        const LikeSeg head = segs.front(), tail = percent ? segs.back() : LikeSeg();
+        std::vector<LikeSeg> middle;
+        for (size_t i = 1; i + 1 < segs.size(); i++)
+            if (!segs[i].tok.empty()) middle.push_back(segs[i]);
+        int tokens = 0, any_one = 0;
+        for (const LikeSeg &s : segs)
+            for (int t : s.tok) { tokens++; any_one += t == kLikeAnyOne; }
+        os << ind(d + 1) << "if (" << a.n << ") " << r.n << " = true; else {\n";
+        const int dd = d + 2;
+        const std::string end = "(" + a.v + " + " + a.len + ")";
+        if (!percent && head.pure()) os << ind(dd) << r.v << " = " << varchar_equals_const(a, head.lit()) << ";\n";   // no wildcard: equality
+        else if (tokens == 0) os << ind(dd) << r.v << " = true;\n";                                                    // '%', '%%': NOT NULL
+        else if (any_one == tokens) {                                                                                  // '_' and '%' only: a code-point count
+            need_like_in_helpers();
+            // the length test first: a value shorter than its code points is no match, and the address of an EMPTY value may be 0 (a pool
+            // of no bytes), which a miss reported as 0 must never be compared with
+            os << ind(dd) << r.v << " = " << a.len << " >= " << tokens << " && tg_lk_skip(" << a.v << ", " << end << ", " << tokens << ") " << (percent ? "!= 0" : "== " + end) << ";\n";
+        }
+        else if (middle.empty() && head.pure() && tail.pure()) {                                                       // lit%, %lit, lit%lit
+            os << ind(dd) << r.v << " = " << a.len << " >= " << tokens;
+            if (!head.tok.empty()) os << " && " << bytes_at(a.v, head.lit());
+            if (!tail.tok.empty()) os << " && " << bytes_at(a.v + " + " + a.len + " - " + std::to_string(tail.tok.size()), tail.lit());
+            os << ";\n";
+        }
+        else {
+            need_like_in_helpers();
+            const std::string id = std::to_string(tmp++), P = "p" + id + "_", E = "e" + id + "_", M = "m" + id + "_";
+            int part = 0;
+            auto seg_const = [&](const LikeSeg &s) {   // -> "name, count"
+                const std::string name = (s.pure() ? "LK" : "LS") + std::to_string(idx) + "_" + std::to_string(part++);
+                std::string body;
+                for (size_t i = 0; i < s.tok.size(); i++) body += (i ? "," : "") + std::to_string(s.tok[i]);
+                define_const(name, s.pure() ? "unsigned char" : "unsigned short", body, s.tok.size());
+                return name + ", " + std::to_string(s.tok.size());
+            };
+            // every token takes at least one byte: shorter values match nothing, and the literal pieces below stay inside the value
+            os << ind(dd) << "const unsigned char* " << P << " = " << a.v << "; const unsigned char* " << E << " = " << end << "; bool " << M << " = " << a.len << " >= " << tokens << ";\n";
+            if (!head.tok.empty()) {
+                if (head.pure()) os << ind(dd) << M << " = " << M << " && " << bytes_at(P, head.lit()) << "; " << P << " += " << head.tok.size() << ";\n";
+                else os << ind(dd) << "if (" << M << ") { " << P << " = tg_lk_match(" << P << ", " << E << ", " << seg_const(head) << "); " << M << " = " << P << " != 0; }\n";
+            }
+            if (!tail.tok.empty()) {
+                const std::string n = std::to_string(tail.tok.size());
+                if (tail.pure()) os << ind(dd) << M << " = " << M << " && " << E << " - " << P << " >= " << n << " && " << bytes_at(E + " - " + n, tail.lit()) << "; " << E << " -= " << n << ";\n";
+                else {
+                    const std::string sc = seg_const(tail);
+                    os << ind(dd) << "if (" << M << ") { const unsigned char* t_ = tg_lk_back(" << P << ", " << E << ", " << sc << "); " << M << " = t_ != 0 && tg_lk_match(t_, " << E << ", " << sc
+                       << ") == " << E << "; " << E << " = t_; }\n";
+                }
+            }
+            for (const LikeSeg &s : middle)
+                os << ind(dd) << "if (" << M << ") { " << P << " = " << (s.pure() ? "tg_lk_find_lit(" : "tg_lk_find(") << P << ", " << E << ", " << seg_const(s) << "); " << M << " = " << P << " != 0; }\n";
+            if (!percent) os << ind(dd) << M << " = " << M << " && " << P << " == " << E << ";\n";
+            os << ind(dd) << r.v << " = " << M << ";\n";
+        }
+        os << ind(d + 1) << "}\n";
+        os << ind(d) << "}\n";
+        return r;
+    }
+
+    static unsigned long long in_mix(unsigned long long x)   // tg_in_mix of the generated module
+    {
+        x ^= x >> 32;
+        x *= 0x9E3779B97F4A7C15ULL;
+        x ^= x >> 29;
+        return x;
+    }
+
+    static std::string hex64(unsigned long long v)
+    {
+        char b[32];
+        snprintf(b, sizeof(b), "0x%llxULL", v);
+        return b;
+    }
+
+    // value IN (constants): null items and duplicates dropped, then by list size a chain of comparisons against immediates or a
+    // hash table emitted as a constant array of the module
+    Val gen_in(const tgpu_expr_node &nd, int idx, int d)
+    {
+        TG_CHECK_ARG(nd.n_args == 1 && nd.type == TGPU_BOOLEAN, "IN takes one value and gives a boolean");
+        TG_CHECK_ARG(nd.slen >= 1, "IN: the list is empty");
+        if (nd.slen > kInMaxItems) fail(TGPU_ERR_NOT_SUPPORTED, "IN: more than 65536 items");
+        TG_CHECK_ARG(nd.ival >= 0 && nd.ival + nd.slen <= (int64_t)nodes.size(), "IN: the list lies outside the node array");
+        const int32_t t = node(nd.args[0]).type;
+        bool has_null = false;
+        std::vector<unsigned long long> words;   // fixed width: the canonical 64-bit pattern of every distinct non-null item, in list order
+        std::vector<std::string> strings;
+        std::set<unsigned long long> seen_words;
+        std::set<std::string> seen_strings;
+        for (int32_t i = 0; i < nd.slen; i++) {
+            const tgpu_expr_node &it = nodes[(size_t)nd.ival + (size_t)i];
+            TG_CHECK_ARG(it.kind == TGPU_EX_CONST, "IN: a list item is not a constant");
+            TG_CHECK_ARG(it.type == t, "IN: a list item is not of the value's type");
+            if (it.is_null) { has_null = true; continue; }
+            if (t == TGPU_VARCHAR) {
+                std::string s = const_text(it);
+                if (seen_strings.insert(s).second) strings.push_back(s);
+                continue;
+            }
+            unsigned long long w = 0;
+            if (t == TGPU_DOUBLE) {
+                double x = it.dval;
+                if (x != x) continue;        // NaN equals nothing
+                if (x == 0.0) x = 0.0;       // -0.0 == +0.0
+                memcpy(&w, &x, 8);
+            }
+            else if (t == TGPU_BIGINT) w = (unsigned long long)it.ival;
+            else if (t == TGPU_INTEGER || t == TGPU_DATE) w = (unsigned long long)(long long)(int32_t)it.ival;
+            else if (t == TGPU_BOOLEAN) w = it.ival != 0;
+            else bad("IN on an unsupported type");
+            if (seen_words.insert(w).second) words.push_back(w);
+        }
+        Val r = declare(TGPU_BOOLEAN, d);
+        os << ind(d) << "{\n";
+        Val v = gen(nd.args[0], d + 1);
+        if (v.type != t) bad("IN value type");
+        std::string found = "false";   // a list of null items only
+        const size_t count = t == TGPU_VARCHAR ? strings.size() : words.size();
+        if (count > 0 && count <= (size_t)kInSmallList) {
+            found.clear();
+            if (t == TGPU_VARCHAR) {
+                std::vector<size_t> lengths;   // switch on the length first: one length test per distinct length
+                for (const std::string &s : strings)
+                    if (std::find(lengths.begin(), lengths.end(), s.size()) == lengths.end()) lengths.push_back(s.size());
+                for (size_t L : lengths) {
+                    std::string alts;
+                    for (const std::string &s : strings)
+                        if (s.size() == L) alts += (alts.empty() ? "" : " || ") + bytes_at(v.v, s);
+                    found += (found.empty() ? "" : " || ") + ("(" + v.len + " == " + std::to_string(L) + " && (" + alts + "))");
+                }
+            }
+            else
+                for (unsigned long long w : words) {
+                    std::string c;
+                    if (t == TGPU_DOUBLE) { double x; memcpy(&x, &w, 8); c = fmt_double(x); }
+                    else if (t == TGPU_BOOLEAN) c = w ? "true" : "false";
+                    else c = std::string(t == TGPU_BIGINT ? "(long long)" : "(int)(long long)") + hex64(w);
+                    found += (found.empty() ? "" : " || ") + (v.v + " == " + c);
+                }
+        }
+        else if (count > 0) {
+            need_like_in_helpers();
+            size_t size = 16;
+            while (size < 2 * count) size *= 2;
+            const std::string T = "TI" + std::to_string(idx), mask = std::to_string(size - 1) + "u";
+            if (t == TGPU_VARCHAR) {
+                std::vector<unsigned> slots(size * 3, 0xFFFFFFFFu);
+                std::string bytes, body, pool_body;
+                for (const std::string &s : strings) {
+                    unsigned h = 2166136261u;   // tg_in_hash_bytes
+                    for (unsigned char c : s) { h ^= c; h *= 16777619u; }
+                    size_t at = h & (size - 1);
+                    while (slots[3 * at + 2] != 0xFFFFFFFFu) at = (at + 1) & (size - 1);
+                    slots[3 * at] = h;
+                    slots[3 * at + 1] = (unsigned)bytes.size();
+                    slots[3 * at + 2] = (unsigned)s.size();
+                    bytes += s;
+                }
+                for (size_t i = 0; i < slots.size(); i++) body += (i ? "," : "") + std::to_string(slots[i]) + "u";
+                for (size_t i = 0; i < bytes.size(); i++) pool_body += (i ? "," : "") + std::to_string((int)(unsigned char)bytes[i]);
+                define_const(T, "unsigned", body, slots.size());
+                define_const(T + "P", "unsigned char", pool_body, bytes.size());
+                found = "tg_in_probe_str(" + T + ", " + T + "P, " + mask + ", " + v.v + ", " + v.len + ")";
+            }
+            else {
+                unsigned long long empty = 0x8000000000000001ULL;   // a word that is no item
+                while (seen_words.count(empty)) empty++;
+                std::vector<unsigned long long> slots(size, empty);
+                for (unsigned long long w : words) {
+                    size_t at = (unsigned)in_mix(w) & (size - 1);
+                    while (slots[at] != empty) at = (at + 1) & (size - 1);
+                    slots[at] = w;
+                }
+                std::string body;
+                for (size_t i = 0; i < size; i++) body += (i ? "," : "") + hex64(slots[i]);
+                define_const(T, "unsigned long long", body, size);
+                if (t == TGPU_DOUBLE) found = "tg_in_probe_double(" + T + ", " + mask + ", " + hex64(empty) + ", " + v.v + ")";
+                else found = "tg_in_probe(" + T + ", " + mask + ", " + hex64(empty) + ", (unsigned long long)(long long)" + v.v + ")";
+            }
+        }
+        os << ind(d + 1) << "if (" << v.n << ") " << r.n << " = true;\n";
+        if (has_null) os << ind(d + 1) << "else if (" << found << ") " << r.v << " = true; else " << r.n << " = true;\n";
+        else os << ind(d + 1) << "else " << r.v << " = " << found << ";\n";
+        os << ind(d) << "}\n";
+        return r;
     }
 
     void assign(const Val &dst, const Val &src, int d)
@@ -3048,9 +3442,10 @@ void FusedAggGpu::generate()
             // without nulls in the page the count of an unmasked aggregate over a never-null expression IS the row count: static
             const bool static_rows = !cnt_masked_[(size_t)cs] && !(cnt_inputs_[(size_t)cs].size() == 1 && cnt_inputs_[(size_t)cs][0] < 0);
             const std::string cfr = "(FA_NO_NULLS ? " + std::string(static_rows ? "1" : "0") + " : F.plan.count_from_rows[" + std::to_string(k) + "])";
-            lc_read << "  unsigned int c" << cs << " = 0; if (!" << cfr << ") c" << cs << " = cnt_base[" << cs << " * 256 + threadIdx.x];\n";
-            lc_upd << "  c" << cs << " += t" << k << " ? 1u : 0u;\n";
-            lc_write << "  if (!" << cfr << ") cnt_base[" << cs << " * 256 + threadIdx.x] = c" << cs << ";\n";
+            // (@CNT@: the count's name, settled below once it is known which columns the expressions read from memory)
+            lc_read << "  unsigned int @CNT@" << cs << " = 0; if (!" << cfr << ") @CNT@" << cs << " = cnt_base[" << cs << " * 256 + threadIdx.x];\n";
+            lc_upd << "  @CNT@" << cs << " += t" << k << " ? 1u : 0u;\n";
+            lc_write << "  if (!" << cfr << ") cnt_base[" << cs << " * 256 + threadIdx.x] = @CNT@" << cs << ";\n";
         }
         if (is_mm) lc_upd << "  if (t" << k << ") tg_minmax_update(" << mm_word << ", " << mm_code << ");\n";
         if (is_dbl && first_wide) {
@@ -3509,11 +3904,18 @@ extern "C" __global__ void __launch_bounds__(256) fg_probe(FgArgs G) {
     std::string kernels = kFaKernels;
     const size_t split = kernels.find("#define FA_STRIPES");
     src << kernels.substr(0, split);
+    // the lane-private counts are c<slot>; a column the expressions read from memory (VARCHAR) owns the name c<channel>, so with such columns
+    // the counts are k<slot> (programs without them keep the source they always had)
+    auto cnt_named = [&](std::string t) {
+        const std::string name = gr.used_cols.empty() ? "c" : "k";
+        for (size_t at; (at = t.find("@CNT@")) != std::string::npos;) t.replace(at, 5, name);
+        return t;
+    };
     src << "template <bool PENDING> __device__ inline void tg_accumulate_row_lc(const FaArgs& F, const FpArgs& A, long long row, const TgRow& R, int g, unsigned char* lds, bool& spilled_) {\n"
         << cols_decl(gr)
         << "  double* hi_base = tg_lc_hi(lds, F.plan, g); double* lo_base = tg_lc_lo(lds, F.plan, g);\n"
         << "  unsigned int* cnt_base = tg_lc_cnt(lds, F.plan, g);\n  (void)hi_base; (void)lo_base; (void)row; (void)spilled_;\n"
-        << eval_all << lc_read.str() << "  unsigned int rows_ = cnt_base[" << rows_slot_ << " * 256 + threadIdx.x];\n" << lc_upd.str() << "  rows_ += 1u;\n" << lc_write.str()
+        << eval_all << cnt_named(lc_read.str()) << "  unsigned int rows_ = cnt_base[" << rows_slot_ << " * 256 + threadIdx.x];\n" << cnt_named(lc_upd.str()) << "  rows_ += 1u;\n" << cnt_named(lc_write.str())
         << "  cnt_base[" << rows_slot_ << " * 256 + threadIdx.x] = rows_;\n}\n";
     src << "__device__ inline void tg_accumulate_row_gl(const FaArgs& F, const FpArgs& A, long long row, const TgRow& R, int g) {\n" << cols_decl(gr) << "  (void)row;\n"
         << eval_all << gl.str() << "}\n";

@@ -11,8 +11,8 @@ from .spi import BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR
 
 EX_INPUT, EX_CONST, EX_CALL, EX_SPECIAL = 0, 1, 2, 3
 OPS = {"ADD": 1, "SUBTRACT": 2, "MULTIPLY": 3, "DIVIDE": 4, "MODULUS": 5, "NEGATE": 6, "EQUAL": 7, "NOT_EQUAL": 8,
-       "LESS_THAN": 9, "LESS_THAN_OR_EQUAL": 10, "GREATER_THAN": 11, "GREATER_THAN_OR_EQUAL": 12, "NOT": 13, "CAST": 14}
-FORMS = {"AND": 1, "OR": 2, "IF": 3, "IS_NULL": 4, "COALESCE": 5, "BETWEEN": 6}
+       "LESS_THAN": 9, "LESS_THAN_OR_EQUAL": 10, "GREATER_THAN": 11, "GREATER_THAN_OR_EQUAL": 12, "NOT": 13, "CAST": 14, "LIKE": 15}
+FORMS = {"AND": 1, "OR": 2, "IF": 3, "IS_NULL": 4, "COALESCE": 5, "BETWEEN": 6, "IN": 7}
 _CMP = {"EQUAL", "NOT_EQUAL", "LESS_THAN", "LESS_THAN_OR_EQUAL", "GREATER_THAN", "GREATER_THAN_OR_EQUAL"}
 
 
@@ -51,9 +51,10 @@ class CallExpression(RowExpression):
 
 
 class SpecialForm(RowExpression):
-    def __init__(self, form, type_id, arguments):
+    def __init__(self, form, type_id, arguments, items=None):
         assert form in FORMS, form
         self.form, self.type, self.arguments = form, type_id, list(arguments)
+        self.items = None if items is None else list(items)   # IN: the list, constants of the value's type
 
 
 def _wrap(v, type_id):
@@ -80,6 +81,19 @@ def if_(c, t, f): return SpecialForm("IF", t.type, [c, t, f])
 def coalesce(*args): return SpecialForm("COALESCE", args[0].type, list(args))
 def between(v, lo, hi): return SpecialForm("BETWEEN", BOOLEAN, [v, _wrap(lo, v.type), _wrap(hi, v.type)])
 def cast(a, type_id): return call("CAST", type_id, a)
+
+
+def like(value, pattern, escape=None):
+    """value LIKE pattern [ESCAPE escape]; pattern / escape: a str (None = the null literal) or a VARCHAR expression, which must be a constant"""
+    args = [value, _wrap(pattern, VARCHAR)]
+    if escape is not None:
+        args.append(_wrap(escape, VARCHAR))
+    return call("LIKE", BOOLEAN, *args)
+
+
+def in_(value, items):
+    """value IN (items); an item is a Python value (None = the null literal) or a constant of the value's type"""
+    return SpecialForm("IN", BOOLEAN, [value], [_wrap(i, value.type) for i in items])
 
 
 class FlatProgram:
@@ -112,6 +126,11 @@ class FlatProgram:
             args = [self._add(a) for a in e.arguments]
             assert len(args) <= 3, "special forms take at most 3 arguments here"
             nd = dict(kind=EX_SPECIAL, type=e.type, op=FORMS[e.form], args=args)
+            if e.items is not None:
+                # the list: consecutive constant nodes (nothing else is added in between), named by (ival, slen) of the IN node
+                nd["ival"], nd["slen"] = len(self.nodes), len(e.items)
+                for item in e.items:
+                    self._add(item)
         else:
             raise TypeError(e)
         self.nodes.append(nd)
