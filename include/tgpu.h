@@ -175,7 +175,56 @@ typedef enum tgpu_expr_op {
      * "Escape string must be a single character", an escape character followed by anything else (or ending the pattern) with "Escape character
      * must be followed by '%', '_' or the escape character itself": both TGPU_ERR_INVALID_ARGUMENT when the factory is created.  A null value,
      * pattern or escape gives NULL.  LIKE raises no per-row error. */
-    TGPU_OP_LIKE = 15
+    TGPU_OP_LIKE = 15,
+    /* String functions (M/operator/scalar/StringFunctions.java, ConcatFunction.java) and CAST(... AS VARCHAR).
+     *
+     * Arguments and nulls.  Every argument is an ordinary expression, not only a constant, and the usual call convention holds: the first null
+     * argument gives NULL and the arguments after it are not evaluated.
+     *
+     * Code-point rule.  A code point starts at every byte b with (b & 0xC0) != 0x80.  LENGTH counts those bytes; SUBSTR counts its positions in
+     * them, and its result begins at such a byte and ends in front of one or at the end of the value (bytes in front of the value's first start
+     * byte belong to no code point).  On well-formed UTF-8 that is the reference's result.  On malformed bytes the reference's result depends on
+     * airlift's SliceUtf8: parity unpinned; the library guarantees the rule above and that no byte outside the value is read.
+     *
+     *   TGPU_OP_LENGTH       (VARCHAR) -> BIGINT                    length :94-100: the number of code points.
+     *   TGPU_OP_SUBSTR       (VARCHAR, BIGINT start [, BIGINT length]) -> VARCHAR     substring :274-309 and :321-367.  start and length are
+     *                        saturated to int32 (Ints.saturatedCast).  start == 0, length <= 0 and an empty value each give ''.  start > 0 counts
+     *                        from the front (1 = the first code point), a start past the end gives ''.  start < 0 counts from the end (-1 = the
+     *                        last code point), a start before the beginning gives ''.  A length that reaches past the end gives the suffix.
+     *                        Deviation: the reference's negative-start branch adds two ints (startCodePoint + lengthCodePoints, :359); for
+     *                        lengths near 2^31 that add overflows and the reference ends in an internal IndexOutOfBoundsException.  The library
+     *                        returns the suffix there.
+     *   TGPU_OP_CONCAT       (VARCHAR, VARCHAR) -> VARCHAR          ConcatFunction.java (n-ary there; the builders nest it left to right).  A
+     *                        result row longer than 2^31 - 1 bytes fails with TGPU_ERR_INVALID_ARGUMENT, "Concatenated string is too large"
+     *                        (the reference's INVALID_FUNCTION_ARGUMENT), at the first such row.
+     *   TGPU_OP_STRPOS       (VARCHAR, VARCHAR substring) -> BIGINT stringPosition :205-247, the two-argument form only.  A byte search
+     *                        (Slice.indexOf); the result is the 1-based code-point index of the first match, 0 when the substring is absent,
+     *                        1 for an empty substring.  The three-argument form (instance) is not part of the IR.
+     *   TGPU_OP_STARTS_WITH  (VARCHAR, VARCHAR prefix) -> BOOLEAN   startsWith :909-915: the value's first bytes equal the prefix.
+     *
+     * TGPU_OP_CAST with a VARCHAR result: from BIGINT and INTEGER the decimal digits of String.valueOf (BigintOperators.java:198-205,
+     * IntegerOperators.java:170), from BOOLEAN 'true' / 'false' (BooleanOperators.java:82), from VARCHAR the value itself.  VARCHAR is the
+     * unbounded varchar: the IR has no length parameter, so the varchar(x) overflow checks of those casts do not arise.  Casts from DOUBLE and
+     * DATE to VARCHAR are not supported (TGPU_ERR_COMPILER).
+     *
+     * IF and COALESCE accept VARCHAR operands and give a VARCHAR result.
+     *
+     * Views and built values.  A VARCHAR expression is a view -- (pointer, length) into an input block or a constant: INPUT, CONST, SUBSTR of a
+     * view, CAST(boolean), IF / COALESCE over views -- or a built value, a list of up to 32 pieces that exists only while a row is evaluated:
+     * CONCAT, CAST(BIGINT / INTEGER AS VARCHAR), IF / COALESCE with a built branch.  Views feed every consumer.  Built values feed a
+     * projection root, CONCAT, LENGTH, IF / COALESCE branches and IS_NULL; under a comparison, BETWEEN, LIKE, IN, SUBSTR, STRPOS or
+     * STARTS_WITH, and with more than 32 pieces, the factory fails with TGPU_ERR_NOT_SUPPORTED naming the consumer.
+     *
+     * Computed VARCHAR projections: at most 8 per page processor ("too many computed VARCHAR projections", TGPU_ERR_COMPILER).  An output
+     * column of more than 2^31 - 1 bytes fails with TGPU_ERR_INSUFFICIENT_RESOURCES, "variable width block cannot exceed 2GB".
+     *
+     * Out of scope: lower / upper (Java's case tables), trim / ltrim / rtrim (airlift's whitespace set), replace, reverse, lpad / rpad and
+     * CHAR(n). */
+    TGPU_OP_LENGTH = 16,
+    TGPU_OP_SUBSTR = 17,
+    TGPU_OP_CONCAT = 18,
+    TGPU_OP_STRPOS = 19,
+    TGPU_OP_STARTS_WITH = 20
 } tgpu_expr_op;
 typedef enum tgpu_special_form { /* M/sql/relational/SpecialForm.java:137-152 */
     TGPU_SF_AND = 1, TGPU_SF_OR, TGPU_SF_IF, TGPU_SF_IS_NULL, TGPU_SF_COALESCE, TGPU_SF_BETWEEN,

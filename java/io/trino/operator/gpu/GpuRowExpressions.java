@@ -2,6 +2,7 @@ package io.trino.operator.gpu;
 
 import io.airlift.slice.Slice;
 import io.trino.spi.type.Type;
+import io.trino.spi.type.VarcharType;
 import io.trino.sql.relational.CallExpression;
 import io.trino.sql.relational.ConstantExpression;
 import io.trino.sql.relational.InputReferenceExpression;
@@ -29,6 +30,10 @@ public final class GpuRowExpressions
             "$operator$CAST"};
     private static final int OP_EQUAL = 7, OP_LIKE = 15, SF_OR = 2, SF_IN = 7;   // TGPU_OP_EQUAL, TGPU_OP_LIKE, TGPU_SF_OR, TGPU_SF_IN
     private static final String LIKE_FUNCTION_NAME = "like";                    // LikeFunctions.likeVarchar (type/LikeFunctions.java:71-74)
+    // TGPU_OP_LENGTH .. TGPU_OP_STARTS_WITH: operator/scalar/StringFunctions.java (length :94, strpos :205, substring / alias substr :274 and
+    // :321, starts_with :909) and operator/scalar/ConcatFunction.java ("concat"), over varchar arguments
+    private static final int OP_CAST = 14, OP_LENGTH = 16, OP_SUBSTR = 17, OP_CONCAT = 18, OP_STRPOS = 19, OP_STARTS_WITH = 20;
+    private static final String CAST_OPERATOR = "$operator$CAST";
 
     public static final class Program
     {
@@ -109,6 +114,13 @@ public final class GpuRowExpressions
         if (e instanceof CallExpression) {
             CallExpression call = (CallExpression) e;
             String name = call.getResolvedFunction().getSignature().getName();
+            if (CAST_OPERATOR.equalsIgnoreCase(name) && call.getType() instanceof VarcharType) {
+                return addCastToVarchar(p, type, call);
+            }
+            int stringOp = stringFunction(name, call.getArguments().size());
+            if (stringOp != 0) {
+                return addStringFunction(p, type, stringOp, call.getArguments());
+            }
             for (int op = 1; op < OPERATORS.length; op++) {
                 if (OPERATORS[op].equalsIgnoreCase(name)) {
                     int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
@@ -143,6 +155,60 @@ public final class GpuRowExpressions
             return emit(p, SPECIAL, type, op, args, false, 0, 0, 0);
         }
         throw new IllegalArgumentException("expression not in the GPU IR: " + e);
+    }
+
+    private static int stringFunction(String name, int arguments)
+    {
+        switch (name.toLowerCase(java.util.Locale.ENGLISH)) {
+            case "length": return arguments == 1 ? OP_LENGTH : 0;
+            case "substr":
+            case "substring": return arguments == 2 || arguments == 3 ? OP_SUBSTR : 0;
+            case "concat": return arguments >= 2 ? OP_CONCAT : 0;
+            case "strpos": return arguments == 2 ? OP_STRPOS : 0;   // the three-argument form (instance) is not in the IR
+            case "starts_with": return arguments == 2 ? OP_STARTS_WITH : 0;
+            default: return 0;
+        }
+    }
+
+    /**
+     * length / substr / concat / strpos / starts_with over varchar -> TGPU_OP_LENGTH .. TGPU_OP_STARTS_WITH.  The same names exist over
+     * char(x), varbinary and arrays: those are outside the IR.  concat(a, b, c, ...) is folded to the left, as the IR's CONCAT takes two.
+     */
+    private static int addStringFunction(Program p, int type, int op, List<RowExpression> arguments)
+    {
+        int strings = op == OP_LENGTH || op == OP_SUBSTR ? 1 : arguments.size();
+        for (int i = 0; i < strings; i++) {
+            if (!(arguments.get(i).getType() instanceof VarcharType)) {
+                throw new IllegalArgumentException("string function over a type that is not varchar");
+            }
+        }
+        int[] args = arguments.stream().mapToInt(a -> add(p, a)).toArray();
+        if (op != OP_CONCAT) {
+            return emit(p, CALL, type, op, args, false, 0, 0, 0);
+        }
+        int result = args[0];
+        for (int i = 1; i < args.length; i++) {
+            result = emit(p, CALL, type, OP_CONCAT, new int[] {result, args[i]}, false, 0, 0, 0);
+        }
+        return result;
+    }
+
+    /**
+     * CAST(x AS varchar) from bigint / integer (String.valueOf), boolean and varchar.  The IR's VARCHAR has no length: a bounded varchar(n)
+     * target, whose cast checks the length, is refused.
+     */
+    private static int addCastToVarchar(Program p, int type, CallExpression call)
+    {
+        if (!((VarcharType) call.getType()).isUnbounded()) {
+            throw new IllegalArgumentException("CAST to a bounded varchar(n) is not in the GPU IR");
+        }
+        RowExpression argument = call.getArguments().get(0);
+        String from = argument.getType().getTypeSignature().getBase();
+        boolean unboundedVarchar = argument.getType() instanceof VarcharType && ((VarcharType) argument.getType()).isUnbounded();
+        if (!(from.equals("bigint") || from.equals("integer") || from.equals("boolean") || unboundedVarchar)) {
+            throw new IllegalArgumentException("CAST to varchar from " + from + " is not in the GPU IR");
+        }
+        return emit(p, CALL, type, OP_CAST, new int[] {add(p, argument)}, false, 0, 0, 0);
     }
 
     private static int addStringConstant(Program p, int type, byte[] bytes)

@@ -394,7 +394,106 @@ struct Val {
     int32_t type;
     bool is_const = false;  // a non-null VARCHAR constant: its bytes are known when the kernel is generated (cmp_expr)
     std::string bytes;
+    // A built VARCHAR value (CONCAT, CAST(integer AS VARCHAR)) has no backing memory: it is an ordered list of pieces, each a view
+    // (p != 0: len bytes at p) or the len decimal characters of the integer iv (p == 0); len = the byte length of the whole value, v is unused.
+    struct Piece { std::string p, iv, len; };
+    std::vector<Piece> pieces;
+    bool built() const { return !pieces.empty(); }
 };
+
+constexpr int kMaxPieces = 32;     // pieces of one built VARCHAR value
+
+// Device helpers of the string functions and of the variable-width writer; they join the constants of a program that uses them and of no other.
+const char *kStringHelpers = R"SRC(
+#ifndef TG_STRING_HELPERS
+#define TG_STRING_HELPERS
+__device__ const unsigned char TG_STR_TRUE[4] = {'t','r','u','e'};
+__device__ const unsigned char TG_STR_FALSE[5] = {'f','a','l','s','e'};
+// the bytes of a word that start no code point (10xxxxxx), as their top bits
+__device__ inline unsigned long long tg_cont8(unsigned long long w) { return w & ~(w << 1) & 0x8080808080808080ULL; }
+// code points of [p, p + n): 8 bytes at a time, then a byte tail; reads inside [p, p + n) only
+__device__ inline long long tg_cp_count(const unsigned char* p, int n) {
+  long long c = 0;
+  int i = 0;
+  for (; i + 8 <= n; i += 8) c += 8 - __popcll(tg_cont8(tg_load8(p + i)));
+  for (; i < n; i++) c += (p[i] & 0xC0) != 0x80;
+  return c;
+}
+// offset of the k-th (from 0) code-point start at or after `from`, n when [from, n) holds no more than k of them; it scans no further
+__device__ inline int tg_cp_offset(const unsigned char* p, int n, int from, long long k) {
+  int i = from;
+  for (; i + 8 <= n; i += 8) {
+    const int c = 8 - __popcll(tg_cont8(tg_load8(p + i)));
+    if (k < c) break;
+    k -= c;
+  }
+  for (; i < n; i++) if ((p[i] & 0xC0) != 0x80 && k-- == 0) return i;
+  return n;
+}
+// Slice.indexOf: the first byte offset at which [k, k + m) stands in [p, p + n), -1 if nowhere (m >= 1)
+__device__ inline int tg_str_find(const unsigned char* p, int n, const unsigned char* k, int m) {
+  const unsigned char k0 = k[0];
+  for (int i = 0; i + m <= n; i++) if (p[i] == k0 && tg_bytes_equal(p + i, k, m)) return i;
+  return -1;
+}
+// characters of String.valueOf(v)
+__device__ inline int tg_digits(long long v) {
+  unsigned long long u = v < 0 ? 0ULL - (unsigned long long)v : (unsigned long long)v, p = 10;
+  int c = 1;
+  while (c < 19 && u >= p) { c++; p *= 10; }
+  return c + (v < 0);
+}
+__device__ inline void tg_vw_digits(unsigned char* dst, long long v, int len) {
+  unsigned long long u = v < 0 ? 0ULL - (unsigned long long)v : (unsigned long long)v;
+  for (int i = len - 1; i >= (v < 0); i--) { dst[i] = (unsigned char)('0' + (int)(u % 10)); u /= 10; }
+  if (v < 0) dst[0] = '-';
+}
+__device__ inline void tg_store8(unsigned char* p, unsigned long long v) { __builtin_memcpy(p, &v, 8); }
+__device__ inline void tg_store4(unsigned char* p, unsigned int v) { __builtin_memcpy(p, &v, 4); }
+// One lane copies a row of its own in 8- / 4- / 1-byte pieces.  The neighbouring rows of the pool belong to the neighbouring lanes, so no
+// piece may leave [dst, dst + n) (nor [src, src + n)): a last piece that is not a whole one overlaps its predecessor, as in tg_bytes_equal.
+__device__ inline void tg_vw_copy_lane(unsigned char* dst, const unsigned char* src, int n) {
+  if (n >= 8) {
+    for (int i = 0; i + 8 <= n; i += 8) tg_store8(dst + i, tg_load8(src + i));
+    if (n & 7) tg_store8(dst + n - 8, tg_load8(src + n - 8));
+  }
+  else if (n >= 4) { tg_store4(dst, tg_load4(src)); tg_store4(dst + n - 4, tg_load4(src + n - 4)); }
+  else for (int i = 0; i < n; i++) dst[i] = src[i];
+}
+struct TgB16 { unsigned int w[4]; };
+// The whole wave copies one row: lane i takes bytes [16 i, 16 i + 16) of every 1 KiB step, the last n % 16 bytes go one per lane.
+__device__ inline void tg_vw_copy_wave(unsigned char* dst, const unsigned char* src, int n, int lane) {
+  const int whole = n & ~15;
+  for (int i = lane * 16; i < whole; i += 1024) { TgB16 v; __builtin_memcpy(&v, src + i, 16); __builtin_memcpy(dst + i, &v, 16); }
+  if (whole + lane < n) dst[whole + lane] = src[whole + lane];
+}
+// One piece of one output row per lane; every lane of the wave calls it (act = the lane has a piece to write).  View pieces of
+// TG_VW_COOP_MIN bytes or more are copied by the whole wave, one after the other; the rest by their own lane.
+__device__ inline void tg_vw_piece(unsigned char* dst, const unsigned char* p, long long iv, int len, bool act) {
+  act = act && len > 0;
+  const bool coop = act && p != 0 && (long long)len >= TG_VW_COOP_MIN;
+  if (act && !coop) { if (p) tg_vw_copy_lane(dst, p, len); else tg_vw_digits(dst, iv, len); }
+  unsigned long long m = __ballot(coop);
+  const int lane = threadIdx.x & 63;
+  while (m) {
+    const int l = __ffsll((long long)m) - 1;
+    m &= m - 1;
+    const unsigned long long s = __shfl((unsigned long long)p, l, 64), t = __shfl((unsigned long long)dst, l, 64);
+    tg_vw_copy_wave((unsigned char*)t, (const unsigned char*)s, __shfl(len, l, 64), lane);
+  }
+}
+#endif
+)SRC";
+
+// rows at or above this many bytes are copied wave-cooperatively by fp_vwrite (TGPU_VW_COOP_MIN)
+constexpr long long kVwCoopMinDefault = 64;    // the sweep of tools/exp_varchar_project.py: fastest on 40-200-byte rows, and 15-byte rows stay with their lanes
+long long vw_coop_min()
+{
+    const char *v = getenv("TGPU_VW_COOP_MIN");
+    if (!v || !*v) return kVwCoopMinDefault;
+    const long long x = atoll(v);
+    return x < 0 ? 0 : x;
+}
 
 struct Gen {
     const std::vector<tgpu_expr_node> &nodes;
@@ -496,10 +595,13 @@ struct Gen {
             case TGPU_VARCHAR: {
                 if (nd.ival < 0 || nd.slen < 0 || (size_t)(nd.ival + nd.slen) > pool.size()) bad("string constant outside the pool");
                 std::string name = "K" + std::to_string(idx);
-                consts << "__device__ const unsigned char " << name << "[" << (nd.slen > 0 ? nd.slen : 1) << "] = {";
-                for (int i = 0; i < nd.slen; i++) consts << (i ? "," : "") << (int)(unsigned char)pool[(size_t)nd.ival + i];
-                if (nd.slen == 0) consts << "0";
-                consts << "};\n";
+                if (defined_consts.insert(idx).second) {
+                    // defined once, whichever generator of the module names it first (and the write pass of a VARCHAR projection generates
+                    // its expression a second time)
+                    std::string body;
+                    for (int i = 0; i < nd.slen; i++) body += (i ? "," : "") + std::to_string((int)(unsigned char)pool[(size_t)nd.ival + i]);
+                    define_const(name, "unsigned char", body, (size_t)nd.slen);
+                }
                 os << ind(d) << r.v << " = " << name << "; " << r.len << " = " << nd.slen << ";\n";
                 r.is_const = true;
                 r.bytes = pool.substr((size_t)nd.ival, (size_t)nd.slen);
@@ -509,10 +611,169 @@ struct Gen {
             }
             return r;
         }
-        case TGPU_EX_CALL: return nd.op == TGPU_OP_LIKE ? gen_like(nd, idx, d) : gen_call(nd, d);
-        case TGPU_EX_SPECIAL: return nd.op == TGPU_SF_IN ? gen_in(nd, idx, d) : gen_special(nd, d);
+        case TGPU_EX_CALL:
+            if (nd.op == TGPU_OP_LIKE) return gen_like(nd, idx, d);
+            if ((nd.op >= TGPU_OP_LENGTH && nd.op <= TGPU_OP_STARTS_WITH) || (nd.op == TGPU_OP_CAST && nd.type == TGPU_VARCHAR)) return gen_string(nd, idx, d);
+            return gen_call(nd, d);
+        case TGPU_EX_SPECIAL: return nd.op == TGPU_SF_IN ? gen_in(nd, idx, d) : gen_special(nd, idx, d);
         default: bad("unknown node kind");
         }
+    }
+
+    // ---- string functions (M/operator/scalar/StringFunctions.java, ConcatFunction.java) and CAST(... AS VARCHAR) ------------------
+    bool string_helpers = false;
+    std::set<int> defined_consts;
+
+    void need_string_helpers()
+    {
+        if (!string_helpers) consts << "#ifndef TG_VW_COOP_MIN\n#define TG_VW_COOP_MIN " << vw_coop_min() << "LL\n#endif\n" << kStringHelpers;
+        string_helpers = true;
+    }
+
+    // pieces of the VARCHAR value node idx gives: 0 = a view, else a built value.  The tree is static, so this is known before any code is emitted.
+    int piece_count(int idx)
+    {
+        const tgpu_expr_node &nd = node(idx);
+        if (nd.type != TGPU_VARCHAR) return 0;
+        auto arg = [&](int k) { return piece_count(nd.args[k]); };
+        if (nd.kind == TGPU_EX_CALL && nd.op == TGPU_OP_CONCAT && nd.n_args == 2) return std::min(std::max(1, arg(0)) + std::max(1, arg(1)), kMaxPieces + 1);
+        if (nd.kind == TGPU_EX_CALL && nd.op == TGPU_OP_CAST && nd.n_args == 1) {
+            const int32_t from = node(nd.args[0]).type;
+            return from == TGPU_BIGINT || from == TGPU_INTEGER ? 1 : from == TGPU_VARCHAR ? arg(0) : 0;
+        }
+        if (nd.kind == TGPU_EX_SPECIAL && (nd.op == TGPU_SF_COALESCE || (nd.op == TGPU_SF_IF && nd.n_args == 3))) {
+            int m = 0;
+            for (int k = nd.op == TGPU_SF_IF ? 1 : 0; k < nd.n_args && k < 3; k++) m = std::max(m, arg(k));
+            return m;
+        }
+        return 0;
+    }
+
+    // the result variables of node idx: a built value's pieces when it is one
+    Val declare_result(int idx, int32_t type, int d)
+    {
+        const int np = type == TGPU_VARCHAR ? piece_count(idx) : 0;
+        if (np == 0) return declare(type, d);
+        if (np > kMaxPieces) fail(TGPU_ERR_NOT_SUPPORTED, "a VARCHAR value of more than " + std::to_string(kMaxPieces) + " pieces (nested CONCAT / CAST AS VARCHAR)");
+        Val r;
+        r.type = TGPU_VARCHAR;
+        const std::string k = std::to_string(tmp++);
+        r.n = "n" + k;
+        r.len = "l" + k;
+        os << ind(d) << "int " << r.len << " = 0; bool " << r.n << " = false;\n";
+        for (int i = 0; i < np; i++) {
+            const std::string s = k + "_" + std::to_string(i);
+            r.pieces.push_back({"p" + s, "i" + s, "l" + s});
+            os << ind(d) << "const unsigned char* p" << s << " = 0; long long i" << s << " = 0; int l" << s << " = 0;\n";
+        }
+        return r;
+    }
+
+    static std::vector<Val::Piece> pieces_of(const Val &v) { return v.built() ? v.pieces : std::vector<Val::Piece>{{v.v, "0", v.len}}; }
+
+    void set_pieces(const Val &dst, const std::vector<Val::Piece> &src, int d)
+    {
+        if (src.size() > dst.pieces.size()) bad("built VARCHAR value: piece count");
+        for (size_t i = 0; i < dst.pieces.size(); i++) {
+            const Val::Piece &p = dst.pieces[i];
+            if (i < src.size()) os << ind(d) << p.p << " = " << src[i].p << "; " << p.iv << " = " << src[i].iv << "; " << p.len << " = " << src[i].len << ";\n";
+            else os << ind(d) << p.p << " = 0; " << p.len << " = 0;\n";   // shorter branches are padded with empty pieces
+        }
+    }
+
+    void no_built(const Val &v, const char *who)
+    {
+        if (v.built())
+            fail(TGPU_ERR_NOT_SUPPORTED, std::string(who) + " over a built VARCHAR value (CONCAT, CAST AS VARCHAR): only a projection, CONCAT, LENGTH, IF, COALESCE and IS_NULL take one");
+    }
+
+    Val gen_string(const tgpu_expr_node &nd, int idx, int d)
+    {
+        const char *name = nd.op == TGPU_OP_LENGTH ? "LENGTH" : nd.op == TGPU_OP_SUBSTR ? "SUBSTR" : nd.op == TGPU_OP_CONCAT ? "CONCAT" :
+                           nd.op == TGPU_OP_STRPOS ? "STRPOS" : nd.op == TGPU_OP_STARTS_WITH ? "STARTS_WITH" : "CAST";
+        const bool one = nd.op == TGPU_OP_LENGTH || nd.op == TGPU_OP_CAST;
+        if (nd.op == TGPU_OP_SUBSTR ? (nd.n_args < 2 || nd.n_args > 3) : nd.n_args != (one ? 1 : 2)) bad(std::string(name) + ": wrong number of arguments");
+        const int32_t want = nd.op == TGPU_OP_LENGTH || nd.op == TGPU_OP_STRPOS ? TGPU_BIGINT : nd.op == TGPU_OP_STARTS_WITH ? TGPU_BOOLEAN : TGPU_VARCHAR;
+        if (nd.type != want) bad(std::string(name) + ": wrong result type");
+        need_string_helpers();
+        Val r = declare_result(idx, nd.type, d);
+        // arguments left to right; the first null argument skips the rest and the call
+        os << ind(d) << "{\n";
+        std::vector<Val> a;
+        int dd = d + 1;
+        for (int k = 0; k < nd.n_args; k++) {
+            a.push_back(gen(nd.args[k], dd));
+            os << ind(dd) << "if (" << a[(size_t)k].n << ") " << r.n << " = true; else {\n";
+            dd++;
+        }
+        const Val &x = a[0];
+        if (nd.op != TGPU_OP_CAST && x.type != TGPU_VARCHAR) bad(std::string(name) + " needs a VARCHAR value");
+        if (nd.op == TGPU_OP_CONCAT || nd.op == TGPU_OP_STRPOS || nd.op == TGPU_OP_STARTS_WITH)
+            if (a[1].type != TGPU_VARCHAR) bad(std::string(name) + " needs two VARCHAR arguments");
+        if (nd.op == TGPU_OP_SUBSTR || nd.op == TGPU_OP_STRPOS || nd.op == TGPU_OP_STARTS_WITH)
+            for (const Val &v : a) no_built(v, name);
+        switch (nd.op) {
+        case TGPU_OP_LENGTH:
+            if (!x.built()) os << ind(dd) << r.v << " = tg_cp_count(" << x.v << ", " << x.len << ");\n";
+            else
+                for (const Val::Piece &p : x.pieces)
+                    os << ind(dd) << r.v << " += " << p.p << " ? tg_cp_count(" << p.p << ", " << p.len << ") : (long long)" << p.len << ";\n";
+            break;
+        case TGPU_OP_SUBSTR: {
+            for (size_t k = 1; k < a.size(); k++)
+                if (a[k].type != TGPU_BIGINT) bad("SUBSTR: start and length must be BIGINT");
+            const bool has_len = nd.n_args == 3;
+            // substring :274-309 / :321-367 with positions counted in code-point starts; start and length saturated to int32
+            os << ind(dd) << r.v << " = " << x.v << ";\n";
+            os << ind(dd) << "if (" << a[1].v << " != 0 && " << x.len << " > 0" << (has_len ? " && " + a[2].v + " > 0" : std::string()) << ") {\n";
+            os << ind(dd + 1) << "long long s_ = " << a[1].v << " > 2147483647LL ? 2147483647LL : " << a[1].v << " < -2147483648LL ? -2147483648LL : " << a[1].v << ";\n";
+            os << ind(dd + 1) << "if (s_ > 0) s_ -= 1; else s_ += tg_cp_count(" << x.v << ", " << x.len << ");\n";
+            os << ind(dd + 1) << "if (s_ >= 0) {\n";
+            os << ind(dd + 2) << "const int b_ = tg_cp_offset(" << x.v << ", " << x.len << ", 0, s_);\n";
+            if (has_len) {
+                os << ind(dd + 2) << "const long long c_ = " << a[2].v << " > 2147483647LL ? 2147483647LL : " << a[2].v << ";\n";
+                os << ind(dd + 2) << "const int e_ = b_ < " << x.len << " ? tg_cp_offset(" << x.v << ", " << x.len << ", b_, c_) : b_;\n";
+            }
+            else os << ind(dd + 2) << "const int e_ = " << x.len << ";\n";
+            os << ind(dd + 2) << r.v << " = " << x.v << " + b_; " << r.len << " = e_ - b_;\n";
+            os << ind(dd + 1) << "}\n";
+            os << ind(dd) << "}\n";
+            break;
+        }
+        case TGPU_OP_CONCAT: {
+            // ConcatFunction.java: a result longer than Integer.MAX_VALUE bytes is INVALID_FUNCTION_ARGUMENT
+            os << ind(dd) << "const long long t_ = (long long)" << x.len << " + (long long)" << a[1].len << ";\n";
+            os << ind(dd) << "if (t_ > 2147483647LL) { tg_error(A.error, row, TG_E_CONCAT); " << r.n << " = true; } else {\n";
+            os << ind(dd + 1) << r.len << " = (int)t_;\n";
+            std::vector<Val::Piece> ps = pieces_of(x), qs = pieces_of(a[1]);
+            ps.insert(ps.end(), qs.begin(), qs.end());
+            set_pieces(r, ps, dd + 1);
+            os << ind(dd) << "}\n";
+            break;
+        }
+        case TGPU_OP_STRPOS:
+            // stringPositionFromStart :225-247 with instance 1: a byte search, reported as a code-point index from 1
+            os << ind(dd) << "if (" << a[1].len << " == 0) " << r.v << " = 1;\n";
+            os << ind(dd) << "else { const int f_ = tg_str_find(" << x.v << ", " << x.len << ", " << a[1].v << ", " << a[1].len << "); " << r.v
+               << " = f_ < 0 ? 0 : tg_cp_count(" << x.v << ", f_) + 1; }\n";
+            break;
+        case TGPU_OP_STARTS_WITH:
+            os << ind(dd) << r.v << " = " << x.len << " >= " << a[1].len << " && tg_bytes_equal(" << x.v << ", " << a[1].v << ", " << a[1].len << ");\n";
+            break;
+        default:   // CAST(x AS VARCHAR)
+            if (x.type == TGPU_VARCHAR) assign(r, x, dd);
+            else if (x.type == TGPU_BIGINT || x.type == TGPU_INTEGER) {
+                // String.valueOf: M/type/BigintOperators.java:198-205, IntegerOperators.java:170
+                os << ind(dd) << r.len << " = tg_digits((long long)" << x.v << ");\n";
+                set_pieces(r, {{"(const unsigned char*)0", "(long long)" + x.v, r.len}}, dd);
+            }
+            else if (x.type == TGPU_BOOLEAN)   // M/type/BooleanOperators.java:82
+                os << ind(dd) << r.v << " = " << x.v << " ? TG_STR_TRUE : TG_STR_FALSE; " << r.len << " = " << x.v << " ? 4 : 5;\n";
+            else bad("unsupported cast");
+        }
+        for (int k = 0; k < nd.n_args; k++) os << ind(--dd) << "}\n";
+        os << ind(d) << "}\n";
+        return r;
     }
 
     static bool is_cmp(int op) { return op >= TGPU_OP_EQUAL && op <= TGPU_OP_GREATER_THAN_OR_EQUAL; }
@@ -649,6 +910,8 @@ struct Gen {
         default:
             if (is_cmp(nd.op)) {
                 if (nd.n_args != 2 || a.type != b.type || nd.type != TGPU_BOOLEAN) bad("comparison operand types must match");
+                no_built(a, "a comparison");
+                no_built(b, "a comparison");
                 os << ind(dd) << r.v << " = " << cmp_expr(at, nd.op, a, b) << ";\n";
             }
             else bad("unknown call op");
@@ -659,7 +922,7 @@ struct Gen {
         return r;
     }
 
-    Val gen_special(const tgpu_expr_node &nd, int d)
+    Val gen_special(const tgpu_expr_node &nd, int idx, int d)
     {
         switch (nd.op) {
         case TGPU_SF_AND:
@@ -683,7 +946,7 @@ struct Gen {
         }
         case TGPU_SF_IF: {
             if (nd.n_args != 3) bad("IF takes three arguments");
-            Val r = declare(nd.type, d);
+            Val r = declare_result(idx, nd.type, d);
             os << ind(d) << "{\n";
             Val c = gen(nd.args[0], d + 1);
             if (c.type != TGPU_BOOLEAN) bad("IF condition must be boolean");
@@ -710,7 +973,7 @@ struct Gen {
         }
         case TGPU_SF_COALESCE: {
             if (nd.n_args < 1) bad("COALESCE needs arguments");
-            Val r = declare(nd.type, d);
+            Val r = declare_result(idx, nd.type, d);
             os << ind(d) << r.n << " = true;\n";
             int depth = d;
             for (int k = 0; k < nd.n_args; k++) {
@@ -734,10 +997,13 @@ struct Gen {
             Val v = gen(nd.args[0], d + 1);
             Val lo = gen(nd.args[1], d + 1);
             if (v.type != lo.type) bad("BETWEEN operand types");
+            no_built(v, "BETWEEN");
+            no_built(lo, "BETWEEN");
             os << ind(d + 1) << "bool ln_ = " << v.n << " || " << lo.n << "; bool lv_ = false; if (!ln_) lv_ = " << cmp_expr(v.type, TGPU_OP_GREATER_THAN_OR_EQUAL, v, lo) << ";\n";
             os << ind(d + 1) << "if (!ln_ && !lv_) " << r.v << " = false; else {\n";
             Val hi = gen(nd.args[2], d + 2);
             if (v.type != hi.type) bad("BETWEEN operand types");
+            no_built(hi, "BETWEEN");
             os << ind(d + 2) << "bool rn_ = " << v.n << " || " << hi.n << "; bool rv_ = false; if (!rn_) rv_ = " << cmp_expr(v.type, TGPU_OP_LESS_THAN_OR_EQUAL, v, hi) << ";\n";
             os << ind(d + 2) << "if (rn_) " << r.n << " = true; else if (!rv_) " << r.v << " = false; else { " << r.n << " = ln_; " << r.v << " = true; }\n";
             os << ind(d + 1) << "}\n";
@@ -867,6 +1133,7 @@ struct Gen {
         os << ind(d) << "{\n";
         Val a = gen(nd.args[0], d + 1);
         if (a.type != TGPU_VARCHAR) bad("LIKE needs a VARCHAR value");
+        no_built(a, "LIKE");
         if (pn.is_null || (en && en->is_null)) {
             os << ind(d + 1) << r.n << " = true;\n" << ind(d) << "}\n";
             return r;
@@ -989,6 +1256,7 @@ struct Gen {
         os << ind(d) << "{\n";
         Val v = gen(nd.args[0], d + 1);
         if (v.type != t) bad("IN value type");
+        no_built(v, "IN");
         std::string found = "false";   // a list of null items only
         const size_t count = t == TGPU_VARCHAR ? strings.size() : words.size();
         if (count > 0 && count <= (size_t)kInSmallList) {
@@ -1062,6 +1330,11 @@ struct Gen {
 
     void assign(const Val &dst, const Val &src, int d)
     {
+        if (dst.built()) {
+            os << ind(d) << dst.n << " = " << src.n << "; " << dst.len << " = " << src.len << ";\n";
+            set_pieces(dst, pieces_of(src), d);
+            return;
+        }
         os << ind(d) << dst.n << " = " << src.n << "; " << dst.v << " = " << src.v << ";";
         if (dst.type == TGPU_VARCHAR) os << " " << dst.len << " = " << src.len << ";";
         os << "\n";
@@ -1073,6 +1346,7 @@ const char *kPrelude = R"SRC(
 #define TG_E_RANGE 2
 #define TG_E_DIV0 7
 #define TG_E_CAST 9
+#define TG_E_CONCAT 10
 #define TG_MAXC 24
 #define TG_MAXP 16
 struct FpArgs {
@@ -1205,10 +1479,13 @@ void PageProcessorGpu::generate()
             p.channel = nd.op;
         }
         else {
-            if (nd.type == TGPU_VARCHAR) g.bad("computed VARCHAR projections are not supported");
             p.kind = ProjKind::COMPUTED;
             p.slot = computed_count_++;
             if (computed_count_ > kFpMaxProj) g.bad("too many computed projections");
+            if (nd.type == TGPU_VARCHAR) {
+                p.vslot = varchar_count_++;
+                if (varchar_count_ > kFpMaxVarchar) g.bad("too many computed VARCHAR projections");
+            }
         }
         projs_.push_back(p);
         output_types_.push_back(nd.type);
@@ -1228,11 +1505,27 @@ void PageProcessorGpu::generate()
         Val v = g.gen(proj_roots_[i], 3);
         const int slot = projs_[i].slot;
         const char *T = projs_[i].type == TGPU_BOOLEAN ? "unsigned char" : ctype(projs_[i].type);
-        g.os << "      ((" << T << "*)A.out_values[" << slot << "])[o] = " << v.n << " ? (" << T << ")0 : (" << T << ")" << v.v << ";\n";
+        // a VARCHAR slot gets the row's byte length only (0 for NULL: the reference's builder appends no byte for one); fp_vwrite copies the bytes
+        if (projs_[i].type == TGPU_VARCHAR) g.os << "      ((int*)A.out_values[" << slot << "])[o] = " << v.n << " ? 0 : " << v.len << ";\n";
+        else g.os << "      ((" << T << "*)A.out_values[" << slot << "])[o] = " << v.n << " ? (" << T << ")0 : (" << T << ")" << v.v << ";\n";
         g.os << "      A.out_nulls[" << slot << "][o] = " << v.n << " ? 1 : 0;\n";
         g.os << "    }\n";
     }
     proj_body << g.os.str();
+    g.os.str("");
+    // the write pass evaluates every VARCHAR projection once more and copies its pieces behind one another
+    std::ostringstream vwrite_body;
+    for (size_t i = 0; i < projs_.size(); i++) {
+        if (projs_[i].vslot < 0) continue;
+        g.need_string_helpers();
+        g.os << "  {\n";
+        Val v = g.gen(proj_roots_[i], 2);
+        g.os << "    unsigned char* d_ = V.pool[" << projs_[i].vslot << "] + V.offsets[" << projs_[i].vslot << "][o];\n";
+        g.os << "    const bool w_ = act && !" << v.n << ";\n";
+        for (const Val::Piece &p : Gen::pieces_of(v)) g.os << "    tg_vw_piece(d_, " << p.p << ", " << p.iv << ", " << p.len << ", w_); d_ += " << p.len << ";\n";
+        g.os << "  }\n";
+    }
+    vwrite_body << g.os.str();
 
     std::ostringstream cols;
     for (int ch : g.used_cols) {
@@ -1318,6 +1611,25 @@ extern "C" __global__ void __launch_bounds__(256) fp_emit(FpArgs A) {
 }
 )SRC";
     }
+    if (varchar_count_ > 0) {
+        // pass 3: one lane per OUTPUT row.  Lanes past the last row evaluate the last row too (and write nothing), so that every lane of a
+        // wave reaches the cooperative copies of tg_vw_piece.
+        src << "struct FvArgs { FpArgs fp; const int* offsets[" << kFpMaxVarchar << "]; unsigned char* pool[" << kFpMaxVarchar << "]; long long n_out; };\n";
+        src << "__device__ inline void tg_vwrite(const FvArgs& V, long long row, long long o, bool act) {\n  const FpArgs& A = V.fp;\n" << cols.str() << vwrite_body.str() << "  (void)row;\n}\n";
+        src << R"SRC(
+extern "C" __global__ void __launch_bounds__(256) fp_vwrite(FvArgs V) {
+  const long long tile_base = (long long)blockIdx.x * TG_TILE;
+#pragma unroll 1
+  for (int s = 0; s < TG_STRIPES; s++) {
+    const long long at = tile_base + s * 256 + threadIdx.x;
+    if (at - (threadIdx.x & 63) >= V.n_out) break;   // the whole wave is past the end
+    const bool act = at < V.n_out;
+    const long long o = act ? at : V.n_out - 1;
+    tg_vwrite(V, V.fp.positions ? (long long)V.fp.positions[o] : o, o, act);
+  }
+}
+)SRC";
+    }
     source_ = src.str();
 }
 
@@ -1352,7 +1664,7 @@ std::string spec_key(const char *what, const std::vector<int32_t> &input_types, 
     for (int32_t i = 0; i < spec->projection_count; i++) put_i32(k, spec->projection_roots[i]);
     put_i32(k, (int32_t)extra.size());
     for (int32_t v : extra) put_i32(k, v);
-    for (const char *env : {"TGPU_FG_EXP", "TGPU_FJ_EXP", "TGPU_FA_STRIPES", "TGPU_FJ_STRIPES", "TGPU_FG_STRIPES", "TGPU_FJ_DEPTH"}) {
+    for (const char *env : {"TGPU_FG_EXP", "TGPU_FJ_EXP", "TGPU_FA_STRIPES", "TGPU_FJ_STRIPES", "TGPU_FG_STRIPES", "TGPU_FJ_DEPTH", "TGPU_VW_COOP_MIN"}) {
         const char *v = getenv(env);
         k += '|';
         if (v) k += v;
@@ -1404,6 +1716,7 @@ void PageProcessorGpu::ensure_loaded(Context *ctx)
     module_ = load_module(source_);
     if (filter_root_ >= 0) fn_count_ = module_->fn("fp_count");
     fn_emit_ = module_->fn("fp_emit");
+    if (varchar_count_ > 0) fn_vwrite_ = module_->fn("fp_vwrite");
 }
 
 static void launch(hipFunction_t f, int grid, FpArgs &args, hipStream_t stream)
@@ -1470,7 +1783,7 @@ bool PageProcessorGpu::process(Context *ctx, const DevicePage &in, DevicePage &o
         DeviceColumn c;
         c.type = p.type;
         c.n = n_sel;
-        c.values_buf = ctx->alloc((size_t)n_sel * type_width(p.type));
+        c.values_buf = ctx->alloc((size_t)n_sel * (p.type == TGPU_VARCHAR ? 4 : type_width(p.type)));   // VARCHAR: the rows' byte lengths
         c.values = c.values_buf->ptr();
         c.nulls_buf = ctx->alloc((size_t)n_sel);
         c.nulls = c.nulls_buf->as<uint8_t>();
@@ -1482,7 +1795,41 @@ bool PageProcessorGpu::process(Context *ctx, const DevicePage &in, DevicePage &o
         ProfileScope ps(ctx, has_filter ? "filter_project_emit" : "project_emit");
         launch(fn_emit_, (int)tiles, args, ctx->stream());
     }
-    if (computed_count_ > 0) check_error();
+    if (varchar_count_ > 0) {
+        // offsets = the scan of the lengths; the totals come back with the error word in one round trip, and the bytes are written only
+        // after that word has been checked
+        FvArgs v{};
+        BufferPtr totals = ctx->alloc(8 * (size_t)kFpMaxVarchar);
+        for (auto &p : projs_) {
+            if (p.vslot < 0) continue;
+            DeviceColumn &c = computed[(size_t)p.slot];
+            c.offsets_buf = ctx->alloc((size_t)(n_sel + 1) * 4);
+            c.offsets = c.offsets_buf->as<int32_t>();
+            k::exclusive_scan_i32(ctx, c.values_buf->as<int32_t>(), c.offsets_buf->as<int32_t>(), n_sel, totals->as<int64_t>() + p.vslot);
+        }
+        int64_t total[kFpMaxVarchar] = {};
+        unsigned long long e = ~0ull;
+        ctx->download_batch({{total, totals->ptr(), 8 * (size_t)varchar_count_}, {&e, err->ptr(), 8}});
+        raise_error(e);
+        for (auto &p : projs_) {
+            if (p.vslot < 0) continue;
+            DeviceColumn &c = computed[(size_t)p.slot];
+            const int64_t bytes = total[p.vslot];
+            if (bytes > 0x7fffffffLL) fail(TGPU_ERR_INSUFFICIENT_RESOURCES, "variable width block cannot exceed 2GB");
+            HIP_CHECK(hipMemcpyAsync(c.offsets_buf->as<int32_t>() + n_sel, totals->as<int64_t>() + p.vslot, 4, hipMemcpyDeviceToDevice, ctx->stream()));
+            c.values_buf = ctx->alloc((size_t)(bytes > 0 ? bytes : 1));
+            c.values = c.values_buf->ptr();
+            c.pool_bytes = bytes;
+            c.pool_exact = true;
+            v.offsets[p.vslot] = c.offsets;
+            v.pool[p.vslot] = c.values_buf->as<uint8_t>();
+        }
+        v.fp = args;
+        v.n_out = n_sel;
+        ProfileScope ps(ctx, "project_varchar_write");
+        launch_args(fn_vwrite_, (int)ceil_div(n_sel, 1024), v, ctx->stream());
+    }
+    else if (computed_count_ > 0) check_error();
     out.n = n_sel;
     for (auto &p : projs_) {
         if (p.kind == ProjKind::COMPUTED) out.cols.push_back(computed[(size_t)p.slot]);
@@ -2183,6 +2530,7 @@ FusedProbeGpu::FusedProbeGpu(std::vector<int32_t> input_types, const tgpu_page_p
         if (nd.kind == TGPU_EX_CALL) {
             const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
             if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;
+            if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
             if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
                 const int32_t from = nodes_[(size_t)nd.args[0]].type;
                 if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;
@@ -3266,6 +3614,7 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
         if (nd.kind == TGPU_EX_CALL) {
             const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
             if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;
+            if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
             if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
                 const int32_t from = nodes_[(size_t)nd.args[0]].type;
                 if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;

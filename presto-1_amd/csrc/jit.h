@@ -11,6 +11,7 @@ namespace tgpu {
 
 constexpr int kFpMaxCols = 24;
 constexpr int kFpMaxProj = 16;
+constexpr int kFpMaxVarchar = 8;   // computed VARCHAR projections of one page processor
 
 struct FpArgs {  // must match the struct declared in the generated source
     const void *col_values[kFpMaxCols];
@@ -24,6 +25,16 @@ struct FpArgs {  // must match the struct declared in the generated source
     unsigned long long *error;
     long long n;
     unsigned long long *sel_mask;
+};
+
+// fp_vwrite, the write pass of the computed VARCHAR projections: fp_emit left each row's byte length in out_values[slot] (an int32 array), the
+// scan of it is offsets[v], and the kernel evaluates the projection again to copy its bytes to pool[v] + offsets[v][o].  The block is this
+// kernel's own: FpArgs, which every fused kernel embeds, keeps its layout.
+struct FvArgs {  // must match the struct declared in the generated source
+    FpArgs fp;
+    const int32_t *offsets[kFpMaxVarchar];
+    uint8_t *pool[kFpMaxVarchar];
+    long long n_out;
 };
 
 struct JitModule;
@@ -69,6 +80,7 @@ private:
         ProjKind kind;
         int channel = -1;   // IDENTITY
         int slot = -1;      // COMPUTED: index into FpArgs.out_*
+        int vslot = -1;     // COMPUTED VARCHAR: index into FvArgs.offsets / pool
         int32_t type = 0;
     };
     void generate();
@@ -82,10 +94,10 @@ private:
     std::vector<int32_t> proj_roots_;
     std::vector<Proj> projs_;
     std::vector<int32_t> output_types_;
-    int computed_count_ = 0;
+    int computed_count_ = 0, varchar_count_ = 0;
     std::string source_;
     std::shared_ptr<JitModule> module_;
-    hipFunction_t fn_count_ = nullptr, fn_emit_ = nullptr;
+    hipFunction_t fn_count_ = nullptr, fn_emit_ = nullptr, fn_vwrite_ = nullptr;
     int single_input_ = -1;
     std::vector<int> filter_channels_, projection_channels_;
     std::shared_ptr<PageProcessorGpu> filter_only_;

@@ -11,7 +11,8 @@ from .spi import BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR
 
 EX_INPUT, EX_CONST, EX_CALL, EX_SPECIAL = 0, 1, 2, 3
 OPS = {"ADD": 1, "SUBTRACT": 2, "MULTIPLY": 3, "DIVIDE": 4, "MODULUS": 5, "NEGATE": 6, "EQUAL": 7, "NOT_EQUAL": 8,
-       "LESS_THAN": 9, "LESS_THAN_OR_EQUAL": 10, "GREATER_THAN": 11, "GREATER_THAN_OR_EQUAL": 12, "NOT": 13, "CAST": 14, "LIKE": 15}
+       "LESS_THAN": 9, "LESS_THAN_OR_EQUAL": 10, "GREATER_THAN": 11, "GREATER_THAN_OR_EQUAL": 12, "NOT": 13, "CAST": 14, "LIKE": 15,
+       "LENGTH": 16, "SUBSTR": 17, "CONCAT": 18, "STRPOS": 19, "STARTS_WITH": 20}
 FORMS = {"AND": 1, "OR": 2, "IF": 3, "IS_NULL": 4, "COALESCE": 5, "BETWEEN": 6, "IN": 7}
 _CMP = {"EQUAL", "NOT_EQUAL", "LESS_THAN", "LESS_THAN_OR_EQUAL", "GREATER_THAN", "GREATER_THAN_OR_EQUAL"}
 
@@ -78,7 +79,7 @@ def or_(a, b): return SpecialForm("OR", BOOLEAN, [a, b])
 def not_(a): return call("NOT", BOOLEAN, a)
 def is_null(a): return SpecialForm("IS_NULL", BOOLEAN, [a])
 def if_(c, t, f): return SpecialForm("IF", t.type, [c, t, f])
-def coalesce(*args): return SpecialForm("COALESCE", args[0].type, list(args))
+def coalesce(*args): return SpecialForm("COALESCE", args[0].type, [_wrap(a, args[0].type) for a in args])
 def between(v, lo, hi): return SpecialForm("BETWEEN", BOOLEAN, [v, _wrap(lo, v.type), _wrap(hi, v.type)])
 def cast(a, type_id): return call("CAST", type_id, a)
 
@@ -94,6 +95,38 @@ def like(value, pattern, escape=None):
 def in_(value, items):
     """value IN (items); an item is a Python value (None = the null literal) or a constant of the value's type"""
     return SpecialForm("IN", BOOLEAN, [value], [_wrap(i, value.type) for i in items])
+
+
+def length(x):
+    """length(x): the code points of a VARCHAR value"""
+    return call("LENGTH", BIGINT, _wrap(x, VARCHAR))
+
+
+def substr(x, start, length=None):
+    """substr(x, start[, length]): positions in code points from 1, a negative start counts from the end"""
+    args = [_wrap(x, VARCHAR), _wrap(start, BIGINT)]
+    if length is not None:
+        args.append(_wrap(length, BIGINT))
+    return call("SUBSTR", VARCHAR, *args)
+
+
+def concat(*args):
+    """concat(a, b, ...): two or more VARCHAR arguments, nested to the left as the IR's CONCAT takes two"""
+    if len(args) < 2:
+        raise ValueError("There must be two or more concatenation arguments")
+    r = _wrap(args[0], VARCHAR)
+    for a in args[1:]:
+        r = call("CONCAT", VARCHAR, r, _wrap(a, VARCHAR))
+    return r
+
+
+def strpos(x, sub):
+    """strpos(x, sub): the code-point index from 1 of the first occurrence of sub, 0 if there is none"""
+    return call("STRPOS", BIGINT, _wrap(x, VARCHAR), _wrap(sub, VARCHAR))
+
+
+def starts_with(x, prefix):
+    return call("STARTS_WITH", BOOLEAN, _wrap(x, VARCHAR), _wrap(prefix, VARCHAR))
 
 
 class FlatProgram:
