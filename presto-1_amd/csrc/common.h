@@ -262,11 +262,13 @@ struct ProfileScope {
     }
 };
 
-// an expression-error word written by a generated kernel: ~0 = none, else (row << 8) | code (7 = division by zero, 9 = invalid cast argument, 10 = concatenated string too large, else overflow)
+// an expression-error word written by a generated kernel: ~0 = none, else (rank << 40) | (row << 8) | code (7 = division by zero, 9 = invalid
+// cast argument, 10 = concatenated string too large, else overflow).  rank orders the roots as the reference evaluates them (0 the filter,
+// 1 + i projection i: jit.cpp "which error a page raises"); the minimum over the page is the failure the reference throws first.
 inline void raise_expression_error(unsigned long long e)
 {
     if (e == ~0ull) return;
-    const long long row = (long long)(e >> 8);
+    const long long row = (long long)((e >> 8) & 0xffffffffull);
     if ((int)(e & 0xff) == 7) fail(TGPU_ERR_DIVISION_BY_ZERO, "Division by zero (position " + std::to_string(row) + ")");
     if ((int)(e & 0xff) == 10) fail(TGPU_ERR_INVALID_ARGUMENT, "Concatenated string is too large (position " + std::to_string(row) + ")");
     if ((int)(e & 0xff) == 9) fail(TGPU_ERR_INVALID_CAST_ARGUMENT, "Cannot cast double to an integer type: NaN or out of range (position " + std::to_string(row) + ")");

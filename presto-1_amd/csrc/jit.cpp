@@ -548,9 +548,36 @@ struct Gen {
         return s.str();
     }
 
-    void error_stmt(int d, const char *code, const Val &r)
+    // ---- which error a page raises -------------------------------------------------------------------------------------------
+    // The reference throws at the first failing node it evaluates: the filter over the rows in order, then projection by projection over
+    // the selected rows in order (PageProcessor.java:313-338).  Here a failing node becomes NULL and the lanes go on, so
+    //   - every root (the filter, one projection) keeps a per-row flag ef_: only its first evaluated failure posts, whatever the nodes
+    //     that are evaluated after it do with the NULL;
+    //   - the key posted is (rank << 40) | (row << 8) | code with rank 0 for the filter and 1 + i for projection i, and the page's error
+    //     word keeps the minimum: filter before projections, then the projection index, then the row.
+    // A program with no raising node gets none of this: its source is what it always was.
+    int raises = 0;   // raise sites emitted so far
+
+    std::string raise(const char *code)
     {
-        os << ind(d) << "{ tg_error(A.error, row, " << code << "); " << r.n << " = true; }\n";
+        if (raises++ == 0)
+            consts << "#ifndef TG_RAISE\n#define TG_RAISE(code) do { if (!ef_) { ef_ = true; tg_error(A.error, er_ + row, code); } } while (0)\n#endif\n";
+        return std::string("TG_RAISE(") + code + ");";
+    }
+
+    // gen() for the root of the filter (rank 0) or of projection i (rank 1 + i): declares the root's flag and key when it can raise
+    Val gen_root(int idx, int d, int rank)
+    {
+        const std::string before = os.str();
+        const int raised = raises;
+        os.str("");
+        Val v = gen(idx, d);
+        const std::string body = os.str();
+        os.str("");
+        os << before;
+        if (raises != raised) os << ind(d) << "bool ef_ = false; const long long er_ = " << rank << "LL << 32;\n";
+        os << body;
+        return v;
     }
 
     // emits code that computes node idx into a fresh (value, null) pair declared at depth d
@@ -743,7 +770,7 @@ struct Gen {
         case TGPU_OP_CONCAT: {
             // ConcatFunction.java: a result longer than Integer.MAX_VALUE bytes is INVALID_FUNCTION_ARGUMENT
             os << ind(dd) << "const long long t_ = (long long)" << x.len << " + (long long)" << a[1].len << ";\n";
-            os << ind(dd) << "if (t_ > 2147483647LL) { tg_error(A.error, row, TG_E_CONCAT); " << r.n << " = true; } else {\n";
+            os << ind(dd) << "if (t_ > 2147483647LL) { " << raise("TG_E_CONCAT") << " " << r.n << " = true; } else {\n";
             os << ind(dd + 1) << r.len << " = (int)t_;\n";
             std::vector<Val::Piece> ps = pieces_of(x), qs = pieces_of(a[1]);
             ps.insert(ps.end(), qs.begin(), qs.end());
@@ -853,12 +880,12 @@ struct Gen {
                 if (nd.op == TGPU_OP_ADD || nd.op == TGPU_OP_SUBTRACT || nd.op == TGPU_OP_MULTIPLY) {
                     const char *fn = nd.op == TGPU_OP_ADD ? "__builtin_add_overflow" : nd.op == TGPU_OP_SUBTRACT ? "__builtin_sub_overflow" : "__builtin_mul_overflow";
                     os << ind(dd) << T << " t_; if (" << fn << "(" << a.v << ", " << b.v << ", &t_))";
-                    os << " { tg_error(A.error, row, TG_E_RANGE); " << r.n << " = true; } else " << r.v << " = t_;\n";
+                    os << " { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = t_;\n";
                 }
                 else {
-                    os << ind(dd) << "if (" << b.v << " == 0) { tg_error(A.error, row, TG_E_DIV0); " << r.n << " = true; }\n";
+                    os << ind(dd) << "if (" << b.v << " == 0) { " << raise("TG_E_DIV0") << " " << r.n << " = true; }\n";
                     if (nd.op == TGPU_OP_DIVIDE) {
-                        os << ind(dd) << "else if (" << a.v << " == " << MINV << " && " << b.v << " == -1) { tg_error(A.error, row, TG_E_RANGE); " << r.n << " = true; }\n";
+                        os << ind(dd) << "else if (" << a.v << " == " << MINV << " && " << b.v << " == -1) { " << raise("TG_E_RANGE") << " " << r.n << " = true; }\n";
                         os << ind(dd) << "else " << r.v << " = " << a.v << " / " << b.v << ";\n";
                     }
                     else {
@@ -873,9 +900,9 @@ struct Gen {
             if (nd.n_args != 1 || a.type != nd.type) bad("negate operand type");
             if (nd.type == TGPU_DOUBLE) os << ind(dd) << r.v << " = -" << a.v << ";\n";
             else if (nd.type == TGPU_BIGINT)
-                os << ind(dd) << "if (" << a.v << " == (-9223372036854775807LL - 1)) { tg_error(A.error, row, TG_E_RANGE); " << r.n << " = true; } else " << r.v << " = -" << a.v << ";\n";
+                os << ind(dd) << "if (" << a.v << " == (-9223372036854775807LL - 1)) { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = -" << a.v << ";\n";
             else if (nd.type == TGPU_INTEGER)
-                os << ind(dd) << "if (" << a.v << " == (-2147483647 - 1)) { tg_error(A.error, row, TG_E_RANGE); " << r.n << " = true; } else " << r.v << " = -" << a.v << ";\n";
+                os << ind(dd) << "if (" << a.v << " == (-2147483647 - 1)) { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = -" << a.v << ";\n";
             else bad("negate on unsupported type");
             break;
         case TGPU_OP_NOT:
@@ -888,7 +915,7 @@ struct Gen {
             else if (nd.type == TGPU_DOUBLE && (at == TGPU_BIGINT || at == TGPU_INTEGER)) os << ind(dd) << r.v << " = (double)" << a.v << ";\n";
             else if (nd.type == TGPU_BIGINT && at == TGPU_INTEGER) os << ind(dd) << r.v << " = (long long)" << a.v << ";\n";
             else if (nd.type == TGPU_INTEGER && at == TGPU_BIGINT)
-                os << ind(dd) << "if (" << a.v << " > 2147483647LL || " << a.v << " < -2147483648LL) { tg_error(A.error, row, TG_E_RANGE); " << r.n << " = true; } else " << r.v << " = (int)" << a.v << ";\n";
+                os << ind(dd) << "if (" << a.v << " > 2147483647LL || " << a.v << " < -2147483648LL) { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = (int)" << a.v << ";\n";
             // castToBoolean: M/type/BigintOperators.java:115-120, IntegerOperators.java:146-151, DoubleOperators.java:101-106 (NaN -> true)
             else if (nd.type == TGPU_BOOLEAN && (at == TGPU_BIGINT || at == TGPU_INTEGER || at == TGPU_DOUBLE)) os << ind(dd) << r.v << " = " << a.v << " != 0;\n";
             // M/type/BooleanOperators.java:37-63
@@ -897,13 +924,13 @@ struct Gen {
             else if (nd.type == TGPU_BIGINT && at == TGPU_DOUBLE) {
                 // DoubleOperators.castToLong :153-163 (DoubleMath.roundToLong HALF_UP): ties away from zero; NaN / inf / out of long range -> INVALID_CAST_ARGUMENT
                 os << ind(dd) << "double z_ = tg_round_half_away(" << a.v << ");\n";
-                os << ind(dd) << "if (!(z_ >= -9223372036854775808.0 && z_ < 9223372036854775808.0)) { tg_error(A.error, row, TG_E_CAST); " << r.n << " = true; } else " << r.v << " = (long long)z_;\n";
+                os << ind(dd) << "if (!(z_ >= -9223372036854775808.0 && z_ < 9223372036854775808.0)) { " << raise("TG_E_CAST") << " " << r.n << " = true; } else " << r.v << " = (long long)z_;\n";
             }
             else if (nd.type == TGPU_INTEGER && at == TGPU_DOUBLE) {
                 // DoubleOperators.castToInteger :108-121: NaN -> INVALID_CAST_ARGUMENT, else toIntExact((long) round(value))
                 os << ind(dd) << "double z_ = tg_round_half_away(" << a.v << ");\n";
-                os << ind(dd) << "if (" << a.v << " != " << a.v << ") { tg_error(A.error, row, TG_E_CAST); " << r.n << " = true; }\n";
-                os << ind(dd) << "else if (!(z_ >= -2147483648.0 && z_ <= 2147483647.0)) { tg_error(A.error, row, TG_E_RANGE); " << r.n << " = true; } else " << r.v << " = (int)z_;\n";
+                os << ind(dd) << "if (" << a.v << " != " << a.v << ") { " << raise("TG_E_CAST") << " " << r.n << " = true; }\n";
+                os << ind(dd) << "else if (!(z_ >= -2147483648.0 && z_ <= 2147483647.0)) { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = (int)z_;\n";
             }
             else bad("unsupported cast");
             break;
@@ -1493,7 +1520,7 @@ void PageProcessorGpu::generate()
 
     std::ostringstream filter_body, proj_body;
     if (filter_root_ >= 0) {
-        Val f = g.gen(filter_root_, 2);
+        Val f = g.gen_root(filter_root_, 2, 0);
         if (f.type != TGPU_BOOLEAN) g.bad("filter must be boolean");
         g.os << "    return !" << f.n << " && " << f.v << ";\n";
         filter_body << g.os.str();
@@ -1502,7 +1529,7 @@ void PageProcessorGpu::generate()
     for (size_t i = 0; i < projs_.size(); i++) {
         if (projs_[i].kind != ProjKind::COMPUTED) continue;
         g.os << "    {\n";
-        Val v = g.gen(proj_roots_[i], 3);
+        Val v = g.gen_root(proj_roots_[i], 3, 1 + (int)i);
         const int slot = projs_[i].slot;
         const char *T = projs_[i].type == TGPU_BOOLEAN ? "unsigned char" : ctype(projs_[i].type);
         // a VARCHAR slot gets the row's byte length only (0 for NULL: the reference's builder appends no byte for one); fp_vwrite copies the bytes
@@ -1519,7 +1546,7 @@ void PageProcessorGpu::generate()
         if (projs_[i].vslot < 0) continue;
         g.need_string_helpers();
         g.os << "  {\n";
-        Val v = g.gen(proj_roots_[i], 2);
+        Val v = g.gen_root(proj_roots_[i], 2, 1 + (int)i);
         g.os << "    unsigned char* d_ = V.pool[" << projs_[i].vslot << "] + V.offsets[" << projs_[i].vslot << "][o];\n";
         g.os << "    const bool w_ = act && !" << v.n << ";\n";
         for (const Val::Piece &p : Gen::pieces_of(v)) g.os << "    tg_vw_piece(d_, " << p.p << ", " << p.iv << ", " << p.len << ", w_); d_ += " << p.len << ";\n";
@@ -2603,7 +2630,7 @@ void FusedProbeGpu::generate()
     gr.reg_mode = true;
     std::vector<std::string> reg_bodies;
     if (filter_root_ >= 0) {
-        Val f = gr.gen(filter_root_, 1);
+        Val f = gr.gen_root(filter_root_, 1, 0);
         if (f.type != TGPU_BOOLEAN) gr.bad("filter must be boolean");
         std::ostringstream fb;
         fb << "__device__ inline bool tg_filter(const FpArgs& A, long long row, const TgRow& R) {\n@COLS@" << gr.os.str() << "  return !" << f.n << " && " << f.v << ";\n}\n";
@@ -2612,7 +2639,7 @@ void FusedProbeGpu::generate()
     else reg_bodies.push_back("__device__ inline bool tg_filter(const FpArgs& A, long long row, const TgRow& R) { return true; }\n");
     {
         gr.os.str("");
-        Val v = gr.gen(proj_roots_[(size_t)join_channel_], 1);
+        Val v = gr.gen_root(proj_roots_[(size_t)join_channel_], 1, 1 + join_channel_);
         std::ostringstream f;
         f << "__device__ inline bool tg_key(const FpArgs& A, long long row, const TgRow& R, long long& key) {\n@COLS@" << gr.os.str() << "  key = (long long)" << v.v
           << ";\n  return " << v.n << ";\n}\n";
@@ -2625,7 +2652,7 @@ void FusedProbeGpu::generate()
     std::set<int> outs(output_channels_.begin(), output_channels_.end());
     for (int ch : outs) {
         gm.os.str("");
-        Val v = gm.gen(proj_roots_[(size_t)ch], 1);
+        Val v = gm.gen_root(proj_roots_[(size_t)ch], 1, 1 + ch);
         std::ostringstream f;
         f << "__device__ inline bool tg_p" << ch << "(const FpArgs& A, long long row, " << ctype(proj_types_[(size_t)ch]) << "& out) {\n@COLS@" << gm.os.str()
           << "  out = " << v.v << ";\n  return " << v.n << ";\n}\n";
@@ -2646,7 +2673,7 @@ void FusedProbeGpu::generate()
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int ch = output_channels_[i];
         gc.os.str("");
-        Val v = gc.gen(proj_roots_[(size_t)ch], 1);
+        Val v = gc.gen_root(proj_roots_[(size_t)ch], 1, 1 + ch);
         std::ostringstream f;
         f << "__device__ inline bool tg_c" << i << "(const FpArgs& A, long long row, const TgRow& R, " << ctype(proj_types_[(size_t)ch]) << "& out) {\n@COLS@" << gc.os.str()
           << "  out = " << v.v << ";\n  return " << v.n << ";\n}\n";
@@ -2671,7 +2698,7 @@ void FusedProbeGpu::generate()
             if (ch == join_channel_ && (key_can_raise_ || free_rule == 1)) continue;
             Gen ga(nodes_, pool_, input_types_);
             ga.reg_mode = true;
-            ga.gen(proj_roots_[(size_t)ch], 1);
+            ga.gen_root(proj_roots_[(size_t)ch], 1, 1 + ch);
             bool held = ga.used_cols.empty() && ga.consts.str().empty();
             for (int col : ga.reg_cols) held = held && gr.reg_cols.count(col) != 0;
             free_out_[i] = held;
@@ -3732,7 +3759,7 @@ void FusedAggGpu::generate()
     Gen gm(nodes_, pool_, input_types_);
     std::ostringstream filter_fn;
     if (filter_root_ >= 0) {
-        Val f = gm.gen(filter_root_, 1);
+        Val f = gm.gen_root(filter_root_, 1, 0);
         if (f.type != TGPU_BOOLEAN) gm.bad("filter must be boolean");
         filter_fn << "__device__ inline bool tg_filter_mem(const FpArgs& A, long long row) {\n" << cols_decl(gm) << gm.os.str() << "  return !" << f.n << " && " << f.v << ";\n}\n";
     }
@@ -3758,13 +3785,13 @@ void FusedAggGpu::generate()
         eval << "  bool t" << k << " = true; double x" << k << " = 0.0; long long y" << k << " = 0; (void)x" << k << "; (void)y" << k << ";\n  {\n";
         gr.os.str("");
         if (a.mask_channel >= 0) {
-            Val m = gr.gen(proj_roots_[(size_t)a.mask_channel], 2);
+            Val m = gr.gen_root(proj_roots_[(size_t)a.mask_channel], 2, 1 + a.mask_channel);
             eval << gr.os.str() << "    t" << k << " = !" << m.n << " && " << m.v << ";\n";
             gr.os.str("");
         }
         if (a.function != TGPU_AGG_COUNT_ALL) {
             eval << "    if (t" << k << ") {\n";
-            Val v = gr.gen(proj_roots_[(size_t)a.input_channel], 3);
+            Val v = gr.gen_root(proj_roots_[(size_t)a.input_channel], 3, 1 + a.input_channel);
             eval << gr.os.str();
             gr.os.str("");
             eval << "      if (" << v.n << ") t" << k << " = false;\n";
@@ -4113,7 +4140,7 @@ void FusedAggGpu::generate()
             gf.tmp = gr.tmp + 1000;
             std::ostringstream body;
             if (filter_root_ >= 0) {
-                Val f = gf.gen(filter_root_, 1);
+                Val f = gf.gen_root(filter_root_, 1, 0);
                 body << cols_decl(gf) << gf.os.str() << "  return !" << f.n << " && " << f.v << ";\n";
             }
             else body << "  return true;\n";

@@ -261,6 +261,39 @@ def product_engine(pkg, ctx):
     return ProductEngine()
 
 
+def drive_pages(pkg, op, pages):
+    """the driver loop of to_pages one input page at a time, for programs that may fail: -> (host output pages, None), or
+    (the output so far, (the TgpuError, the index of the input page that was the last one added, the position its message names))"""
+    import re
+    outs, at = [], -1
+
+    def take():
+        o = op.getOutput()
+        if o is not None:
+            if o.position_count > 0:
+                outs.append(o.to_host())
+            o.release()
+    try:
+        for at, pg in enumerate(pages):
+            assert not op.isBlocked() and op.needsInput()
+            op.addInput(pg)
+            take()
+            for _ in range(1000):
+                if op.needsInput():
+                    break
+                take()
+        op.finish()
+        for _ in range(1000):
+            if op.isFinished():
+                break
+            take()
+        assert op.isFinished()
+    except pkg.TgpuError as e:
+        m = re.search(r"\(position (\d+)\)", str(e))
+        return outs, (e, at, int(m.group(1)) if m else None)
+    return outs, None
+
+
 # ---- page-level fixtures: T/operator/TestFilterAndProjectOperator.java, T/operator/project/TestPageProcessor.java -------------
 def run_page_fixtures(E, engine, ref_gold):
     """ref_gold = tests/golden/reference_vectors.json; asserts inside"""
