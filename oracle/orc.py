@@ -127,10 +127,14 @@ def rle_v2_short_repeat(value, count, signed):
     return bytes([((size - 1) << 3) | (count - 3)]) + v.to_bytes(size, "big")
 
 
-def rle_v2_delta(first, deltas, signed):
-    """one DELTA run: first value + deltas of one sign (or all equal: fixed delta)"""
+def rle_v2_delta(first, deltas, signed, width=None):
+    """one DELTA run: first value + deltas of one sign (or all equal: fixed delta).  width: the packed width (a width code, 2..64) whatever the
+    deltas need -- also for equal deltas, and for ONE delta (a run of 2 values with a width and nothing packed, which no writer emits)"""
     out = bytearray()
     n = len(deltas)
+    if width is not None:
+        mags = [abs(d) for d in deltas[1:]]
+        return bytes([0xc0 | (_WIDTH_CODE[width] << 1) | (n >> 8), n & 0xff]) + write_vlong(first, signed) + write_vlong(deltas[0], True) + pack_bits(mags, width)
     if len(set(deltas)) == 1:
         out += bytes([0xc0 | (n >> 8), n & 0xff]) + write_vlong(first, signed) + write_vlong(deltas[0], True)
         return bytes(out)
@@ -142,12 +146,13 @@ def rle_v2_delta(first, deltas, signed):
     return bytes(out)
 
 
-def rle_v2_patched_base(values, base, fb, patch_width, patches):
-    """one PATCHED_BASE run: values = base + (low fb bits | patch << fb at the patched positions); patches = [(gap, patch value)] with gaps <= 255"""
+def rle_v2_patched_base(values, base, fb, patch_width, patches, base_width=None, gap_width=None):
+    """one PATCHED_BASE run: values = base + (low fb bits | patch << fb at the patched positions); patches = [(gap, patch value)] with gaps <= 255.
+    base_width (bytes) / gap_width (bits): wider fields than the base / the gaps need"""
     n = len(values) - 1
-    bw = max(1, (abs(base).bit_length() + 8) // 8)
+    bw = base_width or max(1, (abs(base).bit_length() + 8) // 8)
     bb = abs(base) | ((1 << (bw * 8 - 1)) if base < 0 else 0)
-    pgw = max(1, max(g for g, _ in patches).bit_length())
+    pgw = gap_width or max(1, max(g for g, _ in patches).bit_length())
     out = bytearray([0x80 | (_WIDTH_CODE[fb] << 1) | (n >> 8), n & 0xff, ((bw - 1) << 5) | _WIDTH_CODE[patch_width], ((pgw - 1) << 5) | len(patches)])
     out += bb.to_bytes(bw, "big")
     out += pack_bits([(int(v) - base) & ((1 << fb) - 1) for v in values], fb)

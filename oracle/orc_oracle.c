@@ -185,12 +185,10 @@ int64_t o_orc_rle_v2(const uint8_t *bytes, int64_t len, int32_t is_signed, int64
             const int fourth = rd(&in);
             const int patch_gap_width = ((fourth >> 5) & 7) + 1;
             const int patch_list_length = fourth & 0x1f;
-            int64_t base = (int64_t)bytes_to_long_be(&in, base_width);
-            const int64_t mask = (int64_t)1 << ((base_width * 8) - 1);
-            if ((base & mask) != 0) {
-                base = base & ~mask;
-                base = -base;
-            }
+            /* (Java's long arithmetic wraps: every sum and shift below is done on uint64_t, shifts by the count modulo 64) */
+            const uint64_t raw_base = bytes_to_long_be(&in, base_width);
+            const uint64_t mask = (uint64_t)1 << ((base_width * 8) - 1);
+            const uint64_t base = (raw_base & mask) != 0 ? ~(raw_base & ~mask) + 1 : raw_base;
             unpack_generic(&in, unpacked, 0, length, fb);
             if (patch_width + patch_gap_width > 64) return -1;   /* "Invalid RLEv2 encoded stream" */
             const int bit_size = o_orc_closest_fixed_bits(patch_width + patch_gap_width);
@@ -210,7 +208,7 @@ int64_t o_orc_rle_v2(const uint8_t *bytes, int64_t len, int32_t is_signed, int64
             actual_gap += (int64_t)current_gap;
             for (int i = 0; i < length; i++) {
                 if (i == actual_gap) {
-                    const int64_t patched = (int64_t)((uint64_t)unpacked[i] | (current_patch << fb));
+                    const uint64_t patched = (uint64_t)unpacked[i] | (current_patch << (fb & 63));   /* :219 */
                     EMIT(base + patched);
                     patch_index++;
                     if (patch_index < patch_list_length) {
@@ -227,7 +225,7 @@ int64_t o_orc_rle_v2(const uint8_t *bytes, int64_t len, int32_t is_signed, int64
                         actual_gap += i;
                     }
                 }
-                else EMIT(base + unpacked[i]);
+                else EMIT(base + (uint64_t)unpacked[i]);
             }
         }
         else {   /* DELTA :82-132 */
@@ -246,6 +244,9 @@ int64_t o_orc_rle_v2(const uint8_t *bytes, int64_t len, int32_t is_signed, int64
             }
             else {
                 const int64_t delta_base = zigzag_decode(read_unsigned_vint(&in));
+                /* a packed width with no second value: :121 makes the length -1 and the width-specialised unpackers of LongBitPacker.java:110-351 are
+                 * handed a negative count; no writer emits it, the library refuses it ("Invalid RLEv2 encoded stream") and so does the oracle */
+                if (length < 1) return -1;
                 EMIT((int64_t)((uint64_t)first_val + (uint64_t)delta_base));
                 int64_t prev = out[n - 1];
                 length -= 1;

@@ -190,8 +190,14 @@ def zigzag_uleb(v):
     return uleb(((v << 1) ^ (v >> 63)) & ((1 << 64) - 1))
 
 
-def delta_encode(values, physical, block_size=128, miniblocks=4):
-    """a DELTA_BINARY_PACKED section over `values` (wrapping arithmetic of the physical type's width, like the writers)"""
+def dictionary_ids_encode(ids, bit_width):
+    """the value section of a dictionary-encoded page: the bit width byte -- free: any width >= what the dictionary needs -- then the ids' hybrid stream"""
+    return bytes([bit_width]) + hybrid_encode(ids, bit_width)
+
+
+def delta_encode(values, physical, block_size=128, miniblocks=4, tail_width=0):
+    """a DELTA_BINARY_PACKED section over `values` (wrapping arithmetic of the physical type's width, like the writers).  tail_width: the width
+    byte listed for the miniblocks of the last block that hold no value and are not written (writers list 0)"""
     bits = 32 if physical == INT32 else 64
     mask = (1 << bits) - 1
 
@@ -211,7 +217,7 @@ def delta_encode(values, physical, block_size=128, miniblocks=4):
         for m in range(miniblocks):
             part = rel[m * mini:(m + 1) * mini]
             if not part:
-                widths.append(0)
+                widths.append(tail_width)
                 continue
             w = max(x.bit_length() for x in part)
             widths.append(w)
@@ -229,22 +235,22 @@ def delta_encode(values, physical, block_size=128, miniblocks=4):
     return bytes(out)
 
 
-def delta_length_encode(values):
-    return delta_encode([len(b) for b in values], INT32) + b"".join(bytes(b) for b in values)
+def delta_length_encode(values, block_size=128, miniblocks=4):
+    return delta_encode([len(b) for b in values], INT32, block_size, miniblocks) + b"".join(bytes(b) for b in values)
 
 
-def delta_byte_array_encode(values):
-    """prefix = the longest common prefix with the value before (what the writers do); any prefix <= that would be valid"""
+def delta_byte_array_encode(values, block_size=128, miniblocks=4, share_prefixes=True):
+    """prefix = the longest common prefix with the value before (what the writers do); any prefix <= that is valid: share_prefixes=False writes 0 throughout"""
     prefixes, suffixes, prev = [], [], b""
     for v in values:
         v = bytes(v)
         k = 0
-        while k < min(len(prev), len(v)) and prev[k] == v[k]:
+        while share_prefixes and k < min(len(prev), len(v)) and prev[k] == v[k]:
             k += 1
         prefixes.append(k)
         suffixes.append(v[k:])
         prev = v
-    return delta_encode(prefixes, INT32) + delta_length_encode(suffixes)
+    return delta_encode(prefixes, INT32, block_size, miniblocks) + delta_length_encode(suffixes, block_size, miniblocks)
 
 
 def plain_encode(physical, values):

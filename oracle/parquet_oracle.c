@@ -111,7 +111,8 @@ int64_t o_pq_delta_binary_packed(const uint8_t *bytes, int64_t len, int64_t want
     uint64_t block_size, miniblocks, total, zz;
     if (pq_uleb(bytes, len, &at, &block_size) || pq_uleb(bytes, len, &at, &miniblocks) || pq_uleb(bytes, len, &at, &total) || pq_uleb(bytes, len, &at, &zz)) return -1;
     if (miniblocks == 0 || miniblocks > 4096 || block_size == 0 || block_size % 128 || block_size % miniblocks || (block_size / miniblocks) % 32) return -1;
-    if ((int64_t)total < want) return -1;
+    if (block_size / miniblocks > 0x7fffffffull) return -1;   /* a page holds at most 2^31 - 1 values: no miniblock is larger */
+    if (total > 0x7fffffffffffffffull || (int64_t)total < want) return -1;
     if (consumed) *consumed = at;
     if (want == 0) return 0;
     const int64_t mini = (int64_t)(block_size / miniblocks);
@@ -127,7 +128,8 @@ int64_t o_pq_delta_binary_packed(const uint8_t *bytes, int64_t len, int64_t want
         at += (int64_t)miniblocks;
         for (uint64_t m = 0; m < miniblocks && n < want; m++) {
             const int w = widths[m];
-            if (w > 64 || at + mini * w / 8 > len) return -1;
+            /* the miniblock fits the rest of the section: decided BEFORE mini * w is multiplied out (mini is a multiple of 32: mini * w is whole bytes) */
+            if (w > 64 || (w > 0 && mini > (len - at) * 8 / w)) return -1;
             for (int64_t i = 0; i < mini && n < want; i++) {
                 uint64_t d = 0;
                 for (int k = 0; k < w; k++) {

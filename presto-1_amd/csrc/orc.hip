@@ -14,6 +14,9 @@
 
 #include "kernels.h"
 
+#define WALK_FAIL(msg) ::tgpu::fail(TGPU_ERR_INVALID_ARGUMENT, (msg))
+#include "stream_walk.h"
+
 #include <cstring>
 
 namespace tgpu {
@@ -23,160 +26,42 @@ namespace {
 
 constexpr int kWave = 64;
 
-enum RunKind : int32_t { SHORT_REPEAT = 0, DIRECT = 1, PATCHED_BASE = 2, DELTA = 3, V1_RUN = 4, V1_LITERALS = 5 };
+// the run directories and the host walks that build them (and are the kernels' whole bounds check): stream_walk.h
+using walk::OrcRun;
+using walk::ByteRun;
+using walk::SHORT_REPEAT;
+using walk::DIRECT;
+using walk::PATCHED_BASE;
+using walk::DELTA;
+using walk::V1_RUN;
+using walk::V1_LITERALS;
+using walk::scan_rle_v2;
+using walk::scan_rle_v1;
+using walk::scan_byte_rle;
 
-struct Run {
-    int64_t in_off;       // first byte of the run's PACKED payload (behind the header fields the host has read)
-    int64_t out_off;      // index of the run's first value
-    int32_t kind, count;  // values of the run
-    int32_t width;        // bit width of the packed values (0: DELTA with a fixed delta)
-    int32_t patch_width, patch_gap_width, patch_count, patch_bits;   // PATCHED_BASE: patch list entries of patch_bits bits = gap | patch
-    int64_t base;         // SHORT_REPEAT: the (zigzag-decoded) value; PATCHED_BASE: base; DELTA: first value
-    int64_t delta;        // DELTA: fixed delta / delta base
-    int64_t patch_off;    // PATCHED_BASE: first byte of the patch list
-};
-
-int decode_bit_width(int n)
-{
-    if (n >= 0 && n <= 23) return n + 1;
-    static const int wide[8] = {26, 28, 30, 32, 40, 48, 56, 64};
-    return wide[(n - 24) & 7];
-}
-int closest_fixed_bits(int w)
-{
-    if (w == 0) return 1;
-    if (w <= 24) return w;
-    if (w <= 26) return 26;
-    if (w <= 28) return 28;
-    if (w <= 30) return 30;
-    if (w <= 32) return 32;
-    if (w <= 40) return 40;
-    if (w <= 48) return 48;
-    if (w <= 56) return 56;
-    return 64;
-}
-
-struct HostReader {
-    const uint8_t *p;
-    int64_t len, at = 0;
-    int read()
-    {
-        if (at >= len) fail(TGPU_ERR_INVALID_ARGUMENT, "ORC stream: read past the end of an RLE run");
-        return p[at++];
-    }
-    uint64_t vint()
-    {
-        uint64_t r = 0;
-        int off = 0, b;
-        do {
-            b = read();
-            if (off < 64) r |= (uint64_t)(b & 0x7f) << off;
-            off += 7;
-        } while (b & 0x80);
-        return r;
-    }
-    void skip(int64_t n)
-    {
-        if (at + n > len) fail(TGPU_ERR_INVALID_ARGUMENT, "ORC stream: a run is longer than the stream");
-        at += n;
-    }
-};
-int64_t zigzag(uint64_t v) { return (int64_t)((v >> 1) ^ (uint64_t)(-(int64_t)(v & 1))); }
-
-// the run directory of an RLEv2 stream (LongInputStreamV2.readValues :59-80 and the four readers' header parsing)
-std::vector<Run> scan_rle_v2(const uint8_t *bytes, int64_t len, bool is_signed, int64_t &total)
-{
-    std::vector<Run> runs;
-    HostReader in{bytes, len};
-    total = 0;
-    while (in.at < in.len) {
-        Run r{};
-        const int first = in.read();
-        r.kind = (first >> 6) & 3;
-        r.out_off = total;
-        if (r.kind == SHORT_REPEAT) {   // :255-282
-            const int size = ((first >> 3) & 7) + 1;
-            r.count = (first & 7) + 3;
-            uint64_t v = 0;
-            for (int n = size; n > 0;) {
-                n--;
-                v |= (uint64_t)in.read() << (n * 8);
-            }
-            r.base = is_signed ? zigzag(v) : (int64_t)v;
-            r.in_off = in.at;
-        }
-        else if (r.kind == DIRECT) {   // :229-252
-            r.width = decode_bit_width((first >> 1) & 0x1f);
-            r.count = (((first & 1) << 8) | in.read()) + 1;
-            r.in_off = in.at;
-            in.skip(((int64_t)r.count * r.width + 7) / 8);
-        }
-        else if (r.kind == PATCHED_BASE) {   // :135-226
-            r.width = decode_bit_width((first >> 1) & 0x1f);
-            r.count = (((first & 1) << 8) | in.read()) + 1;
-            const int third = in.read();
-            const int base_width = ((third >> 5) & 7) + 1;
-            r.patch_width = decode_bit_width(third & 0x1f);
-            const int fourth = in.read();
-            r.patch_gap_width = ((fourth >> 5) & 7) + 1;
-            r.patch_count = fourth & 0x1f;
-            uint64_t b = 0;
-            for (int n = base_width; n > 0;) {
-                n--;
-                b |= (uint64_t)in.read() << (n * 8);
-            }
-            const uint64_t mask = 1ull << (base_width * 8 - 1);
-            r.base = (b & mask) ? -(int64_t)(b & ~mask) : (int64_t)b;
-            if (r.patch_width + r.patch_gap_width > 64) fail(TGPU_ERR_INVALID_ARGUMENT, "Invalid RLEv2 encoded stream");
-            r.patch_bits = closest_fixed_bits(r.patch_width + r.patch_gap_width);
-            r.in_off = in.at;
-            in.skip(((int64_t)r.count * r.width + 7) / 8);
-            r.patch_off = in.at;
-            in.skip(((int64_t)r.patch_count * r.patch_bits + 7) / 8);
-        }
-        else {   // DELTA :82-132
-            int fixed_bits = (first >> 1) & 0x1f;
-            if (fixed_bits != 0) fixed_bits = decode_bit_width(fixed_bits);
-            const int length = ((first & 1) << 8) | in.read();
-            const uint64_t fv = in.vint();
-            r.base = is_signed ? zigzag(fv) : (int64_t)fv;
-            r.delta = zigzag(in.vint());
-            r.width = fixed_bits;
-            r.count = length + 1;
-            r.in_off = in.at;
-            if (fixed_bits != 0) {
-                if (length < 1) fail(TGPU_ERR_INVALID_ARGUMENT, "Invalid RLEv2 encoded stream");
-                in.skip(((int64_t)(length - 1) * fixed_bits + 7) / 8);
-            }
-        }
-        total += r.count;
-        runs.push_back(r);
-    }
-    return runs;
-}
-
-// `w` bits at bit offset `bit` of a big-endian bit stream (LongBitPacker.unpackGeneric's order); the buffer has 16 bytes of slack behind it
+// `w` bits at bit offset `bit` of a big-endian bit stream (LongBitPacker.unpackGeneric's order); reads up to walk::kReadBitsReach bytes from the value's first byte: the slack of upload_padded
 __device__ __forceinline__ unsigned long long read_bits(const uint8_t *p, long long bit, int w)
 {
+    static_assert(walk::kReadBitsReach == 9, "read_bits reads q[0] .. q[8]");
     const uint8_t *q = p + (bit >> 3);
     const int sh = (int)(bit & 7);
     unsigned long long x = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) x = (x << 8) | q[i];
+    for (int i = 0; i < walk::kReadBitsReach - 1; i++) x = (x << 8) | q[i];
     if (sh + w <= 64) return w == 64 ? x : ((x << sh) >> (64 - w));
-    return ((x << sh) | ((unsigned long long)q[8] >> (8 - sh))) >> (64 - w);
+    return ((x << sh) | ((unsigned long long)q[walk::kReadBitsReach - 1] >> (8 - sh))) >> (64 - w);
 }
 __device__ __forceinline__ long long dev_zigzag(unsigned long long v) { return (long long)((v >> 1) ^ (unsigned long long)(-(long long)(v & 1))); }
 
 // one wave per run (grid-stride over the runs)
-__global__ void __launch_bounds__(256) rle_v2_decode_kernel(const uint8_t *__restrict__ bytes, const Run *__restrict__ runs, int64_t n_runs, int is_signed,
+__global__ void __launch_bounds__(256) rle_v2_decode_kernel(const uint8_t *__restrict__ bytes, const OrcRun *__restrict__ runs, int64_t n_runs, int is_signed,
                                                             long long *__restrict__ out)
 {
     __shared__ long long s_stage[4][512];
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t ri = wave; ri < n_runs; ri += waves) {
-        const Run r = runs[ri];
+        const OrcRun r = runs[ri];
         long long *o = out + r.out_off;
         const uint8_t *p = bytes + r.in_off;
         if (r.kind == SHORT_REPEAT) {
@@ -208,8 +93,11 @@ __global__ void __launch_bounds__(256) rle_v2_decode_kernel(const uint8_t *__res
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            if (lane < r.patch_count && !(gap == 255 && patch == 0) && pos < (unsigned long long)r.count)
-                stage[pos] = (long long)((unsigned long long)stage[pos] + (patch << r.width));
+            if (lane < r.patch_count && !(gap == 255 && patch == 0) && pos < (unsigned long long)r.count) {
+                // LongInputStreamV2.java:219-222: base + (unpacked | patch << fb), a Java shift (by fb modulo 64: a run of 64-bit values ORs the patch in)
+                const unsigned long long unpacked = (unsigned long long)stage[pos] - (unsigned long long)r.base;
+                stage[pos] = (long long)((unsigned long long)r.base + (unpacked | (patch << (r.width & 63))));
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
             for (int i = lane; i < r.count; i += kWave) o[i] = stage[i];
@@ -248,37 +136,6 @@ __global__ void __launch_bounds__(256) rle_v2_decode_kernel(const uint8_t *__res
             }
         }
     }
-}
-
-struct ByteRun {
-    int64_t in_off, out_off;
-    int32_t count, repeat;   // repeat: one value byte at in_off; else `count` literal bytes
-};
-
-std::vector<ByteRun> scan_byte_rle(const uint8_t *bytes, int64_t len, int64_t &total)   // ByteInputStream.readNextBlock :43-75
-{
-    std::vector<ByteRun> runs;
-    HostReader in{bytes, len};
-    total = 0;
-    while (in.at < in.len) {
-        const int control = in.read();
-        ByteRun r{};
-        r.out_off = total;
-        if ((control & 0x80) == 0) {
-            r.count = control + 3;
-            r.repeat = 1;
-            r.in_off = in.at;
-            in.skip(1);
-        }
-        else {
-            r.count = 0x100 - control;
-            r.in_off = in.at;
-            in.skip(r.count);
-        }
-        total += r.count;
-        runs.push_back(r);
-    }
-    return runs;
 }
 
 __global__ void __launch_bounds__(256) byte_rle_decode_kernel(const uint8_t *__restrict__ bytes, const ByteRun *__restrict__ runs, int64_t n_runs, uint8_t *__restrict__ out)
@@ -360,49 +217,19 @@ __global__ void __launch_bounds__(256) place_lengths_kernel(const int32_t *__res
 
 BufferPtr upload_padded(Context *ctx, const uint8_t *src, int64_t bytes)
 {
-    BufferPtr b = ctx->alloc((size_t)bytes + 32);   // read_bits looks up to 9 bytes past a value's first byte
+    BufferPtr b = ctx->alloc((size_t)bytes + walk::kOrcSlack);   // read_bits looks up to walk::kReadBitsReach bytes past a value's first byte
     if (bytes) ctx->upload(b->ptr(), src, (size_t)bytes);
-    HIP_CHECK(hipMemsetAsync(static_cast<uint8_t *>(b->ptr()) + bytes, 0, 32, ctx->stream()));
+    HIP_CHECK(hipMemsetAsync(static_cast<uint8_t *>(b->ptr()) + bytes, 0, walk::kOrcSlack, ctx->stream()));
     return b;
 }
 
-// every value of an RLEv2 stream as int64 on the device
 // RLEv1 (LongInputStreamV1.java:47-103; files written before Hive 0.12): a control byte < 0x80 = a run of control + 3 values base + i * delta
 // (delta a signed byte, base a varint); else 0x100 - control literal varints.  The host reads the control bytes and walks the varints'
 // continuation bits (it must, to find the next control byte); the device decodes: one lane per run -- a run is at most 130 values.
-std::vector<Run> scan_rle_v1(const uint8_t *bytes, int64_t len, bool is_signed, int64_t &total)
-{
-    std::vector<Run> runs;
-    HostReader in{bytes, len};
-    total = 0;
-    while (in.at < in.len) {
-        Run r{};
-        const int control = in.read();
-        r.out_off = total;
-        if (control < 0x80) {
-            r.kind = V1_RUN;
-            r.count = control + 3;
-            r.delta = (int8_t)in.read();
-            const uint64_t v = in.vint();
-            r.base = is_signed ? zigzag(v) : (int64_t)v;
-            r.in_off = in.at;
-        } else {
-            r.kind = V1_LITERALS;
-            r.count = 0x100 - control;
-            r.in_off = in.at;
-            for (int i = 0; i < r.count; i++) (void)in.vint();
-        }
-        total += r.count;
-        if (total > 0x7fffffffLL) fail(TGPU_ERR_INVALID_ARGUMENT, "ORC stream holds more than 2^31 values");
-        runs.push_back(r);
-    }
-    return runs;
-}
-
-__global__ void __launch_bounds__(256) rle_v1_decode_kernel(const uint8_t *__restrict__ bytes, const Run *__restrict__ runs, int64_t n_runs, int is_signed, long long *__restrict__ out)
+__global__ void __launch_bounds__(256) rle_v1_decode_kernel(const uint8_t *__restrict__ bytes, const OrcRun *__restrict__ runs, int64_t n_runs, int is_signed, long long *__restrict__ out)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_runs; i += (int64_t)gridDim.x * blockDim.x) {
-        const Run r = runs[i];
+        const OrcRun r = runs[i];
         long long *o = out + r.out_off;
         if (r.kind == V1_RUN) {
             for (int k = 0; k < r.count; k++) o[k] = (long long)((unsigned long long)r.base + (unsigned long long)((long long)k * r.delta));
@@ -424,28 +251,29 @@ __global__ void __launch_bounds__(256) rle_v1_decode_kernel(const uint8_t *__res
 
 BufferPtr decode_rle_v1(Context *ctx, const uint8_t *bytes, int64_t len, bool is_signed, int64_t &count)
 {
-    std::vector<Run> runs = scan_rle_v1(bytes, len, is_signed, count);
+    std::vector<OrcRun> runs = scan_rle_v1(bytes, len, is_signed, count);
     BufferPtr out = ctx->alloc((size_t)(count > 0 ? count : 1) * 8);
     if (runs.empty()) return out;
-    BufferPtr dbytes = upload_padded(ctx, bytes, len), druns = ctx->alloc(runs.size() * sizeof(Run));
-    ctx->upload(druns->ptr(), runs.data(), runs.size() * sizeof(Run));
+    BufferPtr dbytes = upload_padded(ctx, bytes, len), druns = ctx->alloc(runs.size() * sizeof(OrcRun));
+    ctx->upload(druns->ptr(), runs.data(), runs.size() * sizeof(OrcRun));
     ProfileScope ps(ctx, "orc_rle_v1_decode");
-    rle_v1_decode_kernel<<<grid_for(ctx, (int64_t)runs.size()), 256, 0, ctx->stream()>>>(dbytes->as<uint8_t>(), druns->as<Run>(), (int64_t)runs.size(), is_signed ? 1 : 0,
+    rle_v1_decode_kernel<<<grid_for(ctx, (int64_t)runs.size()), 256, 0, ctx->stream()>>>(dbytes->as<uint8_t>(), druns->as<OrcRun>(), (int64_t)runs.size(), is_signed ? 1 : 0,
                                                                                        out->as<long long>());
     check_launch("orc_rle_v1_decode");
     ctx->sync();   // `runs` (host) backs the upload
     return out;
 }
 
+// every value of an RLEv2 stream as int64 on the device
 BufferPtr decode_rle_v2(Context *ctx, const uint8_t *bytes, int64_t len, bool is_signed, int64_t &count)
 {
-    std::vector<Run> runs = scan_rle_v2(bytes, len, is_signed, count);
+    std::vector<OrcRun> runs = scan_rle_v2(bytes, len, is_signed, count);
     BufferPtr out = ctx->alloc((size_t)(count > 0 ? count : 1) * 8);
     if (runs.empty()) return out;
-    BufferPtr dbytes = upload_padded(ctx, bytes, len), druns = ctx->alloc(runs.size() * sizeof(Run));
-    ctx->upload(druns->ptr(), runs.data(), runs.size() * sizeof(Run));
+    BufferPtr dbytes = upload_padded(ctx, bytes, len), druns = ctx->alloc(runs.size() * sizeof(OrcRun));
+    ctx->upload(druns->ptr(), runs.data(), runs.size() * sizeof(OrcRun));
     ProfileScope ps(ctx, "orc_rle_v2_decode");
-    rle_v2_decode_kernel<<<grid_for(ctx, (int64_t)runs.size() * kWave), 256, 0, ctx->stream()>>>(dbytes->as<uint8_t>(), druns->as<Run>(), (int64_t)runs.size(), is_signed ? 1 : 0,
+    rle_v2_decode_kernel<<<grid_for(ctx, (int64_t)runs.size() * kWave), 256, 0, ctx->stream()>>>(dbytes->as<uint8_t>(), druns->as<OrcRun>(), (int64_t)runs.size(), is_signed ? 1 : 0,
                                                                                               out->as<long long>());
     check_launch("orc_rle_v2_decode");
     ctx->sync();   // `runs` (host) backs the upload

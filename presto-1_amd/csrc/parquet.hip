@@ -15,6 +15,9 @@
 
 #include "kernels.h"
 
+#define WALK_FAIL(msg) ::tgpu::fail(TGPU_ERR_INVALID_ARGUMENT, (msg))
+#include "stream_walk.h"
+
 #include <rocprim/rocprim.hpp>
 
 #include <cstring>
@@ -28,54 +31,11 @@ constexpr int kWave = 64;
 enum Physical : int32_t { PQ_BOOLEAN = 0, PQ_INT32 = 1, PQ_INT64 = 2, PQ_DOUBLE = 5, PQ_BYTE_ARRAY = 6 };          // parquet.thrift Type
 enum Encoding : int32_t { PQ_PLAIN = 0, PQ_PLAIN_DICTIONARY = 2, PQ_RLE = 3, PQ_DELTA_BINARY_PACKED = 5, PQ_DELTA_LENGTH_BYTE_ARRAY = 6, PQ_DELTA_BYTE_ARRAY = 7, PQ_RLE_DICTIONARY = 8 };                           // parquet.thrift Encoding
 
-struct Run {
-    int64_t in_off;    // bit-packed run: first byte of the packed values
-    int64_t out_off;   // index of the run's first value
-    int32_t count;     // values of the run (the last bit-packed run is cut at the number of values wanted: its tail is padding)
-    int32_t packed;    // 1 = bit-packed, 0 = RLE
-    int64_t value;     // RLE: the repeated value
-};
-
-// the run directory of an RLE / bit-packed hybrid stream (Encodings.md; RunLengthBitPackingHybridDecoder.readNext): header = ULEB128;
-// bit 0 set: (header >> 1) groups of 8 bit-packed values; clear: a run of header >> 1 copies of one value of ceil(bit_width / 8) bytes
-std::vector<Run> scan_hybrid(const uint8_t *bytes, int64_t len, int bit_width, int64_t want)
-{
-    TG_CHECK_ARG(bit_width >= 0 && bit_width <= 32, "Parquet hybrid stream: bit width out of range");
-    std::vector<Run> runs;
-    int64_t at = 0, total = 0;
-    while (total < want) {
-        if (at >= len) fail(TGPU_ERR_INVALID_ARGUMENT, "Parquet hybrid stream ends before the page's values do");
-        uint64_t header = 0;
-        for (int shift = 0;; shift += 7) {
-            if (at >= len || shift > 35) fail(TGPU_ERR_INVALID_ARGUMENT, "Parquet hybrid stream: bad run header");
-            const int b = bytes[at++];
-            header |= (uint64_t)(b & 0x7f) << shift;
-            if (!(b & 0x80)) break;
-        }
-        Run r{};
-        r.out_off = total;
-        if (header & 1) {
-            const int64_t values = (int64_t)(header >> 1) * 8, packed_bytes = (int64_t)(header >> 1) * bit_width;
-            r.packed = 1;
-            r.in_off = at;
-            r.count = (int32_t)std::min<int64_t>(values, want - total);
-            // (writers may cut the padding of the LAST group short: only the bytes the wanted values occupy must be there)
-            if (at + ((int64_t)r.count * bit_width + 7) / 8 > len) fail(TGPU_ERR_INVALID_ARGUMENT, "Parquet hybrid stream: a bit-packed run is longer than the stream");
-            at = std::min<int64_t>(at + packed_bytes, len);
-        } else {
-            const int64_t count = (int64_t)(header >> 1);
-            const int width_bytes = (bit_width + 7) / 8;
-            if (count == 0 || at + width_bytes > len) fail(TGPU_ERR_INVALID_ARGUMENT, "Parquet hybrid stream: bad RLE run");
-            uint64_t v = 0;
-            for (int i = 0; i < width_bytes; i++) v |= (uint64_t)bytes[at++] << (8 * i);
-            r.value = (int64_t)v;
-            r.count = (int32_t)std::min<int64_t>(count, want - total);
-        }
-        total += r.count;
-        runs.push_back(r);
-    }
-    return runs;
-}
+// the run directories and the host walks that build them (and are the kernels' whole bounds check): stream_walk.h
+using Run = walk::HybridRun;
+using walk::Mini;
+using walk::scan_hybrid;
+using walk::scan_byte_arrays;
 
 __global__ void __launch_bounds__(256) hybrid_decode_kernel(const uint8_t *__restrict__ bytes, const Run *__restrict__ runs, int64_t n_runs, int bit_width, int32_t *__restrict__ out)
 {
@@ -90,7 +50,7 @@ __global__ void __launch_bounds__(256) hybrid_decode_kernel(const uint8_t *__res
                 const uint8_t *p = bytes + r.in_off + (bit >> 3);
                 unsigned long long word = 0;
 #pragma unroll
-                for (int k = 0; k < 5; k++) word |= (unsigned long long)p[k] << (8 * k);   // 32 bits at any bit offset span at most 5 bytes (the buffer is padded)
+                for (int k = 0; k < walk::kHybridReach; k++) word |= (unsigned long long)p[k] << (8 * k);   // 32 bits at any bit offset span at most 5 bytes (the buffer is padded)
                 v = (long long)((word >> (bit & 7)) & mask);
             }
             out[r.out_off + i] = (int32_t)v;
@@ -166,9 +126,9 @@ __global__ void __launch_bounds__(256) copy_strings_kernel(const uint8_t *__rest
 
 BufferPtr upload_padded(Context *ctx, const uint8_t *src, int64_t bytes)
 {
-    BufferPtr b = ctx->alloc((size_t)bytes + 16);
+    BufferPtr b = ctx->alloc((size_t)bytes + walk::kParquetSlack);
     if (bytes) ctx->upload(b->ptr(), src, (size_t)bytes);
-    HIP_CHECK(hipMemsetAsync(static_cast<uint8_t *>(b->ptr()) + bytes, 0, 16, ctx->stream()));
+    HIP_CHECK(hipMemsetAsync(static_cast<uint8_t *>(b->ptr()) + bytes, 0, walk::kParquetSlack, ctx->stream()));
     return b;
 }
 
@@ -209,24 +169,6 @@ Present decode_levels(Context *ctx, const uint8_t *def_levels, int64_t def_len, 
     k::exclusive_scan_i32(ctx, flags->as<int32_t>(), p.rank->as<int32_t>(), n, total->as<int64_t>());
     p.non_null = ctx->read_scalar(total->as<int64_t>());
     return p;
-}
-
-// PLAIN BYTE_ARRAY values: where each value's bytes start in `bytes` and how long it is (a 4-byte little-endian length in front of each)
-void scan_byte_arrays(const uint8_t *bytes, int64_t len, int64_t count, std::vector<int32_t> &src_off, std::vector<int32_t> &lengths)
-{
-    src_off.resize((size_t)count);
-    lengths.resize((size_t)count);
-    int64_t at = 0;
-    for (int64_t i = 0; i < count; i++) {
-        if (at + 4 > len) fail(TGPU_ERR_INVALID_ARGUMENT, "Parquet PLAIN BYTE_ARRAY section ends inside a length");
-        uint32_t l;
-        memcpy(&l, bytes + at, 4);
-        at += 4;
-        if (l > 0x7fffffffu || at + (int64_t)l > len) fail(TGPU_ERR_INVALID_ARGUMENT, "Parquet PLAIN BYTE_ARRAY value is longer than its section");
-        src_off[(size_t)i] = (int32_t)at;
-        lengths[(size_t)i] = (int32_t)l;
-        at += l;
-    }
 }
 
 int width_of(int32_t physical)
@@ -310,14 +252,6 @@ DeviceColumn plain_column(Context *ctx, int32_t type, int32_t physical, const ui
 // miniblock, the miniblocks' (delta - min delta) bit-packed least significant bit first.  The host walks the block headers (three varints per
 // 128 values), the device unpacks every miniblock -- one lane per value -- and a prefix sum turns the deltas into values (wrapping 64-bit
 // arithmetic; INT32 keeps the low half).
-struct Mini {
-    int64_t in_off;      // first byte of the miniblock's packed deltas
-    int64_t out_off;     // index of the value its first delta produces (>= 1: value 0 is the header's first value)
-    int64_t min_delta;
-    int32_t count;       // deltas of the miniblock that are values of the page (the last one may be padded)
-    int32_t width;
-};
-
 __global__ void __launch_bounds__(256) delta_unpack_kernel(const uint8_t *__restrict__ bytes, const Mini *__restrict__ minis, int64_t n_minis, unsigned long long *__restrict__ out)
 {
     const int lane = threadIdx.x & 63;
@@ -328,10 +262,11 @@ __global__ void __launch_bounds__(256) delta_unpack_kernel(const uint8_t *__rest
             const int64_t bit = (int64_t)i * mb.width;
             const uint8_t *p = bytes + mb.in_off + (bit >> 3);
             const int sh = (int)(bit & 7);
+            static_assert(walk::kDeltaUnpackReach == 9, "delta_unpack_kernel reads p[0] .. p[8]");
             unsigned long long lo = 0;
-            memcpy(&lo, p, 8);                                   // (the page is uploaded with 16 bytes of padding)
+            memcpy(&lo, p, 8);                                   // (with p[8] below: walk::kDeltaUnpackReach bytes, inside the upload's padding)
             unsigned long long v = lo >> sh;
-            if (sh && mb.width + sh > 64) v |= (unsigned long long)p[8] << (64 - sh);
+            if (sh && mb.width + sh > 64) v |= (unsigned long long)p[walk::kDeltaUnpackReach - 1] << (64 - sh);
             out[mb.out_off + i] = (v & mask) + (unsigned long long)mb.min_delta;
         }
     }
@@ -343,52 +278,13 @@ __global__ void __launch_bounds__(256) place_low_half_kernel(const long long *__
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) out[r] = (nulls && nulls[r]) ? 0 : (int32_t)compact[rank ? rank[r] : r];
 }
 
-static bool read_uleb(const uint8_t *bytes, int64_t len, int64_t &at, uint64_t &out)
-{
-    uint64_t v = 0;
-    for (int shift = 0;; shift += 7) {
-        if (at >= len || shift > 63) return false;
-        const int b = bytes[at++];
-        v |= (uint64_t)(b & 0x7f) << shift;
-        if (!(b & 0x80)) break;
-    }
-    out = v;
-    return true;
-}
-
 // `want` DELTA_BINARY_PACKED values on the device as wrapping 64-bit integers (want >= 1); *end = the bytes the section takes
 BufferPtr delta_values(Context *ctx, const uint8_t *bytes, int64_t len, int64_t want, int64_t *end)
 {
-    int64_t at = 0;
-    uint64_t block_size, miniblocks, total, zz;
-    TG_CHECK_ARG(read_uleb(bytes, len, at, block_size) && read_uleb(bytes, len, at, miniblocks) && read_uleb(bytes, len, at, total) && read_uleb(bytes, len, at, zz),
-                 "Parquet DELTA_BINARY_PACKED header cut short");
-    TG_CHECK_ARG(miniblocks > 0 && miniblocks <= 4096 && block_size > 0 && block_size % 128 == 0 && block_size % miniblocks == 0 && (block_size / miniblocks) % 32 == 0,
-                 "Parquet DELTA_BINARY_PACKED block shape outside the specification");
-    TG_CHECK_ARG((int64_t)total >= want, "Parquet DELTA_BINARY_PACKED section holds fewer values than the page has non-null positions");
-    const int64_t mini = (int64_t)(block_size / miniblocks);
-    const uint64_t first = (zz >> 1) ^ (~(zz & 1) + 1);
-    std::vector<Mini> minis;
-    for (int64_t done = 1; done < want;) {
-        uint64_t zmin;
-        TG_CHECK_ARG(read_uleb(bytes, len, at, zmin) && at + (int64_t)miniblocks <= len, "Parquet DELTA_BINARY_PACKED block header cut short");
-        const uint64_t min_delta = (zmin >> 1) ^ (~(zmin & 1) + 1);
-        const uint8_t *widths = bytes + at;
-        at += (int64_t)miniblocks;
-        for (uint64_t m = 0; m < miniblocks && done < want; m++) {
-            const int width = widths[m];
-            TG_CHECK_ARG(width <= 64 && at + mini * width / 8 <= len, "Parquet DELTA_BINARY_PACKED miniblock cut short");
-            Mini mb;
-            mb.in_off = at;
-            mb.out_off = done;
-            mb.min_delta = (int64_t)min_delta;
-            mb.count = (int32_t)std::min<int64_t>(mini, want - done);
-            mb.width = width;
-            minis.push_back(mb);
-            done += mb.count;
-            at += mini * width / 8;
-        }
-    }
+    const walk::DeltaPlan plan = walk::scan_delta(bytes, len, want);
+    const std::vector<Mini> &minis = plan.minis;
+    const uint64_t first = plan.first;
+    const int64_t at = plan.end;
     if (end) *end = at;
     // deltas (slot 0: the first value) -> inclusive prefix sum = the values
     BufferPtr seq = ctx->alloc((size_t)want * 8), sums = ctx->alloc((size_t)want * 8);
