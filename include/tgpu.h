@@ -224,7 +224,65 @@ typedef enum tgpu_expr_op {
     TGPU_OP_SUBSTR = 17,
     TGPU_OP_CONCAT = 18,
     TGPU_OP_STRPOS = 19,
-    TGPU_OP_STARTS_WITH = 20
+    TGPU_OP_STARTS_WITH = 20,
+    /* DATE functions (M/operator/scalar/DateTimeFunctions.java), over TGPU_DATE = int32 days since 1970-01-01.
+     *
+     * Calendar.  The proleptic Gregorian (ISO) calendar in UTC with astronomical year numbering -- year 0 exists, negative years are allowed --
+     * which is what Joda's ISOChronology.getInstanceUTC() gives.  It holds for every int32 day count: day -2147483648 is -5877641-06-23, a
+     * Tuesday, and day 2147483647 is 5881580-07-11, a Friday.  No extraction raises an error.
+     *
+     *   TGPU_OP_YEAR              (DATE) -> BIGINT   yearFromDate :517-523
+     *   TGPU_OP_QUARTER           (DATE) -> BIGINT   quarterFromDate :509-515: (month - 1) / 3 + 1
+     *   TGPU_OP_MONTH             (DATE) -> BIGINT   monthFromDate :493-499
+     *   TGPU_OP_WEEK              (DATE) -> BIGINT   weekFromDate :477-483: the ISO-8601 week of the week-year.  With thu = days - (day_of_week - 1) + 3,
+     *                             the Thursday of the value's week: week = (day_of_year(thu) - 1) / 7 + 1
+     *   TGPU_OP_DAY               (DATE) -> BIGINT   dayFromDate :444-450: the day of the month
+     *   TGPU_OP_DAY_OF_WEEK       (DATE) -> BIGINT   dayOfWeekFromDate :436-442: floormod(days + 3, 7) + 1, Monday = 1 ... Sunday = 7
+     *   TGPU_OP_DAY_OF_YEAR       (DATE) -> BIGINT   dayOfYearFromDate :469-475
+     *   TGPU_OP_YEAR_OF_WEEK      (DATE) -> BIGINT   yearOfWeekFromDate :485-491: year(thu)
+     *   TGPU_OP_LAST_DAY_OF_MONTH (DATE) -> DATE     lastDayOfMonthFromDate :460-467: same year and month, last day
+     *   TGPU_OP_DATE_TRUNC        (VARCHAR unit, DATE) -> DATE                truncateDate :260-268.  day: the value itself; week: the Monday on or
+     *                             before it; month, quarter, year: the first day of the period
+     *   TGPU_OP_DATE_ADD          (VARCHAR unit, BIGINT value, DATE) -> DATE  addFieldValueDate :270-278.  day: d + v; week: d + 7v; month: the
+     *                             (year, month) moves by v months and the day of the month is clamped to the target month's length (Jan 31 + 1
+     *                             month = Feb 28 or Feb 29); quarter: 3v months; year: 12v months (Feb 29 + 1 year = Feb 28)
+     *   TGPU_OP_DATE_DIFF         (VARCHAR unit, DATE d1, DATE d2) -> BIGINT  diffDate :280-287.  For d2 >= d1 the largest n >= 0 with
+     *                             date_add(unit, n, d1) <= d2 (date_add unbounded here); for d2 < d1 it is -date_diff(unit, d2, d1).  day and week
+     *                             reduce to (d2 - d1) / {1, 7} truncated toward zero
+     *
+     * Units.  The unit is 'day', 'week', 'month', 'quarter' or 'year', matched after ASCII lower-casing (getDateField :289-305 uses
+     * toLowerCase(ENGLISH)).  It must be a TGPU_EX_CONST VARCHAR node (TGPU_ERR_NOT_SUPPORTED otherwise): the generator reads it, it is never
+     * evaluated as a value.  Any other string fails when the factory is created with TGPU_ERR_INVALID_ARGUMENT and the reference's message
+     * "'<lower-cased unit>' is not a valid DATE field".  A null unit constant gives NULL for every row and the other arguments are not evaluated:
+     * the usual first-null-argument rule, which holds for the other arguments too.  Wrong argument types, result type or argument count:
+     * TGPU_ERR_COMPILER.
+     *
+     * Deviation (int32 DATE).  The reference does toIntExact(value), computes in a long and fails only when a too-large day count is written
+     * to an int block (S/type/AbstractIntType.java:85-95).  The library's DATE is int32 everywhere: a row fails with
+     * TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE when date_add's value lies outside int32 or when the DATE result of date_add, date_trunc or
+     * last_day_of_month lies outside int32 days (date_trunc in the range's first year, whose first days lie before it; last_day_of_month in its last 11 days).  It
+     * fails like the checked arithmetic ops do, with the same rule for which error of a page wins.  No intermediate value overflows silently.
+     *
+     * Deviation (date_diff).  The rule above was compared with a restatement of Joda's getDifferenceAsLong (BasicMonthOfYearDateTimeField,
+     * getYearDifference) on 300,000 date pairs biased to month ends and leap days without a mismatch for month, quarter and year, but Joda's
+     * source is not part of the reference tree: beyond the reference's test literals Joda parity unpinned; the rule above is what the library
+     * guarantees.
+     *
+     * Out of the IR: CAST between DATE and any other type (TGPU_ERR_COMPILER), the TIMESTAMP / TIME / INTERVAL variants of these functions,
+     * date_format / date_parse / to_iso8601 / current_date and the date + interval operators (a planner folds constant intervals into
+     * date_add). */
+    TGPU_OP_YEAR = 21,
+    TGPU_OP_QUARTER = 22,
+    TGPU_OP_MONTH = 23,
+    TGPU_OP_WEEK = 24,
+    TGPU_OP_DAY = 25,
+    TGPU_OP_DAY_OF_WEEK = 26,
+    TGPU_OP_DAY_OF_YEAR = 27,
+    TGPU_OP_YEAR_OF_WEEK = 28,
+    TGPU_OP_LAST_DAY_OF_MONTH = 29,
+    TGPU_OP_DATE_TRUNC = 30,
+    TGPU_OP_DATE_ADD = 31,
+    TGPU_OP_DATE_DIFF = 32
 } tgpu_expr_op;
 typedef enum tgpu_special_form { /* M/sql/relational/SpecialForm.java:137-152 */
     TGPU_SF_AND = 1, TGPU_SF_OR, TGPU_SF_IF, TGPU_SF_IS_NULL, TGPU_SF_COALESCE, TGPU_SF_BETWEEN,

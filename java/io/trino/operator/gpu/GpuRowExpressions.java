@@ -1,6 +1,7 @@
 package io.trino.operator.gpu;
 
 import io.airlift.slice.Slice;
+import io.trino.spi.type.DateType;
 import io.trino.spi.type.Type;
 import io.trino.spi.type.VarcharType;
 import io.trino.sql.relational.CallExpression;
@@ -34,6 +35,10 @@ public final class GpuRowExpressions
     // :321, starts_with :909) and operator/scalar/ConcatFunction.java ("concat"), over varchar arguments
     private static final int OP_CAST = 14, OP_LENGTH = 16, OP_SUBSTR = 17, OP_CONCAT = 18, OP_STRPOS = 19, OP_STARTS_WITH = 20;
     private static final String CAST_OPERATOR = "$operator$CAST";
+    // TGPU_OP_YEAR .. TGPU_OP_DATE_DIFF: operator/scalar/DateTimeFunctions.java over DATE (truncateDate :260, addFieldValueDate :270, diffDate :280,
+    // dayOfWeekFromDate :436 ... yearFromDate :517)
+    private static final int OP_YEAR = 21, OP_QUARTER = 22, OP_MONTH = 23, OP_WEEK = 24, OP_DAY = 25, OP_DAY_OF_WEEK = 26, OP_DAY_OF_YEAR = 27, OP_YEAR_OF_WEEK = 28;
+    private static final int OP_LAST_DAY_OF_MONTH = 29, OP_DATE_TRUNC = 30, OP_DATE_ADD = 31, OP_DATE_DIFF = 32;
 
     public static final class Program
     {
@@ -121,6 +126,11 @@ public final class GpuRowExpressions
             if (stringOp != 0) {
                 return addStringFunction(p, type, stringOp, call.getArguments());
             }
+            int dateOp = dateFunction(name, call.getArguments().size());
+            if (dateOp != 0 && overDates(dateOp, call.getArguments())) {
+                int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
+                return emit(p, CALL, type, dateOp, args, false, 0, 0, 0);
+            }
             for (int op = 1; op < OPERATORS.length; op++) {
                 if (OPERATORS[op].equalsIgnoreCase(name)) {
                     int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
@@ -168,6 +178,51 @@ public final class GpuRowExpressions
             case "starts_with": return arguments == 2 ? OP_STARTS_WITH : 0;
             default: return 0;
         }
+    }
+
+    /**
+     * The names and aliases of DateTimeFunctions.java's DATE functions -> TGPU_OP_YEAR .. TGPU_OP_DATE_DIFF.  EXTRACT(field FROM d) arrives
+     * as these function names.  d + INTERVAL arrives as an interval operator, which is outside the IR: a planner that wants it on the device
+     * folds a constant interval into date_add first.
+     */
+    private static int dateFunction(String name, int arguments)
+    {
+        switch (name.toLowerCase(java.util.Locale.ENGLISH)) {
+            case "year": return arguments == 1 ? OP_YEAR : 0;
+            case "quarter": return arguments == 1 ? OP_QUARTER : 0;
+            case "month": return arguments == 1 ? OP_MONTH : 0;
+            case "week":
+            case "week_of_year": return arguments == 1 ? OP_WEEK : 0;
+            case "day":
+            case "day_of_month": return arguments == 1 ? OP_DAY : 0;
+            case "day_of_week":
+            case "dow": return arguments == 1 ? OP_DAY_OF_WEEK : 0;
+            case "day_of_year":
+            case "doy": return arguments == 1 ? OP_DAY_OF_YEAR : 0;
+            case "year_of_week":
+            case "yow": return arguments == 1 ? OP_YEAR_OF_WEEK : 0;
+            case "last_day_of_month": return arguments == 1 ? OP_LAST_DAY_OF_MONTH : 0;
+            case "date_trunc": return arguments == 2 ? OP_DATE_TRUNC : 0;
+            case "date_add": return arguments == 3 ? OP_DATE_ADD : 0;
+            case "date_diff": return arguments == 3 ? OP_DATE_DIFF : 0;
+            default: return 0;
+        }
+    }
+
+    /**
+     * The same names exist over timestamps, times and intervals: only the DATE flavour is in the IR, every other one falls through to
+     * "function not in the GPU IR".  The unit of date_trunc / date_add / date_diff is a varchar, which the library wants constant.
+     */
+    private static boolean overDates(int op, List<RowExpression> arguments)
+    {
+        if (op < OP_DATE_TRUNC) {
+            return arguments.get(0).getType() instanceof DateType;
+        }
+        if (!(arguments.get(0).getType() instanceof VarcharType)) {
+            return false;
+        }
+        boolean dates = arguments.get(arguments.size() - 1).getType() instanceof DateType;
+        return op == OP_DATE_DIFF ? dates && arguments.get(1).getType() instanceof DateType : dates;
     }
 
     /**

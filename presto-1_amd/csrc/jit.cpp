@@ -641,6 +641,7 @@ struct Gen {
         case TGPU_EX_CALL:
             if (nd.op == TGPU_OP_LIKE) return gen_like(nd, idx, d);
             if ((nd.op >= TGPU_OP_LENGTH && nd.op <= TGPU_OP_STARTS_WITH) || (nd.op == TGPU_OP_CAST && nd.type == TGPU_VARCHAR)) return gen_string(nd, idx, d);
+            if (nd.op >= TGPU_OP_YEAR && nd.op <= TGPU_OP_DATE_DIFF) return gen_date(nd, d);
             return gen_call(nd, d);
         case TGPU_EX_SPECIAL: return nd.op == TGPU_SF_IN ? gen_in(nd, idx, d) : gen_special(nd, idx, d);
         default: bad("unknown node kind");
@@ -799,6 +800,86 @@ struct Gen {
             else bad("unsupported cast");
         }
         for (int k = 0; k < nd.n_args; k++) os << ind(--dd) << "}\n";
+        os << ind(d) << "}\n";
+        return r;
+    }
+
+    // ---- DATE functions (M/operator/scalar/DateTimeFunctions.java); the arithmetic is csrc/device_date.h ------------------------------
+    bool date_helpers = false;
+
+    void need_date_helpers()
+    {
+        if (!date_helpers) consts << device_header("device_date.h");   // (guarded by its own #ifndef: several generators feed one module)
+        date_helpers = true;
+    }
+
+    // getDateField :289-305: the unit after ASCII lower-casing -> TG_DATE_UNIT_*
+    static int date_unit(const std::string &text)
+    {
+        std::string u = text;
+        for (char &c : u)
+            if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+        static const char *kUnits[] = {"day", "week", "month", "quarter", "year"};
+        for (int i = 0; i < 5; i++)
+            if (u == kUnits[i]) return i;
+        fail(TGPU_ERR_INVALID_ARGUMENT, "'" + u + "' is not a valid DATE field");
+    }
+
+    Val gen_date(const tgpu_expr_node &nd, int d)
+    {
+        static const char *kNames[] = {"YEAR", "QUARTER", "MONTH", "WEEK", "DAY", "DAY_OF_WEEK", "DAY_OF_YEAR", "YEAR_OF_WEEK", "LAST_DAY_OF_MONTH", "DATE_TRUNC", "DATE_ADD", "DATE_DIFF"};
+        static const char *kFields[] = {"year", "quarter", "month", "week", "day", "day_of_week", "day_of_year", "year_of_week"};
+        const std::string name = kNames[nd.op - TGPU_OP_YEAR];
+        const bool has_unit = nd.op >= TGPU_OP_DATE_TRUNC;
+        const int arity = nd.op == TGPU_OP_DATE_TRUNC ? 2 : has_unit ? 3 : 1;
+        if (nd.n_args != arity) bad(name + ": wrong number of arguments");
+        const bool date_result = nd.op == TGPU_OP_LAST_DAY_OF_MONTH || nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD;
+        if (nd.type != (date_result ? TGPU_DATE : TGPU_BIGINT)) bad(name + ": wrong result type");
+        const int first = has_unit ? 1 : 0;
+        for (int k = 0; k < nd.n_args; k++) {
+            const int32_t want = k < first ? TGPU_VARCHAR : (nd.op == TGPU_OP_DATE_ADD && k == 1) ? TGPU_BIGINT : TGPU_DATE;
+            if (node(nd.args[k]).type != want) bad(name + ": wrong argument type");
+        }
+        int unit = -1;
+        bool null_unit = false;
+        if (has_unit) {
+            const tgpu_expr_node &un = node(nd.args[0]);
+            if (un.kind != TGPU_EX_CONST) fail(TGPU_ERR_NOT_SUPPORTED, name + ": the unit must be a VARCHAR constant");
+            null_unit = un.is_null != 0;
+            if (!null_unit) unit = date_unit(const_text(un));
+        }
+        Val r = declare(nd.type, d);
+        if (null_unit) {   // the first argument is null: the others are not evaluated
+            os << ind(d) << r.n << " = true;\n";
+            return r;
+        }
+        if (!(nd.op == TGPU_OP_DATE_TRUNC && unit == 0)) need_date_helpers();   // date_trunc('day', d) is d
+        // arguments left to right; the first null argument skips the rest and the call
+        os << ind(d) << "{\n";
+        std::vector<Val> a;
+        int dd = d + 1;
+        for (int k = first; k < nd.n_args; k++) {
+            a.push_back(gen(nd.args[k], dd));
+            os << ind(dd) << "if (" << a.back().n << ") " << r.n << " = true; else {\n";
+            dd++;
+        }
+        const std::string u = std::to_string(unit);
+        // a DATE result that is no int32 day count (and date_add's amount outside int32) raises like the checked arithmetic does
+        auto checked = [&](const std::string &call) {
+            os << ind(dd) << "int o_ = 0; const int t_ = " << call << ";\n";
+            os << ind(dd) << "if (o_) { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = t_;\n";
+        };
+        switch (nd.op) {
+        case TGPU_OP_LAST_DAY_OF_MONTH: checked("tg_date_last_day_of_month(" + a[0].v + ", &o_)"); break;
+        case TGPU_OP_DATE_TRUNC:
+            if (unit == 0) os << ind(dd) << r.v << " = " << a[0].v << ";\n";
+            else checked("tg_date_trunc(" + u + ", " + a[0].v + ", &o_)");
+            break;
+        case TGPU_OP_DATE_ADD: checked("tg_date_add(" + u + ", " + a[0].v + ", " + a[1].v + ", &o_)"); break;
+        case TGPU_OP_DATE_DIFF: os << ind(dd) << r.v << " = tg_date_diff(" << u << ", " << a[0].v << ", " << a[1].v << ");\n"; break;
+        default: os << ind(dd) << r.v << " = tg_date_" << kFields[nd.op - TGPU_OP_YEAR] << "(" << a[0].v << ");\n";
+        }
+        for (int k = first; k < nd.n_args; k++) os << ind(--dd) << "}\n";
         os << ind(d) << "}\n";
         return r;
     }
@@ -2558,6 +2639,7 @@ FusedProbeGpu::FusedProbeGpu(std::vector<int32_t> input_types, const tgpu_page_p
             const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
             if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;
             if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
+            if (nd.op == TGPU_OP_LAST_DAY_OF_MONTH || nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD) return true;   // a DATE result outside int32 days
             if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
                 const int32_t from = nodes_[(size_t)nd.args[0]].type;
                 if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;
@@ -3642,6 +3724,7 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
             const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
             if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;
             if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
+            if (nd.op == TGPU_OP_LAST_DAY_OF_MONTH || nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD) return true;   // a DATE result outside int32 days
             if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
                 const int32_t from = nodes_[(size_t)nd.args[0]].type;
                 if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;

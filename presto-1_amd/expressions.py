@@ -12,7 +12,9 @@ from .spi import BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR
 EX_INPUT, EX_CONST, EX_CALL, EX_SPECIAL = 0, 1, 2, 3
 OPS = {"ADD": 1, "SUBTRACT": 2, "MULTIPLY": 3, "DIVIDE": 4, "MODULUS": 5, "NEGATE": 6, "EQUAL": 7, "NOT_EQUAL": 8,
        "LESS_THAN": 9, "LESS_THAN_OR_EQUAL": 10, "GREATER_THAN": 11, "GREATER_THAN_OR_EQUAL": 12, "NOT": 13, "CAST": 14, "LIKE": 15,
-       "LENGTH": 16, "SUBSTR": 17, "CONCAT": 18, "STRPOS": 19, "STARTS_WITH": 20}
+       "LENGTH": 16, "SUBSTR": 17, "CONCAT": 18, "STRPOS": 19, "STARTS_WITH": 20,
+       "YEAR": 21, "QUARTER": 22, "MONTH": 23, "WEEK": 24, "DAY": 25, "DAY_OF_WEEK": 26, "DAY_OF_YEAR": 27, "YEAR_OF_WEEK": 28,
+       "LAST_DAY_OF_MONTH": 29, "DATE_TRUNC": 30, "DATE_ADD": 31, "DATE_DIFF": 32}
 FORMS = {"AND": 1, "OR": 2, "IF": 3, "IS_NULL": 4, "COALESCE": 5, "BETWEEN": 6, "IN": 7}
 _CMP = {"EQUAL", "NOT_EQUAL", "LESS_THAN", "LESS_THAN_OR_EQUAL", "GREATER_THAN", "GREATER_THAN_OR_EQUAL"}
 
@@ -127,6 +129,33 @@ def strpos(x, sub):
 
 def starts_with(x, prefix):
     return call("STARTS_WITH", BOOLEAN, _wrap(x, VARCHAR), _wrap(prefix, VARCHAR))
+
+
+# DATE functions: extraction gives BIGINT; a Python int stands for a DATE constant (days since 1970-01-01), None for the null literal
+def year(d): return call("YEAR", BIGINT, _wrap(d, DATE))
+def quarter(d): return call("QUARTER", BIGINT, _wrap(d, DATE))
+def month(d): return call("MONTH", BIGINT, _wrap(d, DATE))
+def week(d): return call("WEEK", BIGINT, _wrap(d, DATE))
+def day(d): return call("DAY", BIGINT, _wrap(d, DATE))
+def day_of_week(d): return call("DAY_OF_WEEK", BIGINT, _wrap(d, DATE))
+def day_of_year(d): return call("DAY_OF_YEAR", BIGINT, _wrap(d, DATE))
+def year_of_week(d): return call("YEAR_OF_WEEK", BIGINT, _wrap(d, DATE))
+def last_day_of_month(d): return call("LAST_DAY_OF_MONTH", DATE, _wrap(d, DATE))
+
+
+def date_trunc(unit, d):
+    """date_trunc(unit, d); unit: 'day', 'week', 'month', 'quarter' or 'year' in any case (a str, None = the null literal), a constant"""
+    return call("DATE_TRUNC", DATE, _wrap(unit, VARCHAR), _wrap(d, DATE))
+
+
+def date_add(unit, value, d):
+    """date_add(unit, value, d): value a BIGINT expression or a Python int; months clamp the day of the month to the target month"""
+    return call("DATE_ADD", DATE, _wrap(unit, VARCHAR), _wrap(value, BIGINT), _wrap(d, DATE))
+
+
+def date_diff(unit, d1, d2):
+    """date_diff(unit, d1, d2): the whole units from d1 to d2, negative when d2 < d1"""
+    return call("DATE_DIFF", BIGINT, _wrap(unit, VARCHAR), _wrap(d1, DATE), _wrap(d2, DATE))
 
 
 class FlatProgram:
