@@ -17,7 +17,6 @@
 
 #include <algorithm>
 #include <fstream>
-#include <functional>
 #include <list>
 #include <tuple>
 #include <set>
@@ -508,7 +507,7 @@ struct Gen {
     bool reg_mode = false;
     std::set<int> reg_cols;
 
-    Gen(const std::vector<tgpu_expr_node> &n, const std::string &p, const std::vector<int32_t> &t) : nodes(n), pool(p), in_types(t) {}
+    explicit Gen(const ExprProgram &p) : nodes(p.nodes), pool(p.pool), in_types(p.input_types) {}
 
     std::string ind(int d) { return std::string((size_t)d * 2, ' '); }
 
@@ -886,31 +885,41 @@ struct Gen {
 
     static bool is_cmp(int op) { return op >= TGPU_OP_EQUAL && op <= TGPU_OP_GREATER_THAN_OR_EQUAL; }
 
-    // x = 'constant': every piece lies inside [x, x + len) -- a last piece that is not a whole one overlaps its predecessor instead of
-    // reaching past the end (the last string of a pool ends where the allocation ends)
-    static std::string varchar_equals_const(const Val &x, const std::string &k)
+    // How L bytes at p are compared with a constant: as 8- / 4- / 1-byte pieces (at, width).  Every piece lies inside [p, p + L) -- a last
+    // piece that is not a whole one overlaps its predecessor instead of reaching past the end (the last string of a pool ends where the
+    // allocation ends).
+    static std::vector<std::pair<int, int>> equal_pieces(int L)
     {
-        const int L = (int)k.size();
-        auto imm = [&](int at, int w) {
-            unsigned long long v = 0;
-            for (int i = w - 1; i >= 0; i--) v = (v << 8) | (unsigned char)k[(size_t)(at + i)];
-            return std::to_string(v) + (w == 8 ? "ULL" : "U");
-        };
-        auto piece = [&](int at, int w) {
-            if (w == 1) return "(unsigned)" + x.v + "[" + std::to_string(at) + "] == " + imm(at, 1);
-            return std::string(w == 8 ? "tg_load8(" : "tg_load4(") + x.v + " + " + std::to_string(at) + ") == " + imm(at, w);
-        };
-        std::string e = "(" + x.len + " == " + std::to_string(L);
+        std::vector<std::pair<int, int>> pieces;
         int i = 0;
-        for (; L - i >= 8; i += 8) e += " && " + piece(i, 8);
+        for (; L - i >= 8; i += 8) pieces.push_back({i, 8});
         if (i < L) {
-            if (L >= 8) e += " && " + piece(L - 8, 8);
+            if (L >= 8) pieces.push_back({L - 8, 8});
             else if (L >= 4) {
-                e += " && " + piece(0, 4);
-                if (L > 4) e += " && " + piece(L - 4, 4);
+                pieces.push_back({0, 4});
+                if (L > 4) pieces.push_back({L - 4, 4});
             }
             else
-                for (; i < L; i++) e += " && " + piece(i, 1);
+                for (; i < L; i++) pieces.push_back({i, 1});
+        }
+        return pieces;
+    }
+
+    // the piece of k at `at` as the immediate a little-endian load of its width gives
+    static std::string imm(const std::string &k, int at, int w)
+    {
+        unsigned long long v = 0;
+        for (int i = w - 1; i >= 0; i--) v = (v << 8) | (unsigned char)k[(size_t)(at + i)];
+        return std::to_string(v) + (w == 8 ? "ULL" : "U");
+    }
+
+    // x = 'constant': the length first, then the pieces
+    static std::string varchar_equals_const(const Val &x, const std::string &k)
+    {
+        std::string e = "(" + x.len + " == " + std::to_string(k.size());
+        for (auto [at, w] : equal_pieces((int)k.size())) {
+            if (w == 1) e += " && (unsigned)" + x.v + "[" + std::to_string(at) + "] == " + imm(k, at, 1);
+            else e += std::string(w == 8 ? " && tg_load8(" : " && tg_load4(") + x.v + " + " + std::to_string(at) + ") == " + imm(k, at, w);
         }
         return e + ")";
     }
@@ -1138,32 +1147,15 @@ struct Gen {
                << (count ? body : "0") << "};\n#endif\n";
     }
 
-    // the bytes at p equal k, compared as 8- / 4- / 1-byte immediates; every piece lies inside [p, p + |k|) (see varchar_equals_const)
+    // the bytes at p equal k (the pieces of equal_pieces; p is an expression, hence the parentheses)
     static std::string bytes_at(const std::string &p, const std::string &k)
     {
-        const int L = (int)k.size();
-        if (L == 0) return "true";
-        auto imm = [&](int at, int w) {
-            unsigned long long v = 0;
-            for (int i = w - 1; i >= 0; i--) v = (v << 8) | (unsigned char)k[(size_t)(at + i)];
-            return std::to_string(v) + (w == 8 ? "ULL" : "U");
-        };
-        auto piece = [&](int at, int w) {
-            if (w == 1) return "(unsigned)(" + p + ")[" + std::to_string(at) + "] == " + imm(at, 1);
-            return std::string(w == 8 ? "tg_load8((" : "tg_load4((") + p + ") + " + std::to_string(at) + ") == " + imm(at, w);
-        };
+        if (k.empty()) return "true";
         std::string e = "(";
-        int i = 0;
-        auto add = [&](const std::string &s) { e += (e.size() > 1 ? " && " : "") + s; };
-        for (; L - i >= 8; i += 8) add(piece(i, 8));
-        if (i < L) {
-            if (L >= 8) add(piece(L - 8, 8));
-            else if (L >= 4) {
-                add(piece(0, 4));
-                if (L > 4) add(piece(L - 4, 4));
-            }
-            else
-                for (; i < L; i++) add(piece(i, 1));
+        for (auto [at, w] : equal_pieces((int)k.size())) {
+            if (e.size() > 1) e += " && ";
+            if (w == 1) e += "(unsigned)(" + p + ")[" + std::to_string(at) + "] == " + imm(k, at, 1);
+            else e += std::string(w == 8 ? "tg_load8((" : "tg_load4((") + p + ") + " + std::to_string(at) + ") == " + imm(k, at, w);
         }
         return e + ")";
     }
@@ -1502,36 +1494,133 @@ __device__ inline double tg_round_half_away(double x) {
 #define TG_STRIPES 4
 )SRC";
 
+// The column pointers a generated function of the fused kernels declares for the channels its expressions read from memory.  `no_nulls` names
+// the macro of the specialisation for pages without null vectors (FJ_NO_NULLS / FA_NO_NULLS).
+std::string fused_cols_decl(const Gen &g, const char *no_nulls)
+{
+    std::ostringstream cols;
+    for (int ch : g.used_cols) {
+        const int32_t t = g.in_types[(size_t)ch];
+        const char *T = (t == TGPU_VARCHAR || t == TGPU_BOOLEAN) ? "unsigned char" : ctype(t);
+        cols << "  const " << T << "* c" << ch << " = (const " << T << "*)A.col_values[" << ch << "]; (void)c" << ch << ";\n";
+        cols << "  const unsigned char* cn" << ch << " = " << no_nulls << " ? (const unsigned char*)0 : A.col_nulls[" << ch << "]; (void)cn" << ch << ";\n";
+        if (t == TGPU_VARCHAR) cols << "  const int* co" << ch << " = A.col_offsets[" << ch << "]; (void)co" << ch << ";\n";
+    }
+    return cols.str();
+}
+
+// The pre-loaded row of register-row mode (Gen::reg_mode): struct `name` with one field pair (c<ch>, n<ch>) per channel of `cols`, its
+// loader tg_load_<suffix> and tg_zero_<suffix>.  by_tile: the loader addresses a row as tile base + lane offset, (column + tb)[o], else as
+// column[row].  carry_cols: further channels that exist under #if FJ_CARRY only (what only the join's carried outputs read).
+std::string row_decl(const std::vector<int32_t> &in_types, const char *name, const char *suffix, const std::set<int> &cols, bool by_tile, const char *no_nulls,
+                     const std::vector<int> *carry_cols = nullptr)
+{
+    auto ftype = [&](int ch) { return in_types[(size_t)ch] == TGPU_BOOLEAN ? "unsigned char" : ctype(in_types[(size_t)ch]); };
+    std::ostringstream s;
+    // one line per channel of `cols`, then the carry-only channels inside their guard
+    auto each = [&](auto line) {
+        for (int ch : cols) line(ch);
+        if (!carry_cols) return;
+        s << "#if FJ_CARRY\n";
+        for (int ch : *carry_cols) line(ch);
+        s << "#endif\n";
+    };
+    s << "struct " << name << " {\n";
+    each([&](int ch) { s << "  " << ftype(ch) << " c" << ch << "; unsigned char n" << ch << ";\n"; });
+    if (cols.empty()) s << "  int unused;\n";
+    s << "};\n__device__ inline void tg_load_" << suffix << "(const FpArgs& A, " << (by_tile ? "long long tb, unsigned int o, " : "long long row, ") << name << "& R) {\n";
+    each([&](int ch) {
+        const std::string values = "(const " + std::string(ftype(ch)) + "*)A.col_values[" + std::to_string(ch) + "]", nulls = "A.col_nulls[" + std::to_string(ch) + "]";
+        s << "  R.c" << ch << " = (" << values << (by_tile ? " + tb)[o]" : ")[row]") << "; R.n" << ch << " = (!" << no_nulls << " && " << nulls << ") ? "
+          << (by_tile ? "(" + nulls + " + tb)[o]" : nulls + "[row]") << " : 0;\n";
+    });
+    s << "  (void)A; " << (by_tile ? "(void)tb; (void)o;" : "(void)row;") << " (void)R;\n}\n__device__ inline void tg_zero_" << suffix << "(" << name << "& R) {\n";
+    each([&](int ch) { s << "  R.c" << ch << " = 0; R.n" << ch << " = 0;\n"; });
+    s << "  (void)R;\n}\n";
+    return s.str();
+}
+
 }  // namespace
 
-PageProcessorGpu::PageProcessorGpu(std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec) : input_types_(std::move(input_types))
+ExprProgram::ExprProgram(std::vector<int32_t> types, const tgpu_page_processor_spec *spec) : input_types(std::move(types))
 {
     TG_CHECK_ARG(spec != nullptr, "page processor spec is null");
     TG_CHECK_ARG(spec->node_count >= 0 && (spec->node_count == 0 || spec->nodes != nullptr), "bad node array");
-    nodes_.assign(spec->nodes, spec->nodes + spec->node_count);
-    if (spec->string_pool && spec->string_pool_len > 0) pool_.assign(spec->string_pool, spec->string_pool + spec->string_pool_len);
-    filter_root_ = spec->filter_root;
-    TG_CHECK_ARG(spec->projection_count >= 0 && spec->projection_count <= 64, "bad projection count");
-    proj_roots_.assign(spec->projection_roots, spec->projection_roots + spec->projection_count);
-    for (int32_t t : input_types_) TG_CHECK_ARG(valid_type(t), "unknown input type");
+    nodes.assign(spec->nodes, spec->nodes + spec->node_count);
+    if (spec->string_pool && spec->string_pool_len > 0) pool.assign(spec->string_pool, spec->string_pool + spec->string_pool_len);
+    filter_root = spec->filter_root;
+    TG_CHECK_ARG(spec->projection_count >= 0, "bad projection count");
+    proj_roots.assign(spec->projection_roots, spec->projection_roots + spec->projection_count);
+}
+
+void ExprProgram::resolve_projection_types()
+{
+    proj_types.clear();
+    for (int32_t r : proj_roots) {
+        TG_CHECK_ARG(r >= 0 && r < (int)nodes.size(), "projection root out of range");
+        proj_types.push_back(nodes[(size_t)r].type);
+    }
+}
+
+bool ExprProgram::can_raise(int root) const
+{
+    const tgpu_expr_node &nd = nodes[(size_t)root];
+    if (nd.kind == TGPU_EX_CALL) {
+        const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
+        if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;   // checked integer arithmetic
+        if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
+        if (nd.op == TGPU_OP_LAST_DAY_OF_MONTH || nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD) return true;   // a DATE result outside int32 days
+        if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
+            const int32_t from = nodes[(size_t)nd.args[0]].type;
+            if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;
+        }
+    }
+    if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
+        for (int k = 0; k < nd.n_args; k++)
+            if (can_raise(nd.args[k])) return true;
+    return false;
+}
+
+void ExprProgram::inputs_of(int root, std::set<int> &out) const
+{
+    if (root < 0 || root >= (int)nodes.size()) return;
+    const tgpu_expr_node &nd = nodes[(size_t)root];
+    if (nd.kind == TGPU_EX_INPUT) out.insert(nd.op);
+    if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
+        for (int k = 0; k < nd.n_args && k < 3; k++) inputs_of(nd.args[k], out);
+}
+
+int ExprProgram::identity_channel(int projection) const
+{
+    const tgpu_expr_node &nd = nodes[(size_t)proj_roots[(size_t)projection]];
+    return nd.kind == TGPU_EX_INPUT ? nd.op : -1;
+}
+
+bool ExprProgram::never_null_given_inputs(int root) const
+{
+    const tgpu_expr_node &nd = nodes[(size_t)root];
+    if (nd.kind == TGPU_EX_INPUT) return true;
+    if (nd.kind == TGPU_EX_CONST) return !nd.is_null;
+    if (nd.kind == TGPU_EX_SPECIAL) return false;
+    for (int k = 0; k < nd.n_args; k++)
+        if (!never_null_given_inputs(nd.args[k])) return false;
+    return true;
+}
+
+PageProcessorGpu::PageProcessorGpu(std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec) : prog_(std::move(input_types), spec)
+{
+    TG_CHECK_ARG(prog_.proj_roots.size() <= 64, "bad projection count");
+    for (int32_t t : prog_.input_types) TG_CHECK_ARG(valid_type(t), "unknown input type");
     generate();
     // which input channels do the computed expressions read?
     std::set<int> read;
-    std::function<void(int)> walk = [&](int idx) {
-        if (idx < 0 || idx >= (int)nodes_.size()) return;
-        const tgpu_expr_node &nd = nodes_[(size_t)idx];
-        if (nd.kind == TGPU_EX_INPUT) read.insert(nd.op);
-        if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
-            for (int k = 0; k < nd.n_args && k < 3; k++) walk(nd.args[k]);
-    };
-    if (filter_root_ >= 0) walk(filter_root_);
+    if (prog_.filter_root >= 0) prog_.inputs_of(prog_.filter_root, read);
     filter_channels_.assign(read.begin(), read.end());
     for (size_t i = 0; i < projs_.size(); i++)
-        if (projs_[i].kind == ProjKind::COMPUTED) walk(proj_roots_[i]);
+        if (projs_[i].kind == ProjKind::COMPUTED) prog_.inputs_of(prog_.proj_roots[i], read);
     single_input_ = read.size() == 1 ? *read.begin() : -1;
-    std::set<int> pread;
-    std::swap(read, pread);
-    for (size_t i = 0; i < projs_.size(); i++) walk(proj_roots_[i]);
+    read.clear();
+    for (int32_t root : prog_.proj_roots) prog_.inputs_of(root, read);
     projection_channels_.assign(read.begin(), read.end());
 }
 
@@ -1539,8 +1628,8 @@ std::shared_ptr<PageProcessorGpu> PageProcessorGpu::filter_only()
 {
     std::lock_guard<std::mutex> lk(mu_);
     if (!filter_only_) {
-        tgpu_page_processor_spec spec{nodes_.data(), (int32_t)nodes_.size(), pool_.data(), (int32_t)pool_.size(), filter_root_, 0, nullptr};
-        filter_only_ = PageProcessorGpu::shared(input_types_, &spec);
+        tgpu_page_processor_spec spec{prog_.nodes.data(), (int32_t)prog_.nodes.size(), prog_.pool.data(), (int32_t)prog_.pool.size(), prog_.filter_root, 0, nullptr};
+        filter_only_ = PageProcessorGpu::shared(prog_.input_types, &spec);
     }
     return filter_only_;
 }
@@ -1554,17 +1643,17 @@ void PageProcessorGpu::process_dictionary(Context *ctx, const DeviceColumn &dict
         std::lock_guard<std::mutex> lk(mu_);
         if (!dict_processor_) {
             // the same node array with every input reference pointing at channel 0; no filter; projections = [filter, computed...]
-            std::vector<tgpu_expr_node> nodes = nodes_;
+            std::vector<tgpu_expr_node> nodes = prog_.nodes;
             for (auto &nd : nodes)
                 if (nd.kind == TGPU_EX_INPUT) nd.op = 0;
             std::vector<int32_t> roots;
-            if (filter_root_ >= 0) roots.push_back(filter_root_);
+            if (prog_.filter_root >= 0) roots.push_back(prog_.filter_root);
             std::vector<int32_t> by_slot((size_t)computed_count_, -1);
             for (size_t i = 0; i < projs_.size(); i++)
-                if (projs_[i].kind == ProjKind::COMPUTED) by_slot[(size_t)projs_[i].slot] = proj_roots_[i];
+                if (projs_[i].kind == ProjKind::COMPUTED) by_slot[(size_t)projs_[i].slot] = prog_.proj_roots[i];
             for (int32_t r : by_slot) roots.push_back(r);
-            tgpu_page_processor_spec spec{nodes.data(), (int32_t)nodes.size(), pool_.data(), (int32_t)pool_.size(), -1, (int32_t)roots.size(), roots.data()};
-            dict_processor_ = PageProcessorGpu::shared({input_types_[(size_t)single_input_]}, &spec);
+            tgpu_page_processor_spec spec{nodes.data(), (int32_t)nodes.size(), prog_.pool.data(), (int32_t)prog_.pool.size(), -1, (int32_t)roots.size(), roots.data()};
+            dict_processor_ = PageProcessorGpu::shared({prog_.input_types[(size_t)single_input_]}, &spec);
         }
     }
     DevicePage in;
@@ -1575,14 +1664,14 @@ void PageProcessorGpu::process_dictionary(Context *ctx, const DeviceColumn &dict
 
 void PageProcessorGpu::generate()
 {
-    Gen g(nodes_, pool_, input_types_);
+    Gen g(prog_);
     // classify projections: identity (InputPageProjection) needs no codegen (PageFunctionCompiler.java:176-186)
-    for (int32_t root : proj_roots_) {
+    for (int32_t root : prog_.proj_roots) {
         const tgpu_expr_node &nd = g.node(root);
         Proj p;
         p.type = nd.type;
         if (nd.kind == TGPU_EX_INPUT) {
-            if (nd.op < 0 || nd.op >= (int)input_types_.size() || input_types_[nd.op] != nd.type) g.bad("identity projection channel/type mismatch");
+            if (nd.op < 0 || nd.op >= (int)prog_.input_types.size() || prog_.input_types[nd.op] != nd.type) g.bad("identity projection channel/type mismatch");
             p.kind = ProjKind::IDENTITY;
             p.channel = nd.op;
         }
@@ -1600,8 +1689,8 @@ void PageProcessorGpu::generate()
     }
 
     std::ostringstream filter_body, proj_body;
-    if (filter_root_ >= 0) {
-        Val f = g.gen_root(filter_root_, 2, 0);
+    if (prog_.filter_root >= 0) {
+        Val f = g.gen_root(prog_.filter_root, 2, 0);
         if (f.type != TGPU_BOOLEAN) g.bad("filter must be boolean");
         g.os << "    return !" << f.n << " && " << f.v << ";\n";
         filter_body << g.os.str();
@@ -1610,7 +1699,7 @@ void PageProcessorGpu::generate()
     for (size_t i = 0; i < projs_.size(); i++) {
         if (projs_[i].kind != ProjKind::COMPUTED) continue;
         g.os << "    {\n";
-        Val v = g.gen_root(proj_roots_[i], 3, 1 + (int)i);
+        Val v = g.gen_root(prog_.proj_roots[i], 3, 1 + (int)i);
         const int slot = projs_[i].slot;
         const char *T = projs_[i].type == TGPU_BOOLEAN ? "unsigned char" : ctype(projs_[i].type);
         // a VARCHAR slot gets the row's byte length only (0 for NULL: the reference's builder appends no byte for one); fp_vwrite copies the bytes
@@ -1627,7 +1716,7 @@ void PageProcessorGpu::generate()
         if (projs_[i].vslot < 0) continue;
         g.need_string_helpers();
         g.os << "  {\n";
-        Val v = g.gen_root(proj_roots_[i], 2, 1 + (int)i);
+        Val v = g.gen_root(prog_.proj_roots[i], 2, 1 + (int)i);
         g.os << "    unsigned char* d_ = V.pool[" << projs_[i].vslot << "] + V.offsets[" << projs_[i].vslot << "][o];\n";
         g.os << "    const bool w_ = act && !" << v.n << ";\n";
         for (const Val::Piece &p : Gen::pieces_of(v)) g.os << "    tg_vw_piece(d_, " << p.p << ", " << p.iv << ", " << p.len << ", w_); d_ += " << p.len << ";\n";
@@ -1637,7 +1726,7 @@ void PageProcessorGpu::generate()
 
     std::ostringstream cols;
     for (int ch : g.used_cols) {
-        const int32_t t = input_types_[ch];
+        const int32_t t = prog_.input_types[ch];
         const char *T = t == TGPU_VARCHAR ? "unsigned char" : (t == TGPU_BOOLEAN ? "unsigned char" : ctype(t));
         cols << "  const " << T << "* c" << ch << " = (const " << T << "*)A.col_values[" << ch << "];\n";
         cols << "  const unsigned char* cn" << ch << " = A.col_nulls[" << ch << "];\n";
@@ -1647,7 +1736,7 @@ void PageProcessorGpu::generate()
 
     std::ostringstream src;
     src << kPrelude << g.consts.str();
-    const bool has_filter = filter_root_ >= 0;
+    const bool has_filter = prog_.filter_root >= 0;
     if (has_filter) {
         src << "__device__ inline bool tg_filter(const FpArgs& A, long long row) {\n" << cols.str() << filter_body.str() << "}\n";
         // pass 1: selected rows per tile
@@ -1822,9 +1911,20 @@ void PageProcessorGpu::ensure_loaded(Context *ctx)
     std::lock_guard<std::mutex> lk(mu_);
     if (module_) return;
     module_ = load_module(source_);
-    if (filter_root_ >= 0) fn_count_ = module_->fn("fp_count");
+    if (prog_.filter_root >= 0) fn_count_ = module_->fn("fp_count");
     fn_emit_ = module_->fn("fp_emit");
     if (varchar_count_ > 0) fn_vwrite_ = module_->fn("fp_vwrite");
+}
+
+// a page's column pointers and row count, as every generated kernel takes them
+static void fill_fp_cols(FpArgs &fp, const DevicePage &in)
+{
+    for (size_t i = 0; i < in.cols.size() && i < (size_t)kFpMaxCols; i++) {
+        fp.col_values[i] = in.cols[i].values;
+        fp.col_nulls[i] = in.cols[i].nulls;
+        fp.col_offsets[i] = in.cols[i].offsets;
+    }
+    fp.n = in.n;
 }
 
 static void launch(hipFunction_t f, int grid, FpArgs &args, hipStream_t stream)
@@ -1836,8 +1936,8 @@ static void launch(hipFunction_t f, int grid, FpArgs &args, hipStream_t stream)
 
 bool PageProcessorGpu::process(Context *ctx, const DevicePage &in, DevicePage &out)
 {
-    TG_CHECK_ARG(in.cols.size() == input_types_.size(), "page channel count differs from the operator's input types");
-    for (size_t i = 0; i < in.cols.size(); i++) TG_CHECK_ARG(in.cols[i].type == input_types_[i], "page channel type differs from the operator's input types");
+    TG_CHECK_ARG(in.cols.size() == prog_.input_types.size(), "page channel count differs from the operator's input types");
+    for (size_t i = 0; i < in.cols.size(); i++) TG_CHECK_ARG(in.cols[i].type == prog_.input_types[i], "page channel type differs from the operator's input types");
     out.cols.clear();
     out.n = 0;
     const int64_t n = in.n;
@@ -1845,12 +1945,7 @@ bool PageProcessorGpu::process(Context *ctx, const DevicePage &in, DevicePage &o
     ensure_loaded(ctx);
 
     FpArgs args{};
-    for (size_t i = 0; i < in.cols.size() && i < (size_t)kFpMaxCols; i++) {
-        args.col_values[i] = in.cols[i].values;
-        args.col_nulls[i] = in.cols[i].nulls;
-        args.col_offsets[i] = in.cols[i].offsets;
-    }
-    args.n = n;
+    fill_fp_cols(args, in);
     const int64_t tiles = ceil_div(n, 1024);
     TG_CHECK_ARG(tiles <= 0x7fffffffLL, "page too large");
     BufferPtr err = ctx->alloc(8);
@@ -1862,7 +1957,7 @@ bool PageProcessorGpu::process(Context *ctx, const DevicePage &in, DevicePage &o
 
     int64_t n_sel = n;
     BufferPtr positions, tile_counts, tile_offsets, sel_mask;
-    const bool has_filter = filter_root_ >= 0;
+    const bool has_filter = prog_.filter_root >= 0;
     if (has_filter) {
         sel_mask = ctx->alloc((size_t)tiles * 4 * 4 * 8);   // TG_STRIPES (4) x 4 waves ballots per tile
         args.sel_mask = sel_mask->as<unsigned long long>();
@@ -2614,45 +2709,19 @@ extern "C" __global__ void __launch_bounds__(256) fj_pair(FjPairArgs P) {
 }  // namespace
 
 FusedProbeGpu::FusedProbeGpu(std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec, int32_t join_channel, std::vector<int32_t> output_channels)
-    : input_types_(std::move(input_types)), output_channels_(std::move(output_channels)), join_channel_(join_channel)
+    : prog_(std::move(input_types), spec), output_channels_(std::move(output_channels)), join_channel_(join_channel)
 {
-    TG_CHECK_ARG(spec != nullptr, "page processor spec is null");
-    nodes_.assign(spec->nodes, spec->nodes + spec->node_count);
-    if (spec->string_pool && spec->string_pool_len > 0) pool_.assign(spec->string_pool, spec->string_pool + spec->string_pool_len);
-    filter_root_ = spec->filter_root;
-    proj_roots_.assign(spec->projection_roots, spec->projection_roots + spec->projection_count);
-    TG_CHECK_ARG(join_channel_ >= 0 && join_channel_ < (int)proj_roots_.size(), "join channel out of range");
-    for (int32_t ch : output_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)proj_roots_.size(), "probe output channel out of range");
-    for (int32_t r : proj_roots_) {
-        TG_CHECK_ARG(r >= 0 && r < (int)nodes_.size(), "projection root out of range");
-        proj_types_.push_back(nodes_[(size_t)r].type);
-    }
-    const int32_t kt = proj_types_[(size_t)join_channel_];
+    TG_CHECK_ARG(join_channel_ >= 0 && join_channel_ < (int)prog_.proj_roots.size(), "join channel out of range");
+    for (int32_t ch : output_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)prog_.proj_roots.size(), "probe output channel out of range");
+    prog_.resolve_projection_types();
+    const int32_t kt = prog_.proj_types[(size_t)join_channel_];
     supported_ = (kt == TGPU_BIGINT || kt == TGPU_INTEGER || kt == TGPU_DATE) && (int)output_channels_.size() <= kFpMaxProj;
-    for (int32_t ch : output_channels_) supported_ = supported_ && proj_types_[(size_t)ch] != TGPU_VARCHAR;
-    // The fused kernel evaluates the non-key projections lazily (for matching rows only) or not at all (channels the join
-    // drops), whereas FilterAndProjectOperator evaluates every projection on every selected row.  That is only equivalent
-    // when those projections cannot raise: anything with checked integer arithmetic keeps the unfused composition.
-    std::function<bool(int)> can_raise = [&](int idx) -> bool {
-        const tgpu_expr_node &nd = nodes_[(size_t)idx];
-        if (nd.kind == TGPU_EX_CALL) {
-            const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
-            if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;
-            if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
-            if (nd.op == TGPU_OP_LAST_DAY_OF_MONTH || nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD) return true;   // a DATE result outside int32 days
-            if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
-                const int32_t from = nodes_[(size_t)nd.args[0]].type;
-                if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;
-            }
-        }
-        if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
-            for (int k = 0; k < nd.n_args; k++)
-                if (can_raise(nd.args[k])) return true;
-        return false;
-    };
-    for (size_t ch = 0; ch < proj_roots_.size(); ch++)
-        if ((int)ch != join_channel_ && can_raise(proj_roots_[ch])) supported_ = false;
-    key_can_raise_ = can_raise(proj_roots_[(size_t)join_channel_]);
+    for (int32_t ch : output_channels_) supported_ = supported_ && prog_.proj_types[(size_t)ch] != TGPU_VARCHAR;
+    // the fused kernel evaluates the non-key projections lazily (for matching rows only) or not at all (channels the join drops):
+    // one that can raise keeps the unfused composition (ExprProgram::can_raise)
+    for (size_t ch = 0; ch < prog_.proj_roots.size(); ch++)
+        if ((int)ch != join_channel_ && prog_.can_raise(prog_.proj_roots[ch])) supported_ = false;
+    key_can_raise_ = prog_.can_raise(prog_.proj_roots[(size_t)join_channel_]);
     if (supported_) generate();
 }
 
@@ -2689,30 +2758,19 @@ void fused_probe_depth_counts(int64_t out[2])
 
 void FusedProbeGpu::generate()
 {
-    auto cols_decl = [&](const Gen &g) {
-        std::ostringstream cols;
-        for (int ch : g.used_cols) {
-            const int32_t t = input_types_[(size_t)ch];
-            const char *T = (t == TGPU_VARCHAR || t == TGPU_BOOLEAN) ? "unsigned char" : ctype(t);
-            cols << "  const " << T << "* c" << ch << " = (const " << T << "*)A.col_values[" << ch << "]; (void)c" << ch << ";\n";
-            cols << "  const unsigned char* cn" << ch << " = FJ_NO_NULLS ? (const unsigned char*)0 : A.col_nulls[" << ch << "]; (void)cn" << ch << ";\n";
-            if (t == TGPU_VARCHAR) cols << "  const int* co" << ch << " = A.col_offsets[" << ch << "]; (void)co" << ch << ";\n";
-        }
-        return cols.str();
-    };
     auto splice = [](std::string t, const std::string &cols) {
         size_t p = t.find("@COLS@");
         if (p != std::string::npos) t.replace(p, 6, cols);
         return t;
     };
-    const int32_t kt = proj_types_[(size_t)join_channel_];
+    const int32_t kt = prog_.proj_types[(size_t)join_channel_];
 
     // (a) filter + join key in register-row mode: evaluated for every row of pass 1 from pre-loaded column values
-    Gen gr(nodes_, pool_, input_types_);
+    Gen gr(prog_);
     gr.reg_mode = true;
     std::vector<std::string> reg_bodies;
-    if (filter_root_ >= 0) {
-        Val f = gr.gen_root(filter_root_, 1, 0);
+    if (prog_.filter_root >= 0) {
+        Val f = gr.gen_root(prog_.filter_root, 1, 0);
         if (f.type != TGPU_BOOLEAN) gr.bad("filter must be boolean");
         std::ostringstream fb;
         fb << "__device__ inline bool tg_filter(const FpArgs& A, long long row, const TgRow& R) {\n@COLS@" << gr.os.str() << "  return !" << f.n << " && " << f.v << ";\n}\n";
@@ -2721,22 +2779,22 @@ void FusedProbeGpu::generate()
     else reg_bodies.push_back("__device__ inline bool tg_filter(const FpArgs& A, long long row, const TgRow& R) { return true; }\n");
     {
         gr.os.str("");
-        Val v = gr.gen_root(proj_roots_[(size_t)join_channel_], 1, 1 + join_channel_);
+        Val v = gr.gen_root(prog_.proj_roots[(size_t)join_channel_], 1, 1 + join_channel_);
         std::ostringstream f;
         f << "__device__ inline bool tg_key(const FpArgs& A, long long row, const TgRow& R, long long& key) {\n@COLS@" << gr.os.str() << "  key = (long long)" << v.v
           << ";\n  return " << v.n << ";\n}\n";
         reg_bodies.push_back(f.str());
     }
     // (b) output projections in memory mode: evaluated lazily in pass 2 for the matching rows only
-    Gen gm(nodes_, pool_, input_types_);
+    Gen gm(prog_);
     gm.tmp = gr.tmp;
     std::vector<std::string> mem_bodies;
     std::set<int> outs(output_channels_.begin(), output_channels_.end());
     for (int ch : outs) {
         gm.os.str("");
-        Val v = gm.gen_root(proj_roots_[(size_t)ch], 1, 1 + ch);
+        Val v = gm.gen_root(prog_.proj_roots[(size_t)ch], 1, 1 + ch);
         std::ostringstream f;
-        f << "__device__ inline bool tg_p" << ch << "(const FpArgs& A, long long row, " << ctype(proj_types_[(size_t)ch]) << "& out) {\n@COLS@" << gm.os.str()
+        f << "__device__ inline bool tg_p" << ch << "(const FpArgs& A, long long row, " << ctype(prog_.proj_types[(size_t)ch]) << "& out) {\n@COLS@" << gm.os.str()
           << "  out = " << v.v << ";\n  return " << v.n << ";\n}\n";
         mem_bodies.push_back(f.str());
     }
@@ -2747,7 +2805,7 @@ void FusedProbeGpu::generate()
     // touches most 128-byte lines of those columns anyway, and a probe launch that is bound by its table lookups (the orders launch
     // of Q3: L2 requests) has the HBM bandwidth to stream them.  Eligible: up to 4 fixed-width outputs of at most 24 bytes together that
     // read fixed-width columns only.
-    Gen gc(nodes_, pool_, input_types_);
+    Gen gc(prog_);
     gc.reg_mode = true;
     gc.tmp = gm.tmp + 1000;
     std::vector<std::string> carry_bodies;
@@ -2755,12 +2813,12 @@ void FusedProbeGpu::generate()
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int ch = output_channels_[i];
         gc.os.str("");
-        Val v = gc.gen_root(proj_roots_[(size_t)ch], 1, 1 + ch);
+        Val v = gc.gen_root(prog_.proj_roots[(size_t)ch], 1, 1 + ch);
         std::ostringstream f;
-        f << "__device__ inline bool tg_c" << i << "(const FpArgs& A, long long row, const TgRow& R, " << ctype(proj_types_[(size_t)ch]) << "& out) {\n@COLS@" << gc.os.str()
+        f << "__device__ inline bool tg_c" << i << "(const FpArgs& A, long long row, const TgRow& R, " << ctype(prog_.proj_types[(size_t)ch]) << "& out) {\n@COLS@" << gc.os.str()
           << "  out = " << v.v << ";\n  return " << v.n << ";\n}\n";
         carry_bodies.push_back(f.str());
-        carry_bytes += type_width(proj_types_[(size_t)ch]);
+        carry_bytes += type_width(prog_.proj_types[(size_t)ch]);
     }
     carry_supported_ = !output_channels_.empty() && output_channels_.size() <= 4 && carry_bytes <= 24 && gc.used_cols.empty();   // (used_cols: columns read from memory = VARCHAR inputs)
     std::vector<int> carry_only_cols;   // columns only the carried outputs read
@@ -2778,9 +2836,9 @@ void FusedProbeGpu::generate()
         for (size_t i = 0; i < output_channels_.size() && i < 4; i++) {
             const int ch = output_channels_[i];
             if (ch == join_channel_ && (key_can_raise_ || free_rule == 1)) continue;
-            Gen ga(nodes_, pool_, input_types_);
+            Gen ga(prog_);
             ga.reg_mode = true;
-            ga.gen_root(proj_roots_[(size_t)ch], 1, 1 + ch);
+            ga.gen_root(prog_.proj_roots[(size_t)ch], 1, 1 + ch);
             bool held = ga.used_cols.empty() && ga.consts.str().empty();
             for (int col : ga.reg_cols) held = held && gr.reg_cols.count(col) != 0;
             free_out_[i] = held;
@@ -2794,50 +2852,25 @@ void FusedProbeGpu::generate()
     src << "#ifndef FJ_CARRY\n#define FJ_CARRY 0\n#endif\n";
     src << kPrelude << device_header("device_hash.h") << device_header("device_join.h") << gr.consts.str() << gm.consts.str() << gc.consts.str();
     // the pre-loaded row: one field pair per fixed-width column the filter / key (and, in the carry variant, the outputs) read
-    auto field = [&](int ch) {
-        const int32_t t = input_types_[(size_t)ch];
-        return std::string("  ") + (t == TGPU_BOOLEAN ? "unsigned char" : ctype(t)) + " c" + std::to_string(ch) + "; unsigned char n" + std::to_string(ch) + ";\n";
-    };
-    auto load = [&](int ch) {
-        const int32_t t = input_types_[(size_t)ch];
-        const std::string T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t), C = std::to_string(ch);
-        return "  R.c" + C + " = ((const " + T + "*)A.col_values[" + C + "])[row]; R.n" + C + " = (!FJ_NO_NULLS && A.col_nulls[" + C + "]) ? A.col_nulls[" + C + "][row] : 0;\n";
-    };
-    src << "struct TgRow {\n";
-    for (int ch : gr.reg_cols) src << field(ch);
-    src << "#if FJ_CARRY\n";
-    for (int ch : carry_only_cols) src << field(ch);
-    src << "#endif\n";
-    if (gr.reg_cols.empty()) src << "  int unused;\n";
-    src << "};\n__device__ inline void tg_load_row(const FpArgs& A, long long row, TgRow& R) {\n";
-    for (int ch : gr.reg_cols) src << load(ch);
-    src << "#if FJ_CARRY\n";
-    for (int ch : carry_only_cols) src << load(ch);
-    src << "#endif\n";
-    src << "  (void)A; (void)row; (void)R;\n}\n__device__ inline void tg_zero_row(TgRow& R) {\n";
-    for (int ch : gr.reg_cols) src << "  R.c" << ch << " = 0; R.n" << ch << " = 0;\n";
-    src << "#if FJ_CARRY\n";
-    for (int ch : carry_only_cols) src << "  R.c" << ch << " = 0; R.n" << ch << " = 0;\n";
-    src << "#endif\n";
-    src << "  (void)R;\n}\n";
+    src << row_decl(prog_.input_types, "TgRow", "row", gr.reg_cols, false, "FJ_NO_NULLS", &carry_only_cols);
     // load instructions tg_load_row issues per row (FJ_DEPTH 2 sizes its wait with it): a value per column, a null byte where the page may have
     // null vectors; the partial carry reads none of the carry-only columns, so their loads fold away
     src << "#define FJ_ROW_LOADS ((" << gr.reg_cols.size() << " + (FJ_CARRY == 1 ? " << carry_only_cols.size() << " : 0)) * (FJ_NO_NULLS ? 1 : 2))\n";
-    const std::string rc = cols_decl(gr), mc = cols_decl(gm);
+    const std::string rc = fused_cols_decl(gr, "FJ_NO_NULLS"), mc = fused_cols_decl(gm, "FJ_NO_NULLS");
     for (auto &b : reg_bodies) src << splice(b, rc);
     for (auto &b : mem_bodies) src << splice(b, mc);
     // the carried outputs of one row (register form), their evaluation, and the two stores
     src << "struct FjArgs;\nstruct TgOut {\n";
-    for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  " << ctype(proj_types_[(size_t)output_channels_[i]]) << " v" << i << ";\n#endif\n";
+    for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  " << ctype(prog_.proj_types[(size_t)output_channels_[i]]) << " v" << i << ";\n#endif\n";
     src << "#if !FJ_NO_NULLS\n  unsigned char nulls;\n#endif\n};\n__device__ inline void tg_zero_out(TgOut& O) {\n";
     for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  O.v" << i << " = 0;\n#endif\n";
     src << "#if !FJ_NO_NULLS\n  O.nulls = 0;\n#endif\n  (void)O;\n}\n#if FJ_CARRY\n";
     {
-        const std::string cc = cols_decl(gc);
+        const std::string cc = fused_cols_decl(gc, "FJ_NO_NULLS");
         for (size_t i = 0; i < carry_bodies.size(); i++) src << all_or_free(i) << splice(carry_bodies[i], cc) << "#endif\n";
         src << "__device__ inline void tg_carry_eval(const FpArgs& A, long long row, const TgRow& R, TgOut& O) {\n  unsigned char nl = 0;\n";
         for (size_t i = 0; i < output_channels_.size(); i++) {
-            const int32_t t = proj_types_[(size_t)output_channels_[i]];
+            const int32_t t = prog_.proj_types[(size_t)output_channels_[i]];
             src << all_or_free(i) << "  { " << ctype(t) << " v = 0; const bool n = tg_c" << i << "(A, row, R, v); O.v" << i << " = n ? (" << ctype(t) << ")0 : v; nl |= n ? " << (1 << i)
                 << " : 0; }\n#endif\n";
         }
@@ -2847,7 +2880,7 @@ void FusedProbeGpu::generate()
     std::ostringstream carry_funcs;   // need FjArgs: spliced in behind its definition (@CARRY_FUNCS@ in kFjKernels)
     carry_funcs << "#if FJ_CARRY\n__device__ inline void tg_carry_store(const FjArgs& J, long long at, const TgOut& O) {\n";
     for (size_t i = 0; i < output_channels_.size(); i++) {
-        const int32_t t = proj_types_[(size_t)output_channels_[i]];
+        const int32_t t = prog_.proj_types[(size_t)output_channels_[i]];
         const std::string T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
         carry_funcs << all_or_free(i) << "  ((" << T << "*)J.carry[" << i << "])[at] = (" << T << ")O.v" << i << ";\n#endif\n";
     }
@@ -2855,7 +2888,7 @@ void FusedProbeGpu::generate()
                 << "__device__ inline void tg_carry_move(const FjArgs& J, long long from, long long to) {\n  const FpArgs& A = J.fp;\n"
                 << "  const unsigned int nl = J.carry_nulls ? J.carry_nulls[from] : 0u; (void)nl;\n";
     for (size_t i = 0; i < output_channels_.size(); i++) {
-        const int32_t t = proj_types_[(size_t)output_channels_[i]];
+        const int32_t t = prog_.proj_types[(size_t)output_channels_[i]];
         const std::string T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
         carry_funcs << all_or_free(i) << "  ((" << T << "*)A.out_values[" << i << "])[to] = ((const " << T << "*)J.carry[" << i << "])[from]; if (A.out_nulls[" << i
                     << "]) A.out_nulls[" << i << "][to] = (unsigned char)((nl >> " << i << ") & 1u);\n#endif\n";
@@ -2865,7 +2898,7 @@ void FusedProbeGpu::generate()
     src << "__device__ inline void tg_emit_outputs(const FpArgs& A, long long row, long long o) {\n  (void)A; (void)row; (void)o;\n";
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int ch = output_channels_[i];
-        const int32_t t = proj_types_[(size_t)ch];
+        const int32_t t = prog_.proj_types[(size_t)ch];
         const char *T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
         src << not_carried(i) << "  { " << ctype(t) << " v = 0; const bool n = tg_p" << ch << "(A, row, v); ((" << T << "*)A.out_values[" << i << "])[o] = n ? (" << T << ")0 : (" << T
             << ")v; if (A.out_nulls[" << i << "]) A.out_nulls[" << i << "][o] = n ? 1 : 0; }\n#endif\n";   // (no null vector: the host proved the channel null-free)
@@ -2979,7 +3012,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     TG_CHECK_ARG(!pages.empty(), "no page");
     const DevicePage &in = *pages[0];
     const bool multi = pages.size() > 1;
-    for (const DevicePage *pg : pages) TG_CHECK_ARG(pg->cols.size() == input_types_.size(), "page channel count differs from the operator's input types");
+    for (const DevicePage *pg : pages) TG_CHECK_ARG(pg->cols.size() == prog_.input_types.size(), "page channel count differs from the operator's input types");
     if (need_build_positions) source.ensure_rank();
     IntTableView tv;
     TG_CHECK_STATE(source.int_table(tv) && tv.links == nullptr, "fused probe needs the int-key table without duplicate build keys");
@@ -3050,12 +3083,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     pend->need_build_positions = need_build_positions;
     pend->carry = carry;
     FjArgs &J = pend->J;
-    for (size_t i = 0; i < in.cols.size() && i < (size_t)kFpMaxCols; i++) {
-        J.fp.col_values[i] = in.cols[i].values;
-        J.fp.col_nulls[i] = in.cols[i].nulls;
-        J.fp.col_offsets[i] = in.cols[i].offsets;
-    }
-    J.fp.n = multi ? in.n : n;
+    fill_fp_cols(J.fp, in);   // (several pages: the first one's; the kernel reads the descriptors below)
     J.slots = tv.slots;
     J.mask = tv.mask;
     J.bitmap = tv.bitmap;
@@ -3115,12 +3143,7 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
         std::vector<uint8_t> host(desc_bytes + tile_bytes);
         for (size_t i = 0; i < pages.size(); i++) {
             FpArgs d{};
-            for (size_t c = 0; c < pages[i]->cols.size() && c < (size_t)kFpMaxCols; c++) {
-                d.col_values[c] = pages[i]->cols[c].values;
-                d.col_nulls[c] = pages[i]->cols[c].nulls;
-                d.col_offsets[c] = pages[i]->cols[c].offsets;
-            }
-            d.n = pages[i]->n;
+            fill_fp_cols(d, *pages[i]);
             d.error = J.fp.error;
             memcpy(host.data() + i * sizeof(FpArgs), &d, sizeof(FpArgs));
         }
@@ -3144,9 +3167,9 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
         bool nullable = false;
         for (size_t i = 0; i < output_channels_.size(); i++) {
             if (carry == 2 && !free_out_[i]) continue;   // (partial: pass 2 gathers this channel)
-            carry_regions.push_back(ctx->alloc((size_t)cap * type_width(proj_types_[(size_t)output_channels_[i]])));
+            carry_regions.push_back(ctx->alloc((size_t)cap * type_width(prog_.proj_types[(size_t)output_channels_[i]])));
             J.carry[i] = carry_regions.back()->ptr();
-            const tgpu_expr_node &root = nodes_[(size_t)proj_roots_[(size_t)output_channels_[i]]];
+            const tgpu_expr_node &root = prog_.nodes[(size_t)prog_.proj_roots[(size_t)output_channels_[i]]];
             nullable = nullable || !(root.kind == TGPU_EX_INPUT && root.op >= 0 && root.op < (int)in.cols.size() && in.cols[(size_t)root.op].nulls == nullptr);
         }
         if (nullable) {
@@ -3265,14 +3288,14 @@ void FusedProbeGpu::finish(Context *ctx, const std::shared_ptr<Pending> &pend, c
     J.out_build = build_idx->as<int32_t>();
     for (size_t i = 0; i < output_channels_.size(); i++) {
         DeviceColumn c;
-        c.type = proj_types_[(size_t)output_channels_[i]];
+        c.type = prog_.proj_types[(size_t)output_channels_[i]];
         c.n = count;
         c.values_buf = ctx->alloc((size_t)count * type_width(c.type));
         c.values = c.values_buf->ptr();
         // an output that is a plain reference to an input column without a null vector cannot hold a null: no null vector is
         // produced for it (what Block.mayHaveNull() == false gives the reference's downstream operators), so the build / group-by
         // kernels behind the join skip their null checks for the channel
-        const tgpu_expr_node &root = nodes_[(size_t)proj_roots_[(size_t)output_channels_[i]]];
+        const tgpu_expr_node &root = prog_.nodes[(size_t)prog_.proj_roots[(size_t)output_channels_[i]]];
         const bool null_free = root.kind == TGPU_EX_INPUT && root.op >= 0 && root.op < (int)pend->col_nulls.size() && !pend->col_nulls[(size_t)root.op];
         if (!null_free) {
             c.nulls_buf = ctx->alloc((size_t)count);
@@ -3689,52 +3712,27 @@ struct FqArgsHost {
 
 FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec, std::vector<tgpu_agg_spec> aggs,
                          std::vector<int32_t> group_by_channels)
-    : input_types_(std::move(input_types)), aggs_(std::move(aggs))
+    : prog_(std::move(input_types), spec), aggs_(std::move(aggs))
 {
-    TG_CHECK_ARG(spec != nullptr, "page processor spec is null");
-    nodes_.assign(spec->nodes, spec->nodes + spec->node_count);
-    if (spec->string_pool && spec->string_pool_len > 0) pool_.assign(spec->string_pool, spec->string_pool + spec->string_pool_len);
-    filter_root_ = spec->filter_root;
-    proj_roots_.assign(spec->projection_roots, spec->projection_roots + spec->projection_count);
-    for (int32_t r : proj_roots_) {
-        TG_CHECK_ARG(r >= 0 && r < (int)nodes_.size(), "projection root out of range");
-        proj_types_.push_back(nodes_[(size_t)r].type);
-    }
+    prog_.resolve_projection_types();
     TG_CHECK_ARG((int)aggs_.size() <= 16, "at most 16 aggregates");
     supported_ = true;
-    const int np = (int)proj_roots_.size();
+    const int np = (int)prog_.proj_roots.size();
     for (auto &a : aggs_) {
         TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
         if (a.function != TGPU_AGG_COUNT_ALL) {
             TG_CHECK_ARG(a.input_channel >= 0 && a.input_channel < np, "aggregate input channel out of range");
-            const int32_t t = proj_types_[(size_t)a.input_channel];
+            const int32_t t = prog_.proj_types[(size_t)a.input_channel];
             const bool want_bigint = a.function == TGPU_AGG_SUM_BIGINT || a.function == TGPU_AGG_AVG_BIGINT || a.function == TGPU_AGG_MIN_BIGINT || a.function == TGPU_AGG_MAX_BIGINT;
             const bool want_double = a.function == TGPU_AGG_SUM_DOUBLE || a.function == TGPU_AGG_AVG_DOUBLE || a.function == TGPU_AGG_MIN_DOUBLE || a.function == TGPU_AGG_MAX_DOUBLE;
             TG_CHECK_ARG(!(want_bigint && t != TGPU_BIGINT) && !(want_double && t != TGPU_DOUBLE), "aggregate input type mismatch");
-            if (a.function == TGPU_AGG_COUNT_COLUMN && t == TGPU_VARCHAR) supported_ = supported_ && nodes_[(size_t)proj_roots_[(size_t)a.input_channel]].kind == TGPU_EX_INPUT;
+            if (a.function == TGPU_AGG_COUNT_COLUMN && t == TGPU_VARCHAR) supported_ = supported_ && prog_.nodes[(size_t)prog_.proj_roots[(size_t)a.input_channel]].kind == TGPU_EX_INPUT;
         }
-        if (a.mask_channel >= 0) TG_CHECK_ARG(a.mask_channel < np && proj_types_[(size_t)a.mask_channel] == TGPU_BOOLEAN, "aggregate mask must be a BOOLEAN channel");
+        if (a.mask_channel >= 0) TG_CHECK_ARG(a.mask_channel < np && prog_.proj_types[(size_t)a.mask_channel] == TGPU_BOOLEAN, "aggregate mask must be a BOOLEAN channel");
     }
     // Equivalence with FilterAndProject -> HashAggregation needs every projection that can raise to be evaluated on every
     // selected row; the fused kernel evaluates exactly the aggregates' inputs on exactly those rows, so any OTHER projection
     // that can raise (dropped by the aggregation) keeps the unfused composition.
-    std::function<bool(int)> can_raise = [&](int idx) -> bool {
-        const tgpu_expr_node &nd = nodes_[(size_t)idx];
-        if (nd.kind == TGPU_EX_CALL) {
-            const bool int_result = nd.type == TGPU_BIGINT || nd.type == TGPU_INTEGER;
-            if (int_result && nd.op >= TGPU_OP_ADD && nd.op <= TGPU_OP_NEGATE) return true;
-            if (nd.op == TGPU_OP_CONCAT) return true;   // "Concatenated string is too large"
-            if (nd.op == TGPU_OP_LAST_DAY_OF_MONTH || nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD) return true;   // a DATE result outside int32 days
-            if (nd.op == TGPU_OP_CAST && nd.n_args == 1 && int_result) {   // narrowing casts are checked (BIGINT -> INTEGER, DOUBLE -> BIGINT / INTEGER)
-                const int32_t from = nodes_[(size_t)nd.args[0]].type;
-                if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;
-            }
-        }
-        if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
-            for (int k = 0; k < nd.n_args; k++)
-                if (can_raise(nd.args[k])) return true;
-        return false;
-    };
     std::set<int> used;
     for (auto &a : aggs_) {
         if (a.function != TGPU_AGG_COUNT_ALL) used.insert(a.input_channel);
@@ -3743,9 +3741,9 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
     // nothing the accumulate kernels evaluate can raise (TPCH Q1: double arithmetic only): their error word is never written and
     // the per-page read-back of it is skipped
     accumulate_can_raise_ = false;
-    for (int ch : used) accumulate_can_raise_ = accumulate_can_raise_ || can_raise(proj_roots_[(size_t)ch]);
+    for (int ch : used) accumulate_can_raise_ = accumulate_can_raise_ || prog_.can_raise(prog_.proj_roots[(size_t)ch]);
     for (int ch = 0; ch < np; ch++)
-        if (can_raise(proj_roots_[(size_t)ch])) {
+        if (prog_.can_raise(prog_.proj_roots[(size_t)ch])) {
             // a masked aggregate would skip evaluating its input on masked-out rows; an unused channel is never evaluated
             bool always_evaluated = used.count(ch) > 0;
             for (auto &a : aggs_)
@@ -3757,28 +3755,12 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
     n_wide_ = 0;
     n_cnt_ = 0;
     std::map<std::tuple<int, int, int>, int> wide_of, cnt_of;
-    std::function<void(int, std::set<int> &)> inputs_of = [&](int idx, std::set<int> &out) {
-        const tgpu_expr_node &nd = nodes_[(size_t)idx];
-        if (nd.kind == TGPU_EX_INPUT) out.insert(nd.op);
-        if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
-            for (int k = 0; k < nd.n_args; k++) inputs_of(nd.args[k], out);
-    };
-    std::function<bool(int)> never_null_given_inputs = [&](int idx) -> bool {
-        // true when the expression is null only if one of its input columns is (no null literal, no IF / COALESCE subtleties)
-        const tgpu_expr_node &nd = nodes_[(size_t)idx];
-        if (nd.kind == TGPU_EX_INPUT) return true;
-        if (nd.kind == TGPU_EX_CONST) return !nd.is_null;
-        if (nd.kind == TGPU_EX_SPECIAL) return false;
-        for (int k = 0; k < nd.n_args; k++)
-            if (!never_null_given_inputs(nd.args[k])) return false;
-        return true;
-    };
     for (size_t k = 0; k < aggs_.size(); k++) {
         const tgpu_agg_spec &a = aggs_[k];
         // (min / max keep no lane-private sum either: their rows go straight to the state word, device_agg.h tg_minmax_update)
         const bool count_only = a.function == TGPU_AGG_COUNT_ALL || a.function == TGPU_AGG_COUNT_COLUMN || (a.function >= TGPU_AGG_MIN_BIGINT && a.function <= TGPU_AGG_MAX_DOUBLE);
-        const int in_root = a.function == TGPU_AGG_COUNT_ALL ? -1 : proj_roots_[(size_t)a.input_channel];
-        const int mask_root = a.mask_channel >= 0 ? proj_roots_[(size_t)a.mask_channel] : -1;
+        const int in_root = a.function == TGPU_AGG_COUNT_ALL ? -1 : prog_.proj_roots[(size_t)a.input_channel];
+        const int mask_root = a.mask_channel >= 0 ? prog_.proj_roots[(size_t)a.mask_channel] : -1;
         const int kind = a.function == TGPU_AGG_SUM_BIGINT ? 1 : (a.function == TGPU_AGG_AVG_BIGINT ? 2 : 0);
         if (count_only) wide_slot_[k] = -1;
         else {
@@ -3794,8 +3776,8 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
             std::set<int> ins;
             bool simple = true;
             if (in_root >= 0) {
-                inputs_of(in_root, ins);
-                simple = never_null_given_inputs(in_root);
+                prog_.inputs_of(in_root, ins);
+                simple = prog_.never_null_given_inputs(in_root);
             }
             cnt_inputs_.push_back(simple ? std::vector<int>(ins.begin(), ins.end()) : std::vector<int>{-1});
             cnt_masked_.push_back(mask_root >= 0);
@@ -3819,30 +3801,14 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
 
 FusedAggGpu::~FusedAggGpu() {}
 
-int FusedAggGpu::identity_channel(int ch) const
-{
-    const tgpu_expr_node &nd = nodes_[(size_t)proj_roots_[(size_t)ch]];
-    return nd.kind == TGPU_EX_INPUT ? nd.op : -1;
-}
-
 void FusedAggGpu::generate()
 {
-    auto cols_decl = [&](const Gen &g) {
-        std::ostringstream cols;
-        for (int ch : g.used_cols) {
-            const int32_t t = input_types_[(size_t)ch];
-            const char *T = (t == TGPU_VARCHAR || t == TGPU_BOOLEAN) ? "unsigned char" : ctype(t);
-            cols << "  const " << T << "* c" << ch << " = (const " << T << "*)A.col_values[" << ch << "]; (void)c" << ch << ";\n";
-            cols << "  const unsigned char* cn" << ch << " = FA_NO_NULLS ? (const unsigned char*)0 : A.col_nulls[" << ch << "]; (void)cn" << ch << ";\n";
-            if (t == TGPU_VARCHAR) cols << "  const int* co" << ch << " = A.col_offsets[" << ch << "]; (void)co" << ch << ";\n";
-        }
-        return cols.str();
-    };
+    auto cols_decl = [](const Gen &g) { return fused_cols_decl(g, "FA_NO_NULLS"); };
     // (a) the filter in memory mode (pass A)
-    Gen gm(nodes_, pool_, input_types_);
+    Gen gm(prog_);
     std::ostringstream filter_fn;
-    if (filter_root_ >= 0) {
-        Val f = gm.gen_root(filter_root_, 1, 0);
+    if (prog_.filter_root >= 0) {
+        Val f = gm.gen_root(prog_.filter_root, 1, 0);
         if (f.type != TGPU_BOOLEAN) gm.bad("filter must be boolean");
         filter_fn << "__device__ inline bool tg_filter_mem(const FpArgs& A, long long row) {\n" << cols_decl(gm) << gm.os.str() << "  return !" << f.n << " && " << f.v << ";\n}\n";
     }
@@ -3851,7 +3817,7 @@ void FusedAggGpu::generate()
     // (b) the aggregates' masks and inputs in register-row mode (pass C).  Phase 1 evaluates every aggregate's (take, value)
     // pair into registers; the low-cardinality variant then reads ALL the lane's LDS slots, updates them in registers and
     // writes them back (one LDS round trip per row instead of one per aggregate); the global variant issues the exact atomics.
-    Gen gr(nodes_, pool_, input_types_);
+    Gen gr(prog_);
     gr.reg_mode = true;
     gr.tmp = gm.tmp;
     std::ostringstream eval, lc_read, lc_upd, lc_write, gl, nf_any, nf_slow, nf_clear, ord_decl, ord_upd, ord_write, ch_decl, ch_upd, ch_write, ch_sum;
@@ -3868,13 +3834,13 @@ void FusedAggGpu::generate()
         eval << "  bool t" << k << " = true; double x" << k << " = 0.0; long long y" << k << " = 0; (void)x" << k << "; (void)y" << k << ";\n  {\n";
         gr.os.str("");
         if (a.mask_channel >= 0) {
-            Val m = gr.gen_root(proj_roots_[(size_t)a.mask_channel], 2, 1 + a.mask_channel);
+            Val m = gr.gen_root(prog_.proj_roots[(size_t)a.mask_channel], 2, 1 + a.mask_channel);
             eval << gr.os.str() << "    t" << k << " = !" << m.n << " && " << m.v << ";\n";
             gr.os.str("");
         }
         if (a.function != TGPU_AGG_COUNT_ALL) {
             eval << "    if (t" << k << ") {\n";
-            Val v = gr.gen_root(proj_roots_[(size_t)a.input_channel], 3, 1 + a.input_channel);
+            Val v = gr.gen_root(prog_.proj_roots[(size_t)a.input_channel], 3, 1 + a.input_channel);
             eval << gr.os.str();
             gr.os.str("");
             eval << "      if (" << v.n << ") t" << k << " = false;\n";
@@ -3984,21 +3950,7 @@ void FusedAggGpu::generate()
     src << "#define FA_LDS_BYTES " << std::max(2048, max_groups_ * per_group_bytes_) << "\n";   // >= the fold's exchange area (device_agg.h)
     // FA_NO_NULLS 1: the specialisation for pages without null vectors (null loads and per-aggregate count slots fold away)
     src << "#ifndef FA_NO_NULLS\n#define FA_NO_NULLS 0\n#endif\n";
-    src << "struct TgRow {\n";
-    for (int ch : gr.reg_cols) {
-        const int32_t t = input_types_[(size_t)ch];
-        src << "  " << (t == TGPU_BOOLEAN ? "unsigned char" : ctype(t)) << " c" << ch << "; unsigned char n" << ch << ";\n";
-    }
-    if (gr.reg_cols.empty()) src << "  int unused;\n";
-    src << "};\n__device__ inline void tg_load_row(const FpArgs& A, long long row, TgRow& R) {\n";
-    for (int ch : gr.reg_cols) {
-        const int32_t t = input_types_[(size_t)ch];
-        const char *T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
-        src << "  R.c" << ch << " = ((const " << T << "*)A.col_values[" << ch << "])[row]; R.n" << ch << " = (!FA_NO_NULLS && A.col_nulls[" << ch << "]) ? A.col_nulls[" << ch << "][row] : 0;\n";
-    }
-    src << "  (void)A; (void)row; (void)R;\n}\n__device__ inline void tg_zero_row(TgRow& R) {\n";
-    for (int ch : gr.reg_cols) src << "  R.c" << ch << " = 0; R.n" << ch << " = 0;\n";
-    src << "  (void)R;\n}\n";
+    src << row_decl(prog_.input_types, "TgRow", "row", gr.reg_cols, false, "FA_NO_NULLS");
     src << filter_fn.str();
     if (!key_inputs_.empty()) {
         // key accessor generated for this key schema (the GPU counterpart of JoinCompiler's hashRow / positionNotDistinctFromRow)
@@ -4008,7 +3960,7 @@ void FusedAggGpu::generate()
         auto cell = [&](int i, const std::string &row, const std::string &pfx) {
             // declares <pfx>n (null flag) and the cell's value variables for key column i of the raw input at `row`
             const int ch = key_inputs_[(size_t)i];
-            const int32_t t = input_types_[(size_t)ch];
+            const int32_t t = prog_.input_types[(size_t)ch];
             std::ostringstream o;
             o << "    const bool " << pfx << "n = !FA_NO_NULLS && A.col_nulls[" << ch << "] && A.col_nulls[" << ch << "][" << row << "];\n";
             if (t == TGPU_VARCHAR)
@@ -4022,7 +3974,7 @@ void FusedAggGpu::generate()
         };
         auto eq = [&](int i, const std::string &x, const std::string &y) {
             // value equality of two non-null cells (DOUBLE compared as IS NOT DISTINCT: NaN == NaN, -0 == +0)
-            const int32_t t = input_types_[(size_t)key_inputs_[(size_t)i]];
+            const int32_t t = prog_.input_types[(size_t)key_inputs_[(size_t)i]];
             std::ostringstream o;
             if (t == TGPU_VARCHAR)
                 o << "    { if (" << x << "l != " << y << "l) return false; for (int j_ = 0; j_ < " << x << "l; j_++) if (" << x << "p[j_] != " << y << "p[j_]) return false; }\n";
@@ -4035,7 +3987,7 @@ void FusedAggGpu::generate()
         src << "struct SpecKeys {\n  const FpArgs& A; const TgKeyCols& S; long long row0;\n";
         src << "  __device__ long long hash(long long r) const {\n    const long long row = row0 + r; tg_i64 h = 0;\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
-            const int32_t t = input_types_[(size_t)key_inputs_[i]];
+            const int32_t t = prog_.input_types[(size_t)key_inputs_[i]];
             src << "   {\n" << cell((int)i, "row", "x") << "    tg_i64 c = 0;\n    if (!xn) c = ";
             switch (t) {
             case TGPU_BIGINT: src << "tg_hash_long(xv)"; break;
@@ -4049,7 +4001,7 @@ void FusedAggGpu::generate()
         src << "    return h;\n  }\n";
         src << "  __device__ bool eq_store(long long r, int g) const {\n    const long long row = row0 + r;\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
-            const int32_t t = input_types_[(size_t)key_inputs_[i]];
+            const int32_t t = prog_.input_types[(size_t)key_inputs_[i]];
             src << "   {\n" << cell((int)i, "row", "x");
             src << "    const bool yn = S.c[" << i << "].nulls && S.c[" << i << "].nulls[g];\n";
             if (t == TGPU_VARCHAR)
@@ -4085,7 +4037,7 @@ void FusedAggGpu::generate()
         // varchar byte), so that the loads of all the stripes of a tile are in flight together
         src << "struct TgKeyRow {\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
-            const int32_t t = input_types_[(size_t)key_inputs_[i]];
+            const int32_t t = prog_.input_types[(size_t)key_inputs_[i]];
             if (t == TGPU_VARCHAR) src << "  int a" << i << ", e" << i << ", l" << i << "; unsigned char n" << i << ", b" << i << ";\n";
             else src << "  " << (t == TGPU_BOOLEAN ? "unsigned char" : (t == TGPU_DOUBLE ? "unsigned long long" : ctype(t))) << " v" << i << "; unsigned char n" << i << ";\n";
         }
@@ -4094,7 +4046,7 @@ void FusedAggGpu::generate()
         src << "};\n__device__ inline void fg_load_key_a(const FpArgs& A, long long tb, unsigned int o, TgKeyRow& K) {\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
             const int ch = key_inputs_[i];
-            const int32_t t = input_types_[(size_t)ch];
+            const int32_t t = prog_.input_types[(size_t)ch];
             src << "  K.n" << i << " = (!FA_NO_NULLS && A.col_nulls[" << ch << "]) ? (A.col_nulls[" << ch << "] + tb)[o] : 0;\n";
             if (t == TGPU_VARCHAR)
                 src << "  K.a" << i << " = (A.col_offsets[" << ch << "] + tb)[o]; K.e" << i << " = (A.col_offsets[" << ch << "] + tb)[o + 1u];\n";
@@ -4105,10 +4057,10 @@ void FusedAggGpu::generate()
         }
         src << "}\n__device__ inline void fg_key_lengths(TgKeyRow& K) {\n";
         for (size_t i = 0; i < key_inputs_.size(); i++)
-            if (input_types_[(size_t)key_inputs_[i]] == TGPU_VARCHAR) src << "  K.l" << i << " = K.e" << i << " - K.a" << i << ";\n";
+            if (prog_.input_types[(size_t)key_inputs_[i]] == TGPU_VARCHAR) src << "  K.l" << i << " = K.e" << i << " - K.a" << i << ";\n";
         src << "  (void)K;\n}\n__device__ inline void fg_zero_key(TgKeyRow& K) {\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
-            const int32_t t = input_types_[(size_t)key_inputs_[i]];
+            const int32_t t = prog_.input_types[(size_t)key_inputs_[i]];
             if (t == TGPU_VARCHAR) src << "  K.a" << i << " = 0; K.e" << i << " = 0; K.l" << i << " = 0; K.n" << i << " = 1; K.b" << i << " = 0;\n";
             else src << "  K.v" << i << " = 0; K.n" << i << " = 1;\n";
         }
@@ -4117,7 +4069,7 @@ void FusedAggGpu::generate()
         src << "}\n__device__ inline void fg_load_key_b(const FpArgs& A, TgKeyRow& K, bool live) {\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
             const int ch = key_inputs_[i];
-            if (input_types_[(size_t)ch] == TGPU_VARCHAR)
+            if (prog_.input_types[(size_t)ch] == TGPU_VARCHAR)
                 src << "  K.b" << i << " = ((const unsigned char*)A.col_values[" << ch << "])[(live && !K.n" << i << " && K.l" << i << " > 0) ? (unsigned int)K.a" << i << " : 0u];\n";
         }
         src << "  (void)live;\n";
@@ -4126,7 +4078,7 @@ void FusedAggGpu::generate()
         src << "__device__ inline int fg_eq_record(const FpArgs& A, const TgKeyRow& K, const unsigned char* rec, int g) {\n";
         for (size_t i = 0; i < key_inputs_.size(); i++) {
             const int ch = key_inputs_[i];
-            const int32_t t = input_types_[(size_t)ch];
+            const int32_t t = prog_.input_types[(size_t)ch];
             src << "  {\n    const unsigned char* r = rec + ((size_t)g * FG_NKEYS + " << i << ") * 32;\n";
             src << "    const bool xn = K.n" << i << " != 0, yn = r[20] != 0;\n    if (xn || yn) { if (xn != yn) return 0; } else {\n";
             if (t == TGPU_VARCHAR) {
@@ -4172,7 +4124,7 @@ void FusedAggGpu::generate()
             row_sig << "  open = false;\n  unsigned int nm = 0;\n";
             rec_sig << "  unsigned int nm = 0;\n";
             for (size_t i = 0; i < key_inputs_.size(); i++) {
-                const int32_t t = input_types_[(size_t)key_inputs_[i]];
+                const int32_t t = prog_.input_types[(size_t)key_inputs_[i]];
                 const std::string I = std::to_string(i);
                 row_sig << "  const bool n" << I << " = K.n" << I << " != 0; nm |= n" << I << " ? " << (1u << i) << "u : 0u;\n";
                 rec_sig << "  const unsigned char* r" << I << " = rec + ((size_t)g * FG_NKEYS + " << I << ") * 32;\n  const bool n" << I << " = r" << I << "[20] != 0; nm |= n" << I
@@ -4218,31 +4170,17 @@ void FusedAggGpu::generate()
         }
         // (c) the filter in register-row mode for the group probe: its fixed-width input columns are loaded in phase A
         {
-            Gen gf(nodes_, pool_, input_types_);
+            Gen gf(prog_);
             gf.reg_mode = true;
             gf.tmp = gr.tmp + 1000;
             std::ostringstream body;
-            if (filter_root_ >= 0) {
-                Val f = gf.gen_root(filter_root_, 1, 0);
+            if (prog_.filter_root >= 0) {
+                Val f = gf.gen_root(prog_.filter_root, 1, 0);
                 body << cols_decl(gf) << gf.os.str() << "  return !" << f.n << " && " << f.v << ";\n";
             }
             else body << "  return true;\n";
-            src << gf.consts.str() << "struct TgFRow {\n";
-            for (int ch : gf.reg_cols) {
-                const int32_t t = input_types_[(size_t)ch];
-                src << "  " << (t == TGPU_BOOLEAN ? "unsigned char" : ctype(t)) << " c" << ch << "; unsigned char n" << ch << ";\n";
-            }
-            if (gf.reg_cols.empty()) src << "  int unused;\n";
-            src << "};\n__device__ inline void tg_load_frow(const FpArgs& A, long long tb, unsigned int o, TgFRow& R) {\n";
-            for (int ch : gf.reg_cols) {
-                const int32_t t = input_types_[(size_t)ch];
-                const char *T = t == TGPU_BOOLEAN ? "unsigned char" : ctype(t);
-                src << "  R.c" << ch << " = ((const " << T << "*)A.col_values[" << ch << "] + tb)[o]; R.n" << ch << " = (!FA_NO_NULLS && A.col_nulls[" << ch << "]) ? (A.col_nulls[" << ch
-                    << "] + tb)[o] : 0;\n";
-            }
-            src << "  (void)A; (void)tb; (void)o; (void)R;\n}\n__device__ inline void tg_zero_frow(TgFRow& R) {\n";
-            for (int ch : gf.reg_cols) src << "  R.c" << ch << " = 0; R.n" << ch << " = 0;\n";
-            src << "  (void)R;\n}\n__device__ inline bool tg_filter_f(const FpArgs& A, long long row, const TgFRow& R) {\n" << body.str() << "}\n";
+            src << gf.consts.str() << row_decl(prog_.input_types, "TgFRow", "frow", gf.reg_cols, true, "FA_NO_NULLS");
+            src << "__device__ inline bool tg_filter_f(const FpArgs& A, long long row, const TgFRow& R) {\n" << body.str() << "}\n";
         }
         src << R"SRC(
 #ifndef FG_STRIPES
@@ -4461,16 +4399,6 @@ void FusedAggGpu::raise_if_error(Context *ctx, BufferPtr &err)
     raise_expression_error(ctx->read_scalar(err->as<unsigned long long>()));
 }
 
-static void fill_fp_cols(FpArgs &fp, const DevicePage &in)
-{
-    for (size_t i = 0; i < in.cols.size() && i < (size_t)kFpMaxCols; i++) {
-        fp.col_values[i] = in.cols[i].values;
-        fp.col_nulls[i] = in.cols[i].nulls;
-        fp.col_offsets[i] = in.cols[i].offsets;
-    }
-    fp.n = in.n;
-}
-
 void FusedAggGpu::filter_mask(Context *ctx, const DevicePage &in, uint8_t *mask_out)
 {
     TG_CHECK_STATE(supported_, "fused aggregation not supported for this configuration");
@@ -4507,6 +4435,55 @@ struct FgArgsHost {
 };
 }  // namespace
 
+// What accumulate() (one page) and onepass() (a list of pages) both put into the kernels' argument blocks.
+struct FusedAggGpu::HostFill {
+    // the kernels read byte 0 of a VARCHAR key column for rows without a first byte: an all-empty column (no values buffer) gets one to
+    // read, a zeroed `dummy` that is allocated on first need and shared by the pages of a launch
+    static void varchar_key_dummy(const FusedAggGpu &a, Context *ctx, FpArgs &fp, BufferPtr &dummy)
+    {
+        for (int ch : a.key_inputs_)
+            if (a.prog_.input_types[(size_t)ch] == TGPU_VARCHAR && fp.col_values[ch] == nullptr) {
+                if (!dummy) {
+                    dummy = ctx->alloc(16);
+                    HIP_CHECK(hipMemsetAsync(dummy->ptr(), 0, 16, ctx->stream()));
+                }
+                fp.col_values[ch] = dummy->ptr();
+            }
+    }
+    static void states(const FusedAggGpu &a, FaArgsHost &F, GroupedAccumulators &accs)
+    {
+        for (size_t k = 0; k < a.aggs_.size(); k++) {
+            GroupedAccumulators::DeviceState d = accs.device_state((int)k);
+            F.st[k].function = d.function;
+            F.st[k].counts = d.counts;
+            F.st[k].limbs = d.limbs;
+            F.st[k].special = d.special;
+            F.st[k].i128 = d.i128;
+            F.st[k].dsum = d.dsum;
+        }
+    }
+    // the slot plan of the lane-private states (n_groups is the launch's own)
+    static void plan(const FusedAggGpu &a, FaArgsHost &F, const std::vector<const DevicePage *> &pages)
+    {
+        F.plan.n_aggs = (int32_t)a.aggs_.size();
+        F.plan.n_wide = a.n_wide_;
+        F.plan.n_cnt = a.n_cnt_ + 1;
+        F.plan.rows_slot = a.rows_slot_;
+        for (size_t k = 0; k < a.aggs_.size(); k++) {
+            F.plan.wide_slot[k] = a.wide_slot_[k];
+            F.plan.cnt_slot[k] = a.cnt_slot_[k];
+            // the aggregate counts every row of its group when it has no mask and none of the columns its input reads has nulls
+            // in these pages: its count is then the group's row count (one shared LDS counter instead of one per aggregate)
+            const int cs = a.cnt_slot_[k];
+            bool from_rows = !a.cnt_masked_[(size_t)cs];
+            for (const DevicePage *pg : pages)
+                for (int ch : a.cnt_inputs_[(size_t)cs]) from_rows = from_rows && ch >= 0 && pg->cols[(size_t)ch].nulls == nullptr;
+            F.plan.count_from_rows[k] = from_rows ? 1 : 0;
+        }
+        F.plan.per_group_bytes = a.per_group_bytes_;
+    }
+};
+
 void FusedAggGpu::probe_groups(Context *ctx, const DevicePage &in, const GbhProbeLaunch &l)
 {
     TG_CHECK_STATE(supported_ && !key_inputs_.empty(), "fused group lookup not available for this configuration");
@@ -4514,16 +4491,8 @@ void FusedAggGpu::probe_groups(Context *ctx, const DevicePage &in, const GbhProb
     FgArgsHost G{};
     fill_fp_cols(G.fp, in);
     G.fp.error = l.counters + 7;   // the group-by table reads it back together with its own counters (GbhProbeLaunch)
-    // the kernel reads byte 0 of a varchar key column for rows without a first byte: give an all-empty column one to read
     BufferPtr dummy;
-    for (int ch : key_inputs_)
-        if (input_types_[(size_t)ch] == TGPU_VARCHAR && G.fp.col_values[ch] == nullptr) {
-            if (!dummy) {
-                dummy = ctx->alloc(16);
-                HIP_CHECK(hipMemsetAsync(dummy->ptr(), 0, 16, ctx->stream()));
-            }
-            G.fp.col_values[ch] = dummy->ptr();
-        }
+    HostFill::varchar_key_dummy(*this, ctx, G.fp, dummy);
     G.store = l.store;
     G.words = (unsigned long long *)l.words;
     G.mask = l.mask;
@@ -4561,39 +4530,11 @@ void FusedAggGpu::onepass(Context *ctx, const std::vector<const DevicePage *> &p
     auto fill = [&](FpArgs &fp, const DevicePage &pg) {
         fill_fp_cols(fp, pg);
         fp.error = counters + 7;
-        for (int ch : key_inputs_)
-            if (input_types_[(size_t)ch] == TGPU_VARCHAR && fp.col_values[ch] == nullptr) {
-                if (!dummy) {
-                    dummy = ctx->alloc(16);
-                    HIP_CHECK(hipMemsetAsync(dummy->ptr(), 0, 16, ctx->stream()));
-                }
-                fp.col_values[ch] = dummy->ptr();
-            }
+        HostFill::varchar_key_dummy(*this, ctx, fp, dummy);
     };
     fill(F.fp, in);
-    for (size_t k = 0; k < aggs_.size(); k++) {
-        GroupedAccumulators::DeviceState d = accs.device_state((int)k);
-        F.st[k].function = d.function;
-        F.st[k].counts = d.counts;
-        F.st[k].limbs = d.limbs;
-        F.st[k].special = d.special;
-        F.st[k].i128 = d.i128;
-        F.st[k].dsum = d.dsum;
-    }
-    F.plan.n_aggs = (int32_t)aggs_.size();
-    F.plan.n_wide = n_wide_;
-    F.plan.n_cnt = n_cnt_ + 1;
-    F.plan.rows_slot = rows_slot_;
-    for (size_t k = 0; k < aggs_.size(); k++) {
-        F.plan.wide_slot[k] = wide_slot_[k];
-        F.plan.cnt_slot[k] = cnt_slot_[k];
-        const int cs = cnt_slot_[k];
-        bool from_rows = !cnt_masked_[(size_t)cs];
-        for (const DevicePage *pg : pages)
-            for (int ch : cnt_inputs_[(size_t)cs]) from_rows = from_rows && ch >= 0 && pg->cols[(size_t)ch].nulls == nullptr;
-        F.plan.count_from_rows[k] = from_rows ? 1 : 0;
-    }
-    F.plan.per_group_bytes = per_group_bytes_;
+    HostFill::states(*this, F, accs);
+    HostFill::plan(*this, F, pages);
     F.lowcard = 1;
     F.plan.n_groups = (int32_t)groups;
     F.tiles = ceil_div(in.n, 8 * 256);
@@ -4667,15 +4608,7 @@ void FusedAggGpu::accumulate(Context *ctx, const DevicePage &in, const int32_t *
     F.gids = gids;
     F.gids8 = gids8;
     F.gate = gate;
-    for (size_t k = 0; k < aggs_.size(); k++) {
-        GroupedAccumulators::DeviceState d = accs.device_state((int)k);
-        F.st[k].function = d.function;
-        F.st[k].counts = d.counts;
-        F.st[k].limbs = d.limbs;
-        F.st[k].special = d.special;
-        F.st[k].i128 = d.i128;
-        F.st[k].dsum = d.dsum;
-    }
+    HostFill::states(*this, F, accs);
     if (ordered) {
         F.ord_keys = ord_keys->as<unsigned int>();
         F.ord_rows = ord_rows->as<int>();
@@ -4713,21 +4646,7 @@ void FusedAggGpu::accumulate(Context *ctx, const DevicePage &in, const int32_t *
         if (accumulate_can_raise_) raise_if_error(ctx, err);
         return;
     }
-    F.plan.n_aggs = (int32_t)aggs_.size();
-    F.plan.n_wide = n_wide_;
-    F.plan.n_cnt = n_cnt_ + 1;
-    F.plan.rows_slot = rows_slot_;
-    for (size_t k = 0; k < aggs_.size(); k++) {
-        F.plan.wide_slot[k] = wide_slot_[k];
-        F.plan.cnt_slot[k] = cnt_slot_[k];
-        // the aggregate counts every row of its group when it has no mask and none of the columns its input reads has nulls
-        // in this page: its count is then the group's row count (one shared LDS counter instead of one per aggregate)
-        const int cs = cnt_slot_[k];
-        bool from_rows = !cnt_masked_[(size_t)cs];
-        for (int ch : cnt_inputs_[(size_t)cs]) from_rows = from_rows && ch >= 0 && in.cols[(size_t)ch].nulls == nullptr;
-        F.plan.count_from_rows[k] = from_rows ? 1 : 0;
-    }
-    F.plan.per_group_bytes = per_group_bytes_;
+    HostFill::plan(*this, F, {&in});
     const int64_t g = groups > 0 ? groups : 1;
     F.lowcard = (g <= max_groups_ && getenv("TGPU_DISABLE_LOWCARD") == nullptr) ? 1 : 0;
     F.plan.n_groups = F.lowcard ? (int32_t)g : 0;

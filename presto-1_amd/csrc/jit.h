@@ -4,6 +4,7 @@
 #pragma once
 
 #include <algorithm>
+#include <set>
 
 #include "common.h"
 
@@ -39,6 +40,29 @@ struct FvArgs {  // must match the struct declared in the generated source
 
 struct JitModule;
 
+// The expressions of one page processor spec, copied: what the three generators below (page processor, fused join probe, fused aggregation)
+// compile.  A node array with a string pool, the filter's root (-1: none) and one root per projection.
+struct ExprProgram {
+    // refuses a null spec, a bad node array and a negative projection count; everything else is the generators' business
+    ExprProgram(std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec);
+    std::vector<int32_t> input_types;
+    std::vector<tgpu_expr_node> nodes;
+    std::string pool;
+    int filter_root;
+    std::vector<int32_t> proj_roots, proj_types;
+    // proj_types = the type of every projection's root; refuses a root outside the node array.  The fused generators index by it; the page
+    // processor leaves a bad root to its code generator.
+    void resolve_projection_types();
+    // The expression under `root` can fail at run time.  A fused plan evaluates some projections lazily or not at all, where
+    // FilterAndProjectOperator evaluates every one on every selected row: that is only equivalent for projections that cannot raise, so the
+    // fused generators keep the unfused composition for the others.
+    bool can_raise(int root) const;
+    void inputs_of(int root, std::set<int> &out) const;   // the input channels the expression reads
+    int identity_channel(int projection) const;            // the input channel a projection passes through, -1 when it is computed
+    // the expression is null only if one of its input columns is (no null literal, no IF / COALESCE subtleties)
+    bool never_null_given_inputs(int root) const;
+};
+
 // PageProcessor (M/operator/project/PageProcessor.java:111-137): filter, then projections on the selected positions only.
 class PageProcessorGpu {
 public:
@@ -67,7 +91,7 @@ public:
     // entry: [the filter's verdict as BOOLEAN (only when there is a filter), every computed projection in slot order].
     // Throws like process() when an entry raises (the caller then falls back to the flat path: only selected rows may raise).
     void process_dictionary(Context *ctx, const DeviceColumn &dictionary, DevicePage &out);
-    bool has_filter() const { return filter_root_ >= 0; }
+    bool has_filter() const { return prog_.filter_root >= 0; }
     // per projection: -1 = computed (its slot via computed_slot), else the input channel it passes through
     int identity_channel(int projection) const { return projs_[(size_t)projection].kind == ProjKind::IDENTITY ? projs_[(size_t)projection].channel : -1; }
     bool is_null_constant(int projection) const { return projs_[(size_t)projection].kind == ProjKind::CONSTANT_NULL; }
@@ -87,11 +111,7 @@ private:
     void ensure_loaded(Context *ctx);
     std::mutex mu_;
 
-    std::vector<int32_t> input_types_;
-    std::vector<tgpu_expr_node> nodes_;
-    std::string pool_;
-    int filter_root_;
-    std::vector<int32_t> proj_roots_;
+    ExprProgram prog_;
     std::vector<Proj> projs_;
     std::vector<int32_t> output_types_;
     int computed_count_ = 0, varchar_count_ = 0;
@@ -169,7 +189,7 @@ public:
                                                  const std::vector<int32_t> &output_channels);   // see PageProcessorGpu::shared
     void precompile();
     bool supported() const { return supported_; }   // false -> the operator runs the unfused composition
-    const std::vector<int32_t> &projection_types() const { return proj_types_; }
+    const std::vector<int32_t> &projection_types() const { return prog_.proj_types; }
     // probes `in` against the lookup source's int-key table; returns the probe-side output columns + build positions
     // need_build_positions = false (no build output channels, no outer tracking): build_idx is left undefined and the DIRECT
     // layout skips its rank / position lookups
@@ -203,11 +223,8 @@ private:
     void generate();
     struct JitModule *module_for(int prefilter_kind, bool no_nulls, int carry, int epilogue, int depth);
     std::mutex mu_;
-    std::vector<int32_t> input_types_;
-    std::vector<tgpu_expr_node> nodes_;
-    std::string pool_;
-    int filter_root_;
-    std::vector<int32_t> proj_roots_, proj_types_, output_channels_;
+    ExprProgram prog_;
+    std::vector<int32_t> output_channels_;
     int32_t join_channel_;
     bool supported_ = false;
     std::string source_;
@@ -236,10 +253,10 @@ public:
     ~FusedAggGpu();
     void precompile();
     bool supported() const { return supported_; }
-    bool has_filter() const { return filter_root_ >= 0; }
+    bool has_filter() const { return prog_.filter_root >= 0; }
     // channel of the raw input page behind projection `ch` when that projection is a plain column reference, else -1
-    int identity_channel(int ch) const;
-    const std::vector<int32_t> &projection_types() const { return proj_types_; }
+    int identity_channel(int ch) const { return prog_.identity_channel(ch); }
+    const std::vector<int32_t> &projection_types() const { return prog_.proj_types; }
     // mask[row] = 1 iff the filter selects the row (PageFilter semantics); raises the filter's arithmetic errors
     void filter_mask(Context *ctx, const DevicePage &in, uint8_t *mask_out);
     // state[gid[row]] (+)= aggregate inputs of every row with gid >= 0
@@ -274,11 +291,8 @@ private:
     struct JitModule *module_variant(bool nulls, bool gid8);
     std::mutex mu_;
     void raise_if_error(Context *ctx, BufferPtr &err);
-    std::vector<int32_t> input_types_;
-    std::vector<tgpu_expr_node> nodes_;
-    std::string pool_;
-    int filter_root_;
-    std::vector<int32_t> proj_roots_, proj_types_;
+    struct HostFill;   // fills of the kernels' argument blocks that accumulate() and onepass() share (jit.cpp)
+    ExprProgram prog_;
     std::vector<tgpu_agg_spec> aggs_;
     std::vector<int> key_inputs_;
     bool supported_ = false;

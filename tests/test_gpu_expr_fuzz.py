@@ -272,7 +272,7 @@ def test_scan_operator_matches_the_evaluator(pkg, ctx, mode, seed):
     check(prog, outs, err, cut_outcome(prog)[0], "scan", position=False, one_input_page=False)
 
 
-# ---- a raising operator in every place of a fused plan: the two hand-kept can_raise predicates of csrc/jit.cpp -----------------------------
+# ---- a raising operator in every place of a fused plan: ExprProgram::can_raise of csrc/jit.cpp, the one predicate both fused plans ask ----
 ROWS, BAD = 65, 40      # one failing row
 
 
