@@ -627,6 +627,45 @@ int32_t tgpu_window_factory_create_framed(tgpu_context *ctx, int32_t operator_id
                                           int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
                                           int32_t expected_positions, tgpu_operator_factory **out);
 
+/* The same operator with RANGE BETWEEN x PRECEDING / FOLLOWING AND y PRECEDING / FOLLOWING as well: "the rows whose sort key lies within x of mine"
+ * (getFrameRange / seek, M/operator/window/WindowPartition.java:325-521; FrameInfo.java; WindowOperator.createFrameBoundComparators :420-443).  The
+ * arguments are those of tgpu_window_factory_create_framed with frames of tgpu_window_range_frame_spec.  A frame of any other kind -- ROWS, GROUPS,
+ * RANGE by peers -- behaves exactly as through tgpu_window_factory_create_framed, errors included; the two sort key fields are not read for it.
+ * RANGE with a PRECEDING / FOLLOWING bound.  The operator has exactly ONE sort channel.  start_channel / end_channel do not hold an offset: they hold
+ * the bound VALUE per row, sort key - / + offset, computed in front of the operator (ASC: PRECEDING = key - offset, FOLLOWING = key + offset; DESC the
+ * other way round; the offset is checked there to be non-negative and not null).  start_sort_key_channel / end_sort_key_channel hold the sort key
+ * coerced to the bound's type (FrameInfo.sortKeyChannelForStartComparison / ...EndComparison; the sort channel itself where no coercion is needed).
+ * Bound and comparison key are of one type, BIGINT, INTEGER, DATE or DOUBLE, compared with the type's comparison operator (DOUBLE: -0.0 < +0.0, NaN
+ * above +inf, as the sort has it).  TGPU_ERR_INVALID_ARGUMENT when the factory is created: not exactly one sort channel, a channel out of range, a
+ * bound and its comparison key of different types, another type.  The analyzer's bound combinations are checked as before.
+ * THE FRAME.  [lo, hi] = the partition's run of rows with a non-null sort key, K = the comparison key in sorted order, B = the current row's bound,
+ * "K[p] <~ B" = K[p] <= B under ASC and K[p] >= B under DESC.
+ *   a row whose sort key is null       its peer group (the partition's nulls), from the partition's first row for an UNBOUNDED_PRECEDING start and to
+ *                                      its last row for an UNBOUNDED_FOLLOWING end.  Its bounds are never read.
+ *   a row whose sort key is not null   start with a value: the first p in [lo, hi] with B <~ K[p], else hi + 1.  end with a value: the last p in [lo, hi]
+ *                                      with K[p] <~ B, else lo - 1.  CURRENT_ROW: the peer group's first / last row.  UNBOUNDED_*: the partition's
+ *                                      first / last row.  Nulls enter such a frame through UNBOUNDED_* only -- and as hi + 1 / lo - 1 where that is
+ *                                      the block of nulls (1 FOLLOWING .. UNBOUNDED_FOLLOWING with nulls last: the largest key's frame is the nulls).
+ *   empty                              start > end, start behind the partition, end in front of it (emptyFrame, :523-528)
+ * These are the reference's frames whenever the bounds are what a planner produces (key -/+ a non-negative finite offset, without overflow).  For any
+ * other bound (inf - inf, a bound on the wrong side of the row's key) the reference's walk leaves the partition; the library gives the closed form
+ * above and reads nothing outside the partition.  A comparison key that is NOT monotone in the sort key gives an unspecified frame inside the
+ * partition (the search bisects).
+ * get_output fails with TGPU_ERR_INVALID_ARGUMENT, before any other error of the page: "Window frame starting offset must not be null" / "Window frame
+ * ending offset must not be null" for a null bound in a row whose sort key is not null; "Window frame comparison key must not be null where the sort
+ * key is not null" for a null comparison key in such a row.  memory_bytes also counts the search arrays: 8 bytes per row and distinct comparison key
+ * channel, and one byte per row. */
+typedef struct tgpu_window_range_frame_spec {
+    int32_t type, start_type, start_channel, end_type, end_channel;
+    int32_t start_sort_key_channel, end_sort_key_channel;   /* FrameInfo.sortKeyChannelForStartComparison / sortKeyChannelForEndComparison */
+} tgpu_window_range_frame_spec;
+int32_t tgpu_window_factory_create_ranged(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                          int32_t output_channel_count, const int32_t *output_channels,
+                                          int32_t function_count, const tgpu_window_function_spec *functions, const tgpu_window_range_frame_spec *frames,
+                                          int32_t partition_channel_count, const int32_t *partition_channels,
+                                          int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                          int32_t expected_positions, tgpu_operator_factory **out);
+
 /* FilterAndProjectOperator feeding HashAggregationOperator as one fused pipeline (what LocalExecutionPlanner.visitAggregation,
  * M/sql/planner/LocalExecutionPlanner.java:1198,2965-3056, would construct over a filter/project source; the shape of
  * testing/trino-benchmark HandTpchQuery1.java:60-133).  Same results as the two reference operators back to back.  `spec`'s

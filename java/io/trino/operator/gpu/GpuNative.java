@@ -128,6 +128,8 @@ public final class GpuNative
 
     /** WindowOperatorFactory with FrameInfo frames (tgpu_window_factory_create_framed): createWindowFactory plus frames = int[function][5] flattened: {type, startType, startChannel, endType, endChannel} (GpuOperatorFactories.windowFrame); the frame field of a function is not read; nth_value and ntile exist here only */
     public static native long createFramedWindowFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] functions, int[] frames, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int expectedPositions);
+    /** WindowOperatorFactory with RANGE frames whose bounds are values (tgpu_window_factory_create_ranged): createFramedWindowFactory with frames = int[function][7] flattened: {type, startType, startChannel, endType, endChannel, startSortKeyChannel, endSortKeyChannel} (GpuOperatorFactories.windowRangeFrame); for RANGE with a PRECEDING / FOLLOWING bound the channels hold the bound's value and the comparison key */
+    public static native long createRangeWindowFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] functions, int[] frames, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int expectedPositions);
     /** LimitOperatorFactory (tgpu_limit_factory_create): the first limit rows of the stream */
     public static native long createLimitFactory(long context, int operatorId, int[] types, long limit);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);

@@ -542,6 +542,57 @@ public final class GpuOperatorFactories
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuWindowOperator", sourceTypes, poller, factory));
     }
 
+    /**
+     * one frame as the seven ints of tgpu_window_range_frame_spec: windowFrame(..) plus FrameInfo's two comparison key channels.  For a RANGE frame with a
+     * PRECEDING / FOLLOWING bound the start / end channel holds the bound's VALUE (sort key -/+ offset, QueryPlanner.planFrameBound), not an offset
+     */
+    public static int[] windowRangeFrame(FrameInfo frame)
+    {
+        return new int[] {frame.getType().ordinal(), frame.getStartType().ordinal(), frame.getStartChannel(), frame.getEndType().ordinal(), frame.getEndChannel(),
+                frame.getSortKeyChannelForStartComparison(), frame.getSortKeyChannelForEndComparison()};
+    }
+
+    /**
+     * framedWindow(..) with RANGE BETWEEN x PRECEDING / FOLLOWING AND y PRECEDING / FOLLOWING as well (tgpu_window_factory_create_ranged).  functions: one
+     * windowFunction(..) per WindowFunctionDefinition; frames: its FrameInfo.  Optional.empty() for a type without a code, and for a RANGE frame with a value
+     * bound unless FrameInfo.getSortKeyChannel() is the node's single sort channel and getOrdering() agrees with its sort order; the caller returns it itself for
+     * IGNORE NULLS and DOUBLE sums and averages, as for window(..).
+     */
+    public Optional<OperatorFactory> rangeWindow(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> outputChannels, List<int[]> functions,
+            List<FrameInfo> frames, List<Integer> partitionChannels, List<Integer> sortChannels, List<SortOrder> sortOrders, int expectedPositions)
+    {
+        if (frames.size() != functions.size()) {
+            throw new IllegalArgumentException("one frame per window function");
+        }
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        int[] flat = new int[functions.size() * 8];
+        int[] flatFrames = new int[frames.size() * 7];
+        for (int i = 0; i < functions.size(); i++) {
+            System.arraycopy(functions.get(i), 0, flat, i * 8, 8);
+            FrameInfo info = frames.get(i);
+            int[] frame = windowRangeFrame(info);
+            if (frame[0] == FRAME_TYPE_RANGE && (hasOffset(frame[1]) || hasOffset(frame[3]))) {
+                if (sortChannels.size() != 1 || sortOrders.size() != 1 || info.getSortKeyChannel() != sortChannels.get(0) || info.getOrdering().isEmpty()) {
+                    return Optional.empty();
+                }
+                boolean ascending = info.getOrdering().get() == io.trino.sql.tree.SortItem.Ordering.ASCENDING;
+                if (ascending != sortOrders.get(0).isAscending()) {
+                    return Optional.empty();
+                }
+            }
+            System.arraycopy(frame, 0, flatFrames, i * 7, 7);
+        }
+        long factory = GpuNative.createRangeWindowFactory(context, operatorId, codes, ints(outputChannels), flat, flatFrames, ints(partitionChannels), ints(sortChannels),
+                sortOrders.stream().mapToInt(SortOrder::ordinal).toArray(), expectedPositions);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuWindowOperator", sourceTypes, poller, factory));
+    }
+
     /** LimitOperator.LimitOperatorFactory (operator/LimitOperator.java:34-39; LocalExecutionPlanner.visitLimit) */
     public Optional<OperatorFactory> limit(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, long limit)
     {

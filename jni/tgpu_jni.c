@@ -866,6 +866,93 @@ JFN(jlong, createFramedWindowFactory)(JNIEnv *env, jclass c, jlong ctx, jint ope
     return factory_result(env, rc, f);
 }
 
+/* one frame of createRangeWindowFactory: {type, startType, startChannel, endType, endChannel, startSortKeyChannel, endSortKeyChannel} =
+ * tgpu_window_range_frame_spec.  A RANGE frame with a PRECEDING / FOLLOWING bound is checked here; every other frame is window_frame_problem's */
+static const char *window_range_frame_problem(const jint *w, const ints *t, jsize sort_channels, int32_t *code)
+{
+    const jint type = w[0], start = w[1], end = w[3];
+    const int start_value = start == TGPU_BOUND_PRECEDING || start == TGPU_BOUND_FOLLOWING, end_value = end == TGPU_BOUND_PRECEDING || end == TGPU_BOUND_FOLLOWING;
+    if (type != TGPU_FRAME_TYPE_RANGE || !(start_value || end_value)) return window_frame_problem(w, t, code);
+    *code = TGPU_ERR_INVALID_ARGUMENT;
+    if (start < TGPU_BOUND_UNBOUNDED_PRECEDING || start > TGPU_BOUND_UNBOUNDED_FOLLOWING) return "unknown window frame bound";
+    if (end < TGPU_BOUND_UNBOUNDED_PRECEDING || end > TGPU_BOUND_UNBOUNDED_FOLLOWING) return "unknown window frame bound";
+    if (start == TGPU_BOUND_UNBOUNDED_FOLLOWING || end == TGPU_BOUND_UNBOUNDED_PRECEDING || (start == TGPU_BOUND_CURRENT_ROW && end == TGPU_BOUND_PRECEDING) ||
+        (start == TGPU_BOUND_FOLLOWING && end != TGPU_BOUND_FOLLOWING && end != TGPU_BOUND_UNBOUNDED_FOLLOWING))
+        return "invalid window frame bounds";
+    if (sort_channels != 1) return "a RANGE frame with an offset needs exactly one sort channel";
+    for (int side = 0; side < 2; side++) {
+        if (!(side == 0 ? start_value : end_value)) continue;
+        const jint bound = side == 0 ? w[2] : w[4], key = side == 0 ? w[5] : w[6];
+        if (bound < 0 || bound >= t->n) return "frame bound channel out of range";
+        if (key < 0 || key >= t->n) return "frame comparison key channel out of range";
+        if (t->p[bound] != t->p[key]) return "a frame bound and its comparison key differ in type";
+        if (t->p[bound] != TGPU_BIGINT && t->p[bound] != TGPU_INTEGER && t->p[bound] != TGPU_DATE && t->p[bound] != TGPU_DOUBLE)
+            return "a RANGE frame bound must be BIGINT, INTEGER, DATE or DOUBLE";
+    }
+    return NULL;
+}
+
+/* WindowOperatorFactory with RANGE frames whose bounds are values (tgpu_window_factory_create_ranged): createFramedWindowFactory's arguments with frames =
+ * int[function][7] flattened.  The same checks in front of the library; a RANGE frame with a PRECEDING / FOLLOWING bound needs exactly one sort channel, its
+ * bound and comparison key channels in range, of one type, BIGINT / INTEGER / DATE / DOUBLE */
+JFN(jlong, createRangeWindowFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray functions, jintArray frames,
+                                     jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders, jint expectedPositions)
+{
+    UNUSED(c);
+    _Static_assert(sizeof(tgpu_window_function_spec) == 8 * sizeof(jint), "the flattened function array is read as tgpu_window_function_spec");
+    _Static_assert(sizeof(tgpu_window_range_frame_spec) == 7 * sizeof(jint), "the flattened frame array is read as tgpu_window_range_frame_spec");
+    ints t = ints_get(env, types), oc = ints_get(env, outputChannels), fn = ints_get(env, functions), fr = ints_get(env, frames), pc = ints_get(env, partitionChannels),
+         sc = ints_get(env, sortChannels), so = ints_get(env, sortOrders);
+    const char *bad = NULL;
+    int32_t code = TGPU_ERR_INVALID_ARGUMENT;
+    if (t.n <= 0) bad = "empty type array";
+    for (jsize i = 0; !bad && i < t.n; i++)
+        if (t.p[i] < TGPU_BIGINT || t.p[i] > TGPU_VARCHAR) bad = "unknown type";
+    for (jsize i = 0; !bad && i < oc.n; i++)
+        if (oc.p[i] < 0 || oc.p[i] >= t.n) bad = "output channel out of range";
+    if (!bad && sc.n != so.n) bad = "sort channels and sort orders differ in length";
+    if (!bad && pc.n + sc.n > 8) bad = "more than 8 partition and sort channels";
+    for (jsize i = 0; !bad && i < pc.n; i++)
+        if (pc.p[i] < 0 || pc.p[i] >= t.n) bad = "partition channel out of range";
+    for (jsize i = 0; !bad && i < sc.n; i++) {
+        if (sc.p[i] < 0 || sc.p[i] >= t.n) bad = "sort channel out of range";
+        else if (so.p[i] < TGPU_SORT_ASC_NULLS_FIRST || so.p[i] > TGPU_SORT_DESC_NULLS_LAST) bad = "sort order out of range";
+    }
+    if (!bad && fn.n % 8 != 0) bad = "malformed function array";
+    if (!bad && fn.n == 0) bad = "no window function";
+    if (!bad && fn.n / 8 > TGPU_WINDOW_MAX_FUNCTIONS) bad = "more than 16 window functions";
+    if (!bad && fr.n % 7 != 0) bad = "malformed frame array";
+    if (!bad && fr.n / 7 != fn.n / 8) bad = "frame array and function array differ in length";
+    for (jsize i = 0; !bad && i < fn.n / 8; i++) {
+        bad = window_function_problem_of(fn.p + 8 * i, &t, &code, 1);
+        if (!bad) bad = window_range_frame_problem(fr.p + 7 * i, &t, sc.n, &code);
+    }
+    if (!bad && expectedPositions <= 0) {
+        code = TGPU_ERR_INVALID_ARGUMENT;
+        bad = "expected positions must be positive";
+    }
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = 0;
+    if (!bad)
+        rc = tgpu_window_factory_create_ranged(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, oc.n, (const int32_t *)oc.p, fn.n / 8,
+                                               (const tgpu_window_function_spec *)fn.p, (const tgpu_window_range_frame_spec *)fr.p, pc.n, (const int32_t *)pc.p, sc.n,
+                                               (const int32_t *)sc.p, (const int32_t *)so.p, expectedPositions, &f);
+    ints_release(env, &so);
+    ints_release(env, &sc);
+    ints_release(env, &pc);
+    ints_release(env, &fr);
+    ints_release(env, &fn);
+    ints_release(env, &oc);
+    ints_release(env, &t);
+    if (bad) {
+        char message[128];
+        snprintf(message, sizeof(message), "window: %s", bad);
+        throw_native_message(env, code, message);
+        return 0;
+    }
+    return factory_result(env, rc, f);
+}
+
 JFN(jlong, createWindowFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray functions,
                                 jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders, jint expectedPositions)
 {

@@ -17,5 +17,5 @@ from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_
                         FRAME_PARTITION, FRAME_RANGE_TO_CURRENT, FRAME_ROWS_TO_CURRENT, WINDOW_AGGREGATE, WINDOW_CUME_DIST, WINDOW_DENSE_RANK, WINDOW_FIRST_VALUE,
                         WINDOW_LAG, WINDOW_LAST_VALUE, WINDOW_LEAD, WINDOW_PERCENT_RANK, WINDOW_RANK, WINDOW_ROW_NUMBER, WindowFunction, WindowOperatorFactory,
                         WINDOW_NTH_VALUE, WINDOW_NTILE, FRAME_TYPE_RANGE, FRAME_TYPE_ROWS, FRAME_TYPE_GROUPS, BOUND_UNBOUNDED_PRECEDING, BOUND_PRECEDING, BOUND_CURRENT_ROW,
-                        BOUND_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING, WindowFrame)
+                        BOUND_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING, WindowFrame, WindowRangeFrame, window_range_bound)
 from .spi import (BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR, Block, DeviceBlock, DictionaryBlock, LazyBlock, OutputPage, Page, RunLengthEncodedBlock)

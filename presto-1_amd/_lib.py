@@ -96,6 +96,11 @@ class WindowFrameSpec(C.Structure):
     _fields_ = [("type", C.c_int32), ("start_type", C.c_int32), ("start_channel", C.c_int32), ("end_type", C.c_int32), ("end_channel", C.c_int32)]
 
 
+class WindowRangeFrameSpec(C.Structure):
+    _fields_ = [("type", C.c_int32), ("start_type", C.c_int32), ("start_channel", C.c_int32), ("end_type", C.c_int32), ("end_channel", C.c_int32),
+                ("start_sort_key_channel", C.c_int32), ("end_sort_key_channel", C.c_int32)]
+
+
 _lib = None
 
 # every symbol include/tgpu.h declares: (restype, argtypes)
@@ -192,6 +197,8 @@ SYMBOLS = {
     "tgpu_top_n_ranking_factory_create": (i32, [vp, i32, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, P(i32), P(i32), i64, i32, i32, i32, P(vp)]),
     "tgpu_window_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(WindowFunctionSpec), i32, P(i32), i32, P(i32), P(i32), i32, P(vp)]),
     "tgpu_window_factory_create_framed": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(WindowFunctionSpec), P(WindowFrameSpec), i32, P(i32), i32, P(i32), P(i32), i32,
+                                                P(vp)]),
+    "tgpu_window_factory_create_ranged": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(WindowFunctionSpec), P(WindowRangeFrameSpec), i32, P(i32), i32, P(i32), P(i32), i32,
                                                 P(vp)]),
     "tgpu_row_number_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), i64, i32, i32, P(vp)]),
     "tgpu_limit_factory_create": (i32, [vp, i32, i32, P(i32), i64, P(vp)]),

@@ -1298,6 +1298,38 @@ int32_t tgpu_window_factory_create_framed(tgpu_context *ctx, int32_t operator_id
     });
 }
 
+int32_t tgpu_window_factory_create_ranged(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t output_channel_count,
+                                          const int32_t *output_channels, int32_t function_count, const tgpu_window_function_spec *functions,
+                                          const tgpu_window_range_frame_spec *frames, int32_t partition_channel_count, const int32_t *partition_channels,
+                                          int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders, int32_t expected_positions,
+                                          tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(function_count >= 0 && (function_count == 0 || (functions != nullptr && frames != nullptr)), "window functions missing");
+        std::vector<WindowFunctionSpec> specs;
+        for (int32_t i = 0; i < function_count; i++) {
+            const tgpu_window_function_spec &f = functions[i];
+            const tgpu_window_range_frame_spec &w = frames[i];
+            TG_CHECK_ARG(f.argument_count >= 0 && f.argument_count <= 3, "a window function takes 0 to 3 arguments");
+            WindowFunctionSpec spec{f.function, f.agg_function, 0, vec(f.argument_channels, f.argument_count), f.ignore_nulls};
+            spec.general = 1;
+            spec.ranged = 1;
+            spec.frame_type = w.type;
+            spec.start_type = w.start_type;
+            spec.start_channel = w.start_channel;
+            spec.end_type = w.end_type;
+            spec.end_channel = w.end_channel;
+            spec.start_sort_key_channel = w.start_sort_key_channel;
+            spec.end_sort_key_channel = w.end_sort_key_channel;
+            specs.push_back(std::move(spec));
+        }
+        make_factory<WindowOperatorFactory>(ctx, out, operator_id,
+                                            WindowConfig{vec(types, type_count), vec(output_channels, output_channel_count), std::move(specs),
+                                                         vec(partition_channels, partition_channel_count), vec(sort_channels, sort_channel_count),
+                                                         vec(sort_orders, sort_channel_count), expected_positions});
+    });
+}
+
 int32_t tgpu_row_number_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t output_channel_count,
                                        const int32_t *output_channels, int32_t partition_channel_count, const int32_t *partition_channels,
                                        int64_t max_rows_per_partition, int32_t hash_channel, int32_t expected_positions, tgpu_operator_factory **out)

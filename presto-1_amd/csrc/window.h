@@ -16,6 +16,10 @@ struct WindowFunctionSpec {
     // the three frames the old entry point knows back into their `frame` code (general = 0), so that they take the old path bit for bit.
     int32_t general = 0;
     int32_t frame_type = 0, start_type = 0, start_channel = -1, end_type = 0, end_channel = -1;
+    // tgpu_window_factory_create_ranged: a RANGE frame may have PRECEDING / FOLLOWING bounds; start_channel / end_channel then hold the bound VALUE
+    // and the two fields below the comparison key (tgpu_window_range_frame_spec).  Not read for any other frame.
+    int32_t ranged = 0;
+    int32_t start_sort_key_channel = -1, end_sort_key_channel = -1;
 };
 
 class WindowGpu {
@@ -34,7 +38,7 @@ public:
     // `all` = every source channel of the whole input.  *positions = its rows in output order (null: arrival order, nothing was sorted);
     // the result = one column per function, in output order.  Raises the sum overflow / negative offset errors.
     std::vector<DeviceColumn> evaluate(const DevicePage &all, BufferPtr *positions);
-    int64_t scratch_bytes() const { return scratch_bytes_; }   // positions + scan arrays + frame arrays + range-extreme index of the last evaluate()
+    int64_t scratch_bytes() const { return scratch_bytes_; }   // positions + scan arrays + frame arrays + range-extreme index + RANGE search arrays of the last evaluate()
 
 private:
     Context *ctx_;

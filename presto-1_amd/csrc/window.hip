@@ -43,10 +43,20 @@
 //                  so a query reads two to four words, whatever the frame's width.  Frames never cross a partition: nothing is segmented.
 //                  count and sum take the difference of the running arrays at e and s - 1; the sum's running value is kept in both words (`hi`),
 //                  and launch 3 raises no prefix overflow for it: only a frame's own sum outside int64 does, in the evaluate kernel.
+// RANGE frames with a k PRECEDING / k FOLLOWING bound (tgpu_window_factory_create_ranged) fill the same frame_start / frame_end arrays in 4a:
+//   4a'. KEYS      window_range_keys_kernel, once per distinct comparison key channel: codes[i] = the order code (device_order.h) of the comparison
+//                  key of row positions[i], complemented under a descending sort, and key_null[i] = the SORT key of that row is null: one gather,
+//                  after which every comparison is an unsigned compare of neighbouring words of one contiguous array.
+//        BOUNDS    window_range_bounds_kernel, once per distinct frame: the row's bound values read through positions and encoded the same way, the
+//                  partition's run of non-null keys from the null peer group (the nulls of ONE sort channel are one peer group at the partition's
+//                  head or tail: two loads, no search), then per bound a gallop outward from the row's own position and a bisection
+//                  (device_range_frame.h, which a host program compiles as it stands).  No row reads another row's result.
 #include "window.h"
 #include "kernels.h"
 #include "topn.h"
 #include "device_agg.h"
+#include "device_order.h"
+#include "device_range_frame.h"
 
 #include <algorithm>
 
@@ -296,7 +306,7 @@ __global__ void __launch_bounds__(kBlock) window_ends_kernel(ScanBounds b, int64
 }
 
 // ---- frames with offsets ----------------------------------------------------------------------------------------------------------------------
-enum { kErrNullStart = 1, kErrNullEnd = 2, kErrNegative = 4 };      // error word 2
+enum { kErrNullStart = 1, kErrNullEnd = 2, kErrNegative = 4, kErrNullCompare = 8 };      // error word 2
 enum { kErrNthOffset = 1, kErrBuckets = 2 };                        // error word 3
 
 struct FrameArgs {
@@ -383,6 +393,78 @@ __global__ void __launch_bounds__(kBlock) window_frame_bounds_kernel(FrameArgs f
         if (!empty && (s < ps || e > pe || s > e)) empty = true;
         f.frame_start[i] = empty ? -1 : (int)s;
         f.frame_end[i] = empty ? -1 : (int)e;
+    }
+}
+
+// ---- RANGE frames with PRECEDING / FOLLOWING bounds ------------------------------------------------------------------------------------------------
+// the order code of a non-null BIGINT / INTEGER / DATE / DOUBLE cell in the direction of the sort: never decreasing along the sorted order
+__device__ __forceinline__ unsigned long long range_code(const TgColView &c, long long r, int descending)
+{
+    const unsigned long long v = cell_order_bits(c, r);
+    return descending ? ~v : v;
+}
+
+// codes[i] / key_null[i] of one comparison key channel `compare` (in arrival order, like `sort_key`), see the head of this file
+__global__ void __launch_bounds__(kBlock) window_range_keys_kernel(TgColView sort_key, TgColView compare, int descending, const int32_t *__restrict__ positions, int64_t n,
+                                                                   unsigned long long *__restrict__ codes, unsigned char *__restrict__ key_null,
+                                                                   unsigned int *__restrict__ errors)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const long long r = positions ? positions[i] : i;
+        const bool null_key = sort_key.nulls && sort_key.nulls[r];
+        const bool null_compare = compare.nulls && compare.nulls[r];
+        if (!null_key && null_compare) atomicOr(&errors[2], (unsigned int)kErrNullCompare);
+        codes[i] = null_key || null_compare ? 0ULL : range_code(compare, r, descending);
+        key_null[i] = null_key ? 1 : 0;
+    }
+}
+
+struct RangeFrameArgs {
+    int start_type, end_type, descending, nulls_first;
+    TgColView start_bound, end_bound;                   // the bound VALUES in arrival order; read for PRECEDING / FOLLOWING in rows with a non-null sort key
+    const unsigned long long *start_codes, *end_codes;  // [n] the comparison keys of the two bounds in sorted order
+    const unsigned char *key_null;                      // [n]
+    const int32_t *positions;
+    const int32_t *part_start, *peer_start, *part_end, *peer_end;
+    int32_t *frame_start, *frame_end;                   // as FrameArgs
+    unsigned int *errors;
+};
+
+__global__ void __launch_bounds__(kBlock) window_range_bounds_kernel(RangeFrameArgs f, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        // every index is held to [0, n - 1], the partition to [ps, pe] around i and the peer group inside it, before anything is read through them
+        int64_t ps = f.part_start[i];
+        ps = ps < 0 ? 0 : (ps > i ? i : ps);
+        int64_t pe = f.part_end[i];
+        pe = pe < i ? i : (pe > n - 1 ? n - 1 : pe);
+        int64_t peer_s = f.peer_start[i], peer_e = f.peer_end[i];
+        peer_s = peer_s < ps ? ps : (peer_s > i ? i : peer_s);
+        peer_e = peer_e < i ? i : (peer_e > pe ? pe : peer_e);
+        const int row_null = f.key_null[i];
+        long long lo = ps, hi = pe;
+        unsigned long long start_bound = 0, end_bound = 0;
+        unsigned int bad = 0;
+        if (!row_null) {
+            int64_t first_peer_e = f.peer_end[ps], last_peer_s = f.peer_start[pe];
+            first_peer_e = first_peer_e < ps ? ps : (first_peer_e > pe ? pe : first_peer_e);
+            last_peer_s = last_peer_s < ps ? ps : (last_peer_s > pe ? pe : last_peer_s);
+            tg_range_run(f.nulls_first, ps, pe, f.key_null[ps], first_peer_e, f.key_null[pe], last_peer_s, &lo, &hi);
+            const long long row = f.positions ? f.positions[i] : i;
+            if (bound_has_offset(f.start_type)) {
+                if (f.start_bound.nulls && f.start_bound.nulls[row]) bad |= kErrNullStart;
+                else start_bound = range_code(f.start_bound, row, f.descending);
+            }
+            if (bound_has_offset(f.end_type)) {
+                if (f.end_bound.nulls && f.end_bound.nulls[row]) bad |= kErrNullEnd;
+                else end_bound = range_code(f.end_bound, row, f.descending);
+            }
+        }
+        long long s = -1, e = -1;
+        if (bad) atomicOr(&f.errors[2], bad);
+        else tg_range_frame(f.start_type, f.end_type, i, ps, pe, peer_s, peer_e, row_null, lo, hi, f.start_codes, start_bound, f.end_codes, end_bound, &s, &e);
+        f.frame_start[i] = (int)s;
+        f.frame_end[i] = (int)e;
     }
 }
 
@@ -648,6 +730,11 @@ bool is_value_function(int32_t f)
 // the functions that read their frame
 bool reads_frame(int32_t f) { return f == TGPU_WINDOW_AGGREGATE || f == TGPU_WINDOW_FIRST_VALUE || f == TGPU_WINDOW_LAST_VALUE || f == TGPU_WINDOW_NTH_VALUE; }
 bool has_offset(int32_t bound) { return bound == TGPU_BOUND_PRECEDING || bound == TGPU_BOUND_FOLLOWING; }
+// a RANGE frame whose bounds are values to search for
+bool range_offsets(const WindowFunctionSpec &f)
+{
+    return f.general && f.ranged && f.frame_type == TGPU_FRAME_TYPE_RANGE && (has_offset(f.start_type) || has_offset(f.end_type));
+}
 
 // the tgpu_window_frame code of a general frame that is one of the three old frames, or -1
 int old_frame_code(const WindowFunctionSpec &f)
@@ -688,14 +775,25 @@ void WindowGpu::validate(const std::vector<int32_t> &types, const std::vector<Wi
                                      !(f.start_type == TGPU_BOUND_CURRENT_ROW && f.end_type == TGPU_BOUND_PRECEDING) &&
                                      !(f.start_type == TGPU_BOUND_FOLLOWING && f.end_type != TGPU_BOUND_FOLLOWING && f.end_type != TGPU_BOUND_UNBOUNDED_FOLLOWING);
             TG_CHECK_ARG(combination, "invalid window frame bounds");
+            const bool by_value = f.ranged && f.frame_type == TGPU_FRAME_TYPE_RANGE && (has_offset(f.start_type) || has_offset(f.end_type));
+            if (by_value) TG_CHECK_ARG(sort_channels.size() == 1, "a RANGE frame with an offset needs exactly one sort channel");
             for (int side = 0; side < 2; side++) {
                 if (!has_offset(side == 0 ? f.start_type : f.end_type)) continue;
                 const int32_t ch = side == 0 ? f.start_channel : f.end_channel;
+                if (by_value) {   // the bound's value and the comparison key (FrameInfo.sortKeyChannelForStart/EndComparison)
+                    const int32_t key = side == 0 ? f.start_sort_key_channel : f.end_sort_key_channel;
+                    TG_CHECK_ARG(ch >= 0 && ch < nt, "frame bound channel out of range");
+                    TG_CHECK_ARG(key >= 0 && key < nt, "frame comparison key channel out of range");
+                    const int32_t t = types[(size_t)ch];
+                    TG_CHECK_ARG(t == types[(size_t)key], "a frame bound and its comparison key differ in type");
+                    TG_CHECK_ARG(t == TGPU_BIGINT || t == TGPU_INTEGER || t == TGPU_DATE || t == TGPU_DOUBLE, "a RANGE frame bound must be BIGINT, INTEGER, DATE or DOUBLE");
+                    continue;
+                }
                 TG_CHECK_ARG(ch >= 0 && ch < nt, "frame offset channel out of range");
                 TG_CHECK_ARG(types[(size_t)ch] == TGPU_BIGINT || types[(size_t)ch] == TGPU_INTEGER, "a frame offset must be BIGINT or INTEGER");
             }
             // the reference compares the sort key with computed bound channels there: a value search, not a count of rows
-            if (f.frame_type == TGPU_FRAME_TYPE_RANGE && (has_offset(f.start_type) || has_offset(f.end_type)))
+            if (!f.ranged && f.frame_type == TGPU_FRAME_TYPE_RANGE && (has_offset(f.start_type) || has_offset(f.end_type)))
                 fail(TGPU_ERR_NOT_SUPPORTED, "RANGE frames with an offset are not supported");
         }
         if (f.ignore_nulls != 0) fail(TGPU_ERR_NOT_SUPPORTED, "IGNORE NULLS is not supported");
@@ -850,6 +948,8 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
     std::vector<BufferPtr> frame_bufs(functions_.size());   // [2][n]: frame_start, frame_end; shared by the functions of one frame
     std::vector<BufferPtr> index_bufs(functions_.size());   // [3][n] pre, suf, mask, then [levels][chunks]
     const int64_t chunks = ceil_div(n, 64);
+    BufferPtr range_null;                                          // [n] the sort key of the row at a sorted position is null
+    std::vector<std::pair<int32_t, BufferPtr>> range_codes;        // comparison key channel -> [n] its codes in sorted order
     if (any_general) {
         {
             ProfileScope ps(ctx_, "window_frames");
@@ -862,11 +962,54 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
                     const WindowFunctionSpec &other = functions_[o];
                     const bool same = other.general && other.frame_type == spec.frame_type && other.start_type == spec.start_type && other.end_type == spec.end_type &&
                                       (!has_offset(spec.start_type) || other.start_channel == spec.start_channel) &&
-                                      (!has_offset(spec.end_type) || other.end_channel == spec.end_channel);
+                                      (!has_offset(spec.end_type) || other.end_channel == spec.end_channel) &&
+                                      (!range_offsets(spec) || (range_offsets(other) && (!has_offset(spec.start_type) || other.start_sort_key_channel == spec.start_sort_key_channel) &&
+                                                                (!has_offset(spec.end_type) || other.end_sort_key_channel == spec.end_sort_key_channel)));
                     if (same) frame_bufs[f] = frame_bufs[o];
                 }
                 if (frame_bufs[f]) continue;
                 frame_bufs[f] = scratch((size_t)n * 2 * 4);
+                if (range_offsets(spec)) {
+                    const bool descending = sort_orders_[0] == TGPU_SORT_DESC_NULLS_FIRST || sort_orders_[0] == TGPU_SORT_DESC_NULLS_LAST;
+                    const DeviceColumn &sort_key = all.cols[(size_t)sort_channels_[0]];
+                    if (!range_null) range_null = scratch((size_t)n);
+                    // the comparison key of a bound in sorted order: gathered once per distinct channel
+                    auto codes_of = [&](int32_t channel) {
+                        for (const auto &made : range_codes)
+                            if (made.first == channel) return made.second->as<unsigned long long>();
+                        BufferPtr codes = scratch((size_t)n * 8);
+                        window_range_keys_kernel<<<g, kBlock, 0, ctx_->stream()>>>(view_of(sort_key), view_of(all.cols[(size_t)channel]), descending ? 1 : 0, pos, n,
+                                                                                   codes->as<unsigned long long>(), range_null->as<unsigned char>(), errors->as<unsigned int>());
+                        check_launch("window_range_keys");
+                        range_codes.emplace_back(channel, codes);
+                        return codes->as<unsigned long long>();
+                    };
+                    RangeFrameArgs ra{};
+                    ra.start_type = spec.start_type;
+                    ra.end_type = spec.end_type;
+                    ra.descending = descending ? 1 : 0;
+                    ra.nulls_first = sort_orders_[0] == TGPU_SORT_ASC_NULLS_FIRST || sort_orders_[0] == TGPU_SORT_DESC_NULLS_FIRST;
+                    if (has_offset(spec.start_type)) {
+                        ra.start_bound = view_of(all.cols[(size_t)spec.start_channel]);
+                        ra.start_codes = codes_of(spec.start_sort_key_channel);
+                    }
+                    if (has_offset(spec.end_type)) {
+                        ra.end_bound = view_of(all.cols[(size_t)spec.end_channel]);
+                        ra.end_codes = codes_of(spec.end_sort_key_channel);
+                    }
+                    ra.key_null = range_null->as<unsigned char>();
+                    ra.positions = pos;
+                    ra.part_start = bounds.part_start;
+                    ra.peer_start = bounds.peer_start;
+                    ra.part_end = part_end;
+                    ra.peer_end = peer_end;
+                    ra.frame_start = frame_bufs[f]->as<int32_t>();
+                    ra.frame_end = ra.frame_start + n;
+                    ra.errors = errors->as<unsigned int>();
+                    window_range_bounds_kernel<<<g, kBlock, 0, ctx_->stream()>>>(ra, n);
+                    check_launch("window_range_bounds");
+                    continue;
+                }
                 FrameArgs fa{};
                 fa.type = spec.frame_type;
                 fa.start_type = spec.start_type;
@@ -977,6 +1120,7 @@ std::vector<DeviceColumn> WindowGpu::evaluate(const DevicePage &all, BufferPtr *
     if (err[2] & kErrNullStart) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame starting offset must not be null");   // getFrameValue, WindowPartition.java:601-607
     if (err[2] & kErrNullEnd) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame ending offset must not be null");
     if (err[2] & kErrNegative) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame offset must not be negative");
+    if (err[2] & kErrNullCompare) fail(TGPU_ERR_INVALID_ARGUMENT, "Window frame comparison key must not be null where the sort key is not null");
     if (err[3] & kErrNthOffset) fail(TGPU_ERR_INVALID_ARGUMENT, "Offset must be at least 1");                       // NthValueFunction.java:49
     if (err[3] & kErrBuckets) fail(TGPU_ERR_INVALID_ARGUMENT, "Buckets must be greater than 0");                   // NTileFunction.java:52
     if (err[0]) fail(TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "bigint addition overflow");   // BigintOperators.add under LongSumAggregation

@@ -11,6 +11,7 @@ import json
 import numpy as np
 
 from . import _lib
+from . import expressions as _expr
 from .expressions import FlatProgram
 from .spi import OutputPage, Page
 
@@ -870,6 +871,36 @@ class WindowFrame:
         return _lib.WindowFrameSpec(self.type, self.start_type, self.start_channel, self.end_type, self.end_channel)
 
 
+class WindowRangeFrame(WindowFrame):
+    """A RANGE frame whose PRECEDING / FOLLOWING bounds are values (tgpu_window_range_frame_spec; tgpu_window_factory_create_ranged): `start_channel` /
+    `end_channel` = the source channel of the bound's VALUE per row (sort key -/+ offset, see window_range_bound), `start_sort_key_channel` /
+    `end_sort_key_channel` = the sort key coerced to that bound's type (FrameInfo.sortKeyChannelForStart/EndComparison)."""
+
+    def __init__(self, start_type, end_type, start_channel=-1, end_channel=-1, start_sort_key_channel=-1, end_sort_key_channel=-1):
+        super().__init__(FRAME_TYPE_RANGE, start_type, end_type, start_channel, end_channel)
+        self.start_sort_key_channel, self.end_sort_key_channel = int(start_sort_key_channel), int(end_sort_key_channel)
+
+    def range_spec(self):
+        return _lib.WindowRangeFrameSpec(self.type, self.start_type, self.start_channel, self.end_type, self.end_channel, self.start_sort_key_channel,
+                                         self.end_sort_key_channel)
+
+
+def window_range_bound(key, offset, bound_type, sort_order, unit=None):
+    """The RowExpression a planner projects in front of the window for a RANGE bound (QueryPlanner.planFrameBound): key - offset for ASC PRECEDING and
+    DESC FOLLOWING, key + offset for the other two, checked arithmetic in the key's type.  `key` = the sort key (coerced to the offset's type),
+    `offset` = an expression of that type or a Python number; on a DATE key, `unit` names the interval and `offset` is its BIGINT count:
+    date_add(unit, -/+ offset, key)."""
+    if bound_type not in (BOUND_PRECEDING, BOUND_FOLLOWING):
+        raise ValueError("only PRECEDING and FOLLOWING bounds have a value")
+    ascending = sort_order in (ASC_NULLS_FIRST, ASC_NULLS_LAST)
+    subtract = (bound_type == BOUND_PRECEDING) == ascending
+    if unit is not None:
+        if isinstance(offset, _expr.RowExpression):
+            return _expr.date_add(unit, -offset if subtract else offset, key)
+        return _expr.date_add(unit, -int(offset) if subtract else int(offset), key)
+    return key - offset if subtract else key + offset
+
+
 # the three frames of tgpu_window_factory_create as the framed entry point takes them
 _OLD_FRAMES = {FRAME_PARTITION: (FRAME_TYPE_RANGE, BOUND_UNBOUNDED_PRECEDING, BOUND_UNBOUNDED_FOLLOWING),
                FRAME_RANGE_TO_CURRENT: (FRAME_TYPE_RANGE, BOUND_UNBOUNDED_PRECEDING, BOUND_CURRENT_ROW),
@@ -907,6 +938,12 @@ class WindowFunction:
         t, s, e = _OLD_FRAMES[self.frame]
         return _lib.WindowFrameSpec(t, s, -1, e, -1)
 
+    def range_frame_spec(self):
+        if isinstance(self.frame, WindowRangeFrame):
+            return self.frame.range_spec()
+        w = self.frame_spec()
+        return _lib.WindowRangeFrameSpec(w.type, w.start_type, w.start_channel, w.end_type, w.end_channel, -1, -1)
+
 
 class WindowOperatorFactory(OperatorFactory):
     """WindowOperator.WindowOperatorFactory (M/operator/WindowOperator.java:71-203): `functions` OVER (PARTITION BY `partition_channels` ORDER BY
@@ -925,7 +962,11 @@ class WindowOperatorFactory(OperatorFactory):
         so, _ = _i32(sort_orders)
         specs = (_lib.WindowFunctionSpec * max(1, len(functions)))(*[f.spec() for f in functions])
         h = C.c_void_p()
-        if any(f.framed() for f in functions):
+        if any(isinstance(f.frame, WindowRangeFrame) for f in functions):
+            frames = (_lib.WindowRangeFrameSpec * max(1, len(functions)))(*[f.range_frame_spec() for f in functions])
+            _lib.check(_lib.lib().tgpu_window_factory_create_ranged(ctx.handle, operator_id, nt, t, no, o, len(functions), specs, frames, np_, p, ns, sc, so,
+                                                                    int(expected_positions), C.byref(h)))
+        elif any(f.framed() for f in functions):
             frames = (_lib.WindowFrameSpec * max(1, len(functions)))(*[f.frame_spec() for f in functions])
             _lib.check(_lib.lib().tgpu_window_factory_create_framed(ctx.handle, operator_id, nt, t, no, o, len(functions), specs, frames, np_, p, ns, sc, so,
                                                                     int(expected_positions), C.byref(h)))
