@@ -23,6 +23,7 @@
  *   - tgpu_lookup_outer_*        <-> M/operator/LookupOuterOperator.java:32-235, OuterLookupSource.java:146-190
  *   - tgpu_merge_pages_*         <-> M/operator/project/MergePages.java:64-190
  *   - tgpu_dynamic_filter_source_* <-> M/operator/DynamicFilterSourceOperator.java:74-425
+ *   - tgpu_nested_loop_* / tgpu_filter_project_nested_loop_join_* <-> M/operator/NestedLoopBuildOperator.java, NestedLoopJoinPagesBuilder.java, NestedLoopJoinOperator.java
  *   - tgpu_set_builder_* / tgpu_hash_semi_join_* <-> M/operator/SetBuilderOperator.java:39-233, HashSemiJoinOperator.java:44-218, ChannelSet.java:62-108
  *   - tgpu_mark_distinct_* / tgpu_distinct_limit_* <-> M/operator/MarkDistinctOperator.java:37-203, MarkDistinctHash.java:31-87, DistinctLimitOperator.java:40-263
  *   - tgpu_row_number_* / tgpu_limit_* <-> M/operator/RowNumberOperator.java:43-364, LimitOperator.java:25-120
@@ -112,6 +113,7 @@ typedef struct tgpu_operator_factory tgpu_operator_factory;
 typedef struct tgpu_operator tgpu_operator;
 typedef struct tgpu_lookup_source_factory tgpu_lookup_source_factory;
 typedef struct tgpu_set_supplier tgpu_set_supplier;            /* SetBuilderOperator.SetSupplier */
+typedef struct tgpu_nested_loop_bridge tgpu_nested_loop_bridge; /* NestedLoopJoinBridge / NestedLoopJoinPagesSupplier */
 typedef struct tgpu_group_by_hash tgpu_group_by_hash;
 typedef struct tgpu_output_page tgpu_output_page;
 
@@ -456,6 +458,53 @@ int32_t tgpu_hash_semi_join_factory_create(tgpu_context *ctx, int32_t operator_i
  * 1 hash, 2 generic) */
 int32_t tgpu_set_supplier_stats(tgpu_set_supplier *supplier, int64_t *size, int32_t *contains_null, int64_t *bytes, int32_t *layout);
 void tgpu_set_supplier_destroy(tgpu_set_supplier *supplier);
+
+/* ---- nested loop join (LocalExecutionPlanner.visitJoin for a node without equi-criteria: cross join, scalar subquery comparison, band and
+ * inequality joins; M/operator/NestedLoopBuildOperator.java, NestedLoopJoinPagesBuilder.java, NestedLoopJoinOperator.java).  INNER only,
+ * as in the reference.
+ *
+ * The sequence every operator below produces: one probe page (p rows) against each build page (b rows) in turn, in build order.  The
+ * LARGE side of such a pair is the build page iff b > p (a tie makes the probe page large; with an empty probe channel list and a non-empty
+ * build channel list a tie makes the build page large, NestedLoopJoinOperator.java:265-267).  The reference emits one page per row of the
+ * small side, in row order, each holding every row of the large side in order with the small row repeated; channels = probe_channels then
+ * build_channels.  The device operators produce THE ROWS OF THOSE PAGES IN THAT ORDER and cut the sequence into output pages of their
+ * own size.  Without any output channel only position counts come out and only their sum is defined. ---- */
+/* NestedLoopBuildOperatorFactory (NestedLoopBuildOperator.java:33-94) + the bridge to the probes (NestedLoopJoinPagesSupplier).  A sink:
+ * get_output is always null.  The pages are kept in HBM as delivered -- page boundaries decide which side of a pair is large -- except
+ * that empty pages are dropped and, when type_count = 0, pages are only counted and re-cut into pages of 8192 positions plus a remainder
+ * (NestedLoopJoinPagesBuilder.java:64-76,100-105).  memory_bytes = the retained size.  finish() publishes the pages; a second build
+ * operator finishing on the same bridge fails with TGPU_ERR_INTERNAL "pagesFuture already set".  After finish() the operator is blocked,
+ * and not finished, until every probe operator of the bridge has closed and every probe factory has had no_more_operators (as the hash
+ * builder).  The factory cannot be duplicated (TGPU_ERR_NOT_SUPPORTED). */
+int32_t tgpu_nested_loop_build_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                              tgpu_nested_loop_bridge **bridge_out, tgpu_operator_factory **out);
+/* valid once the build operator finished: kept pages (after the re-cut), their positions, their bytes in HBM */
+int32_t tgpu_nested_loop_bridge_stats(tgpu_nested_loop_bridge *bridge, int64_t *pages, int64_t *positions, int64_t *bytes);
+void tgpu_nested_loop_bridge_destroy(tgpu_nested_loop_bridge *bridge);
+/* NestedLoopJoinOperatorFactory (NestedLoopJoinOperator.java:44-108).  is_blocked = 1 and needs_input = 0 until the build operator has
+ * finished; needs_input = 0 while a probe page still has output to give; an empty probe page, or an empty build side, produces nothing;
+ * finish() with output still to give keeps is_finished = 0 until it has been drained; close() at any time is clean; duplicate() shares the
+ * bridge.  Every get_output returns the next piece of the sequence: at most max_output_rows rows (0 = the default: 4,194,304 rows; 2^31 - 1
+ * when both channel lists are empty), and fewer where a VARCHAR channel's pool would otherwise reach 2^31 bytes.  A probe page's product may
+ * exceed 2^31 rows: it comes out piece by piece.  Channels may repeat and come in any order. */
+int32_t tgpu_nested_loop_join_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_nested_loop_bridge *bridge,
+                                             int32_t probe_type_count, const int32_t *probe_types,
+                                             int32_t probe_channel_count, const int32_t *probe_channels,
+                                             int32_t build_channel_count, const int32_t *build_channels,
+                                             int64_t max_output_rows /* 0 = default */, tgpu_operator_factory **out);
+/* NestedLoopJoin(all probe channels, all build channels) feeding FilterAndProjectOperator(spec), as one operator.  Input channel
+ * k < probe_type_count of `spec` is probe channel k, channel probe_type_count + j is build channel j: PROBE FIRST, the order of the join's
+ * output page -- NOT the build-first order of tgpu_lookup_source_factory_set_join_filter.  Output = the filtered and projected sequence.  At
+ * most max_product_rows pairs (0 = the default: 67,108,864) are evaluated per get_output; a step without survivors returns null and the
+ * operator goes on.  A filter over BIGINT / INTEGER / DATE / DOUBLE / BOOLEAN values that cannot raise is evaluated over the virtual
+ * product, only the surviving pairs are written; any other spec (no filter, a filter that can raise, VARCHAR in the filter) runs as product
+ * pieces of the channels it reads followed by the page processor -- same output.  The operator fails with the error the reference
+ * composition throws first: the first reference page that fails, within it the filter before projection 0 before projection 1 ..., then
+ * the first row (found by re-running the failing piece one reference page at a time). */
+int32_t tgpu_filter_project_nested_loop_join_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_nested_loop_bridge *bridge,
+                                                            int32_t probe_type_count, const int32_t *probe_types,
+                                                            const tgpu_page_processor_spec *spec,
+                                                            int64_t max_product_rows /* 0 = default */, tgpu_operator_factory **out);
 
 /* ---- count(DISTINCT x) and SELECT DISTINCT ... LIMIT n (LocalExecutionPlanner.visitMarkDistinct / visitDistinctLimit) ---- */
 /* MarkDistinctOperator.MarkDistinctOperatorFactory (M/operator/MarkDistinctOperator.java:39-92, :94-203; MarkDistinctHash.java:52-69): output

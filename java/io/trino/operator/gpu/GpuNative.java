@@ -115,6 +115,16 @@ public final class GpuNative
     /** out = {distinct keys (a null counted), containsNull 0 / 1, HBM bytes, layout} of the built set */
     public static native void setSupplierStats(long supplier, long[] sizeContainsNullBytesLayout);
     public static native void destroySetSupplier(long supplier);
+
+    /** returns {factory, bridge}: NestedLoopBuildOperatorFactory and its NestedLoopJoinPagesSupplier (tgpu_nested_loop_build_factory_create) */
+    public static native long[] createNestedLoopBuildFactory(long context, int operatorId, int[] types);
+    public static native long createNestedLoopJoinFactory(long context, int operatorId, long bridge, int[] probeTypes, int[] probeChannels, int[] buildChannels, long maxOutputRows);
+    /** NestedLoopJoin -> FilterAndProject as one operator; the program's channels are (probe channels..., build channels...) */
+    public static native long createFilterProjectNestedLoopJoinFactory(long context, int operatorId, long bridge, int[] probeTypes, int[][] nodes, long[] longValues,
+            double[] doubleValues, byte[] stringPool, int filterRoot, int[] projectionRoots, long maxProductRows);
+    /** out = {kept pages, positions, HBM bytes} */
+    public static native void nestedLoopBridgeStats(long bridge, long[] out);
+    public static native void destroyNestedLoopBridge(long bridge);
     /** MarkDistinctOperatorFactory (tgpu_mark_distinct_factory_create): the input page + one BOOLEAN channel; hashChannel -1 = none */
     public static native long createMarkDistinctFactory(long context, int operatorId, int[] types, int[] markDistinctChannels, int hashChannel);
     /** DistinctLimitOperatorFactory (tgpu_distinct_limit_factory_create): output = the distinct channels, then the hash channel if any */

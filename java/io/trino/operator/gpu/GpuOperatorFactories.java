@@ -353,6 +353,91 @@ public final class GpuOperatorFactories
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuHashSemiJoinOperator", probeTypes, poller, factory));
     }
 
+    /** the nested loop join's bridge handle (tgpu_nested_loop_bridge*) between the build operator and the probes (operator/NestedLoopJoinPagesSupplier.java) */
+    public static final class NestedLoopBuild
+    {
+        public final OperatorFactory factory;
+        public final long bridge;
+        final List<Type> buildTypes;
+
+        NestedLoopBuild(OperatorFactory factory, long bridge, List<Type> buildTypes)
+        {
+            this.factory = factory;
+            this.bridge = bridge;
+            this.buildTypes = buildTypes;
+        }
+
+        /** {kept pages (zero-channel pages re-cut to 8192 positions), positions, HBM bytes} of the published build side */
+        public long[] stats()
+        {
+            long[] out = new long[3];
+            GpuNative.nestedLoopBridgeStats(bridge, out);
+            return out;
+        }
+
+        public void destroy()
+        {
+            GpuNative.destroyNestedLoopBridge(bridge);
+        }
+    }
+
+    /**
+     * NestedLoopBuildOperatorFactory (operator/NestedLoopBuildOperator.java:33-94; LocalExecutionPlanner.visitJoin for a JoinNode without equi-criteria).
+     * An empty type list is a build side without channels: its pages are only counted.
+     */
+    public Optional<NestedLoopBuild> nestedLoopBuild(int operatorId, PlanNodeId planNodeId, List<Type> types)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(types);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long[] handles = GpuNative.createNestedLoopBuildFactory(context, operatorId, codes);
+        return Optional.of(new NestedLoopBuild(new GpuNestedLoopBuildOperatorFactory(operatorId, planNodeId, types, poller, handles[0]), handles[1], types));
+    }
+
+    /** NestedLoopJoinOperator.NestedLoopJoinOperatorFactory (operator/NestedLoopJoinOperator.java:44-108): probeChannels then buildChannels; maxOutputRows 0 = the default */
+    public Optional<OperatorFactory> nestedLoopJoin(int operatorId, PlanNodeId planNodeId, NestedLoopBuild build, List<Type> probeTypes, List<Integer> probeChannels,
+            List<Integer> buildChannels, long maxOutputRows)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(probeTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createNestedLoopJoinFactory(context, operatorId, build.bridge, codes, ints(probeChannels), ints(buildChannels), maxOutputRows);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuNestedLoopJoinOperator", probeTypes, poller, factory));
+    }
+
+    /**
+     * The FilterNode / ProjectNode above a JoinNode without equi-criteria fused into the join (tgpu_filter_project_nested_loop_join_factory_create): the
+     * expressions address the join's output page, probe channels first, then the build channels.
+     */
+    public Optional<OperatorFactory> filterProjectNestedLoopJoin(int operatorId, PlanNodeId planNodeId, NestedLoopBuild build, List<Type> probeTypes,
+            Optional<RowExpression> filter, List<RowExpression> projections, long maxProductRows)
+    {
+        int[] codes;
+        Optional<GpuRowExpressions.Program> program;
+        try {
+            codes = GpuPages.typeCodes(probeTypes);
+            program = GpuRowExpressions.serialize(filter, projections);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        if (program.isEmpty()) {
+            return Optional.empty();
+        }
+        GpuRowExpressions.Program p = program.get();
+        long factory = GpuNative.createFilterProjectNestedLoopJoinFactory(context, operatorId, build.bridge, codes, p.nodeArray(), p.longArray(), p.doubleArray(),
+                p.stringPool.toByteArray(), p.filterRoot, p.projectionRoots, maxProductRows);
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuFilterProjectNestedLoopJoinOperator", probeTypes, poller, factory));
+    }
+
     /**
      * MarkDistinctOperator.MarkDistinctOperatorFactory (operator/MarkDistinctOperator.java:51-71; LocalExecutionPlanner.visitMarkDistinct): the source page plus one
      * BOOLEAN channel that is true on the first row of every value of the mark channels; the aggregation reads it as its mask channel.

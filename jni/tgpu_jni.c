@@ -587,6 +587,60 @@ JFN(void, setSupplierStats)(JNIEnv *env, jclass c, jlong supplier, jlongArray ou
 
 JFN(void, destroySetSupplier)(JNIEnv *env, jclass c, jlong supplier) { UNUSED(env); UNUSED(c); tgpu_set_supplier_destroy(H(tgpu_set_supplier, supplier)); }
 
+/* NestedLoopBuildOperatorFactory + its bridge (operator/NestedLoopBuildOperator.java:33-94, NestedLoopJoinPagesSupplier.java): returns
+ * {factory, bridge}.  An empty type array is a build side without channels (its pages are only counted). */
+JFN(jlongArray, createNestedLoopBuildFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types);
+    tgpu_nested_loop_bridge *bridge = NULL;
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = tgpu_nested_loop_build_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, &bridge, &f);
+    ints_release(env, &t);
+    return two_handles(env, rc, f, bridge);
+}
+
+/* NestedLoopJoinOperatorFactory (operator/NestedLoopJoinOperator.java:44-108): probeChannels then buildChannels, the reference's row order */
+JFN(jlong, createNestedLoopJoinFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jlong bridge, jintArray probeTypes, jintArray probeChannels, jintArray buildChannels,
+                                        jlong maxOutputRows)
+{
+    UNUSED(c);
+    ints t = ints_get(env, probeTypes), pc = ints_get(env, probeChannels), bc = ints_get(env, buildChannels);
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = tgpu_nested_loop_join_factory_create(H(tgpu_context, ctx), operatorId, H(tgpu_nested_loop_bridge, bridge), t.n, (const int32_t *)t.p, pc.n, (const int32_t *)pc.p,
+                                                      bc.n, (const int32_t *)bc.p, maxOutputRows, &f);
+    ints_release(env, &bc); ints_release(env, &pc); ints_release(env, &t);
+    return factory_result(env, rc, f);
+}
+
+/* NestedLoopJoin -> FilterAndProject as one operator: the program's channels are (probe channels..., build channels...) */
+JFN(jlong, createFilterProjectNestedLoopJoinFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jlong bridge, jintArray probeTypes, PROGRAM_PARAMS, jlong maxProductRows)
+{
+    UNUSED(c);
+    program pr;
+    if (!program_read(env, &pr, PROGRAM_ARGS)) return 0;
+    ints t = ints_get(env, probeTypes);
+    tgpu_operator_factory *f = NULL;
+    int32_t rc = tgpu_filter_project_nested_loop_join_factory_create(H(tgpu_context, ctx), operatorId, H(tgpu_nested_loop_bridge, bridge), t.n, (const int32_t *)t.p, &pr.spec,
+                                                                     maxProductRows, &f);
+    ints_release(env, &t);
+    program_release(env, &pr);
+    return factory_result(env, rc, f);
+}
+
+/* out = {kept pages, positions, HBM bytes} of the published build side */
+JFN(void, nestedLoopBridgeStats)(JNIEnv *env, jclass c, jlong bridge, jlongArray out)
+{
+    UNUSED(c);
+    int64_t pages = 0, positions = 0, bytes = 0;
+    int32_t rc = tgpu_nested_loop_bridge_stats(H(tgpu_nested_loop_bridge, bridge), &pages, &positions, &bytes);
+    if (rc < 0) { throw_native(env, rc); return; }
+    jlong v[3] = {pages, positions, bytes};
+    set_longs(env, out, v, 3);
+}
+
+JFN(void, destroyNestedLoopBridge)(JNIEnv *env, jclass c, jlong bridge) { UNUSED(env); UNUSED(c); tgpu_nested_loop_bridge_destroy(H(tgpu_nested_loop_bridge, bridge)); }
+
 /* the key channels of the two distinct operators, checked in front of the library: a non-empty type array, a non-empty channel list,
  * every channel in [0, types), hashChannel -1 or a BIGINT channel.  Returns NULL, or the message to throw once the arrays are released */
 static const char *distinct_channels_error(const ints *t, const ints *ch, jint hashChannel)

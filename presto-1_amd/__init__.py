@@ -11,6 +11,8 @@ from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_
                         Context, FilterAndProjectOperatorFactory, ScanFilterAndProjectOperatorFactory, PageSource, RecordCursor, FilterProjectHashAggregationOperatorFactory, FilterProjectLookupJoinOperatorFactory, GroupByHash, HashAggregationOperatorFactory, HashBuilderOperatorFactory,
                         LookupJoinOperatorFactory, LookupOuterOperatorFactory, Operator, OperatorFactory, page_processor_source, fused_probe_launch_counts, fused_probe_depth_counts, precompile_fused_aggregation, precompile_fused_probe, precompile_page_processor, to_pages,
                         SET_BITMAP, SET_GENERIC, SET_HASH, HashSemiJoinOperatorFactory, SetBuilderOperatorFactory, SetSupplier,
+                        NestedLoopBridge, NestedLoopBuildOperatorFactory, NestedLoopJoinOperatorFactory, FilterProjectNestedLoopJoinOperatorFactory,
+                        precompile_nested_loop_filter, nested_loop_filter_source,
                         DistinctLimitOperatorFactory, MarkDistinctOperatorFactory,
                         LimitOperatorFactory, RowNumberOperatorFactory,
                         DENSE_RANK, RANK, ROW_NUMBER, TopNRankingOperatorFactory,

@@ -192,6 +192,11 @@ SYMBOLS = {
     "tgpu_hash_semi_join_factory_create": (i32, [vp, i32, vp, i32, P(i32), i32, i32, P(vp)]),
     "tgpu_set_supplier_stats": (i32, [vp, P(i64), P(i32), P(i64), P(i32)]),
     "tgpu_set_supplier_destroy": (None, [vp]),
+    "tgpu_nested_loop_build_factory_create": (i32, [vp, i32, i32, P(i32), P(vp), P(vp)]),
+    "tgpu_nested_loop_bridge_stats": (i32, [vp, P(i64), P(i64), P(i64)]),
+    "tgpu_nested_loop_bridge_destroy": (None, [vp]),
+    "tgpu_nested_loop_join_factory_create": (i32, [vp, i32, vp, i32, P(i32), i32, P(i32), i32, P(i32), i64, P(vp)]),
+    "tgpu_filter_project_nested_loop_join_factory_create": (i32, [vp, i32, vp, i32, P(i32), P(PageProcessorSpec), i64, P(vp)]),
     "tgpu_mark_distinct_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(vp)]),
     "tgpu_distinct_limit_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i64, i32, P(vp)]),
     "tgpu_top_n_ranking_factory_create": (i32, [vp, i32, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, P(i32), P(i32), i64, i32, i32, i32, P(vp)]),
@@ -224,6 +229,8 @@ EXTRA_SYMBOLS = {
     "tgpu_group_by_hash_rehash_count": (i32, [vp]),
     "tgpu_debug_bind_count": (C.c_longlong, []),
     "tgpu_debug_dictionary_pages": (i64, [vp]),
+    "tgpu_precompile_nested_loop_filter": (i32, [i32, P(i32), i32, P(i32), P(PageProcessorSpec)]),
+    "tgpu_nested_loop_filter_source": (i64, [i32, P(i32), i32, P(i32), P(PageProcessorSpec), cp, i64]),
     "tgpu_precompile_fused_probe": (i32, [i32, P(i32), P(PageProcessorSpec), i32, i32, P(i32)]),
     "tgpu_precompile_fused_aggregation": (i32, [i32, P(i32), P(PageProcessorSpec), i32, P(AggSpec), i32, P(i32)]),
 }

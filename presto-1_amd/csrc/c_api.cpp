@@ -62,6 +62,7 @@ inline Context *ctx_of(const tgpu_operator_factory *h) { return h ? h->ctx : nul
 inline Context *ctx_of(const tgpu_lookup_source_factory *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_group_by_hash *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_set_supplier *h) { return h ? h->ctx : nullptr; }
+inline Context *ctx_of(const tgpu_nested_loop_bridge *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_output_page *h) { return h ? h->ctx : nullptr; }
 inline Context *ctx_of(const tgpu_exchange *h) { return h ? h->ctx : nullptr; }
 
@@ -1217,6 +1218,109 @@ void tgpu_set_supplier_destroy(tgpu_set_supplier *supplier)
     Context *c = supplier->ctx;
     delete supplier;
     if (c) drop(c);
+}
+
+int32_t tgpu_nested_loop_build_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, tgpu_nested_loop_bridge **bridge_out,
+                                              tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && bridge_out && out, "null argument");
+        auto bridge = std::make_unique<tgpu_nested_loop_bridge>();
+        bridge->bridge = std::make_shared<NestedLoopBridge>(vec(types, type_count));
+        make_factory<NestedLoopBuildOperatorFactory>(ctx, out, operator_id, bridge->bridge);
+        bridge->ctx = ctx->ctx.get();
+        retain(bridge->ctx);
+        *bridge_out = bridge.release();
+    });
+}
+
+int32_t tgpu_nested_loop_bridge_stats(tgpu_nested_loop_bridge *bridge, int64_t *pages, int64_t *positions, int64_t *bytes)
+{
+    return guard_on(ctx_of(bridge), [&] {
+        TG_CHECK_ARG(bridge != nullptr, "bridge is null");
+        std::shared_ptr<const NestedLoopPages> p = bridge->bridge->pages();
+        TG_CHECK_STATE(p != nullptr, "Page source has not been built yet");
+        if (pages) *pages = (int64_t)p->pages.size();
+        if (positions) *positions = p->positions;
+        if (bytes) *bytes = p->bytes;
+    });
+}
+
+void tgpu_nested_loop_bridge_destroy(tgpu_nested_loop_bridge *bridge)
+{
+    if (!bridge) return;
+    Context *c = bridge->ctx;
+    delete bridge;
+    if (c) drop(c);
+}
+
+int32_t tgpu_nested_loop_join_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_nested_loop_bridge *bridge, int32_t probe_type_count, const int32_t *probe_types,
+                                             int32_t probe_channel_count, const int32_t *probe_channels, int32_t build_channel_count, const int32_t *build_channels,
+                                             int64_t max_output_rows, tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && bridge && out, "null argument");
+        NestedLoopJoinConfig cfg;
+        cfg.probe_types = vec(probe_types, probe_type_count);
+        cfg.probe_channels = vec(probe_channels, probe_channel_count);
+        cfg.build_channels = vec(build_channels, build_channel_count);
+        cfg.max_rows = max_output_rows;
+        make_factory<NestedLoopJoinOperatorFactory>(ctx, out, operator_id, std::move(cfg), bridge->bridge);
+    });
+}
+
+static NestedLoopJoinConfig nested_loop_filter_config(int32_t probe_type_count, const int32_t *probe_types, const tgpu_page_processor_spec *spec, int64_t max_product_rows)
+{
+    TG_CHECK_ARG(spec != nullptr, "page processor spec is null");
+    TG_CHECK_ARG(spec->node_count >= 0 && (spec->node_count == 0 || spec->nodes != nullptr), "bad node array");
+    TG_CHECK_ARG(spec->projection_count >= 0 && (spec->projection_count == 0 || spec->projection_roots != nullptr), "bad projection count");
+    NestedLoopJoinConfig cfg;
+    cfg.probe_types = vec(probe_types, probe_type_count);
+    cfg.max_rows = max_product_rows;
+    cfg.fused = true;
+    cfg.nodes.assign(spec->nodes, spec->nodes + spec->node_count);
+    if (spec->string_pool && spec->string_pool_len > 0) cfg.pool.assign(spec->string_pool, spec->string_pool + spec->string_pool_len);
+    cfg.filter_root = spec->filter_root;
+    cfg.projection_roots.assign(spec->projection_roots, spec->projection_roots + spec->projection_count);
+    return cfg;
+}
+
+int32_t tgpu_filter_project_nested_loop_join_factory_create(tgpu_context *ctx, int32_t operator_id, tgpu_nested_loop_bridge *bridge, int32_t probe_type_count,
+                                                            const int32_t *probe_types, const tgpu_page_processor_spec *spec, int64_t max_product_rows,
+                                                            tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && bridge && out, "null argument");
+        make_factory<NestedLoopJoinOperatorFactory>(ctx, out, operator_id, nested_loop_filter_config(probe_type_count, probe_types, spec, max_product_rows), bridge->bridge);
+    });
+}
+
+// compile-only entries (no GPU needed), not part of include/tgpu.h: the pair filter's two kernel variants into the on-disk cache, and the
+// generated source.  A filter the generator does not fuse gives TGPU_ERR_NOT_SUPPORTED with the reason as the message.
+static std::shared_ptr<NestedLoopFilterGpu> nested_loop_filter(int32_t probe_type_count, const int32_t *probe_types, int32_t build_type_count, const int32_t *build_types,
+                                                                const tgpu_page_processor_spec *spec)
+{
+    auto f = std::make_shared<NestedLoopFilterGpu>(vec(probe_types, probe_type_count), vec(build_types, build_type_count), spec);
+    if (!f->supported()) fail(TGPU_ERR_NOT_SUPPORTED, "nested loop filter not fused: " + f->reason());
+    return f;
+}
+
+int32_t tgpu_precompile_nested_loop_filter(int32_t probe_type_count, const int32_t *probe_types, int32_t build_type_count, const int32_t *build_types,
+                                           const tgpu_page_processor_spec *spec)
+{
+    return guard([&] { nested_loop_filter(probe_type_count, probe_types, build_type_count, build_types, spec)->precompile(); });
+}
+
+int64_t tgpu_nested_loop_filter_source(int32_t probe_type_count, const int32_t *probe_types, int32_t build_type_count, const int32_t *build_types,
+                                       const tgpu_page_processor_spec *spec, char *buf, int64_t buf_len)
+{
+    int64_t need = 0;
+    int32_t rc = guard([&] {
+        auto f = nested_loop_filter(probe_type_count, probe_types, build_type_count, build_types, spec);
+        need = (int64_t)f->source().size() + 1;
+        if (buf && buf_len >= need) memcpy(buf, f->source().c_str(), (size_t)need);
+    });
+    return rc == TGPU_OK ? need : rc;
 }
 
 int32_t tgpu_mark_distinct_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t mark_channel_count,

@@ -4666,4 +4666,240 @@ void FusedAggGpu::accumulate(Context *ctx, const DevicePage &in, const int32_t *
     if (accumulate_can_raise_) raise_if_error(ctx, err);
 }
 
+// =====================================================================================================================
+// NestedLoopFilterGpu: the join predicate over the virtual product (jit.h)
+// =====================================================================================================================
+namespace {
+const char *kNlKernels = R"SRC(
+#define NL_STRIP 32
+struct NlArgs {
+  FpArgs fp;
+  unsigned long long* masks;
+  int* counts;
+  const int* offsets;
+  int* pair_probe;
+  int* pair_build;
+  long long s0, S, l0, Ln, W;
+  int build_large, pad;
+};
+// One wave = 64 rows of the large side x NL_STRIP rows of the small side.  The lane loads its large row's values ONCE, in front of the loop;
+// the small row is wave-uniform, so its values are scalar loads; the predicate itself touches registers only (NlRow).  Nothing is stored
+// inside the loop: lane i keeps the ballot of small row i and stores it at the end.
+extern "C" __global__ void __launch_bounds__(256) nlj_pair_count(NlArgs N) {
+  const int lane = threadIdx.x & 63;
+  // (readfirstlane: the wave's number is the same in all of its lanes, which the compiler does not see in threadIdx.x >> 6 -- with it the
+  // strip, the small row and the small row's loads are scalar)
+  const long long unit = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long strips = (N.S + NL_STRIP - 1) / NL_STRIP;
+  if (unit >= strips * N.W) return;   // the whole wave
+  const long long strip = unit / N.W, w = unit - strip * N.W;
+  const long long at = w * 64 + lane;
+  const bool in = at < N.Ln;
+  const long long lrow = N.l0 + (in ? at : N.Ln - 1);
+  const long long sb = strip * NL_STRIP;
+  unsigned long long mine = 0;
+  NlRow R;
+#if NL_BUILD_LARGE
+  tg_load_build(N.fp, lrow, R);
+#else
+  tg_load_probe(N.fp, lrow, R);
+#endif
+  for (int i = 0; i < NL_STRIP; i++) {
+    if (sb + i >= N.S) break;
+    const long long srow = N.s0 + sb + i;
+#if NL_BUILD_LARGE
+    tg_load_probe(N.fp, srow, R);
+#else
+    tg_load_build(N.fp, srow, R);
+#endif
+    const bool v = tg_pair_filter(N.fp, R);
+    const unsigned long long b = __ballot(in && v);
+    if (lane == i) mine = b;
+  }
+  if (lane < NL_STRIP && sb + lane < N.S) {
+    const long long e = (sb + lane) * N.W + w;
+    N.masks[e] = mine;
+    N.counts[e] = __popcll(mine);
+  }
+}
+// One wave takes 64 (small row, wave) entries; those with a survivor are written one after the other, each by all lanes: lane i holds
+// large row 64 w + i, its rank among the survivors is mbcnt of the entry's ballot (as in fp_emit).
+extern "C" __global__ void __launch_bounds__(256) nlj_pair_emit(NlArgs N) {
+  const int lane = threadIdx.x & 63;
+  const long long n = N.S * N.W;
+  const long long e0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+  if (e0 >= n) return;
+  const long long e = e0 + lane;
+  const unsigned long long m = e < n ? N.masks[e] : 0ULL;
+  const long long o = e < n ? (long long)N.offsets[e] : 0LL;
+  unsigned long long live = __ballot(m != 0ULL);
+  while (live) {
+    const int j = __ffsll((long long)live) - 1;
+    live &= live - 1;
+    const unsigned long long mj = __shfl(m, j, 64);
+    const long long oj = __shfl(o, j, 64);
+    if ((mj >> lane) & 1ULL) {
+      const long long ej = e0 + j;
+      const long long s = ej / N.W, w = ej - s * N.W;
+      const long long dst = oj + __builtin_amdgcn_mbcnt_hi((unsigned)(mj >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mj, 0u));
+      const int srow = (int)(N.s0 + s), lrow = (int)(N.l0 + w * 64 + lane);
+      N.pair_probe[dst] = N.build_large ? srow : lrow;
+      N.pair_build[dst] = N.build_large ? lrow : srow;
+    }
+  }
+}
+)SRC";
+
+// the node under `root` or one below it has VARCHAR type (an input, a constant, a string function)
+bool touches_varchar(const ExprProgram &p, int root)
+{
+    if (root < 0 || root >= (int)p.nodes.size()) return false;
+    const tgpu_expr_node &nd = p.nodes[(size_t)root];
+    if (nd.type == TGPU_VARCHAR) return true;
+    if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
+        for (int k = 0; k < nd.n_args && k < 3; k++)
+            if (touches_varchar(p, nd.args[k])) return true;
+    return false;
+}
+}  // namespace
+
+NestedLoopFilterGpu::NestedLoopFilterGpu(std::vector<int32_t> probe_types, std::vector<int32_t> build_types, const tgpu_page_processor_spec *spec)
+    : n_probe_(probe_types.size()), prog_([&] {
+          std::vector<int32_t> all = probe_types;
+          all.insert(all.end(), build_types.begin(), build_types.end());
+          return all;
+      }(), spec)
+{
+    prog_.proj_roots.clear();
+    generate();
+}
+
+std::shared_ptr<NestedLoopFilterGpu> NestedLoopFilterGpu::shared(const std::vector<int32_t> &probe_types, const std::vector<int32_t> &build_types,
+                                                                 const tgpu_page_processor_spec *spec)
+{
+    std::vector<int32_t> all = probe_types;
+    all.insert(all.end(), build_types.begin(), build_types.end());
+    return cached_object<NestedLoopFilterGpu>(spec_key("nl", all, spec, {(int32_t)probe_types.size()}),
+                                              [&] { return std::make_shared<NestedLoopFilterGpu>(probe_types, build_types, spec); });
+}
+
+void NestedLoopFilterGpu::generate()
+{
+    if (prog_.filter_root < 0) {
+        reason_ = "no filter";
+        return;
+    }
+    TG_CHECK_ARG(prog_.filter_root < (int)prog_.nodes.size(), "filter root out of range");
+    if (prog_.can_raise(prog_.filter_root)) {
+        reason_ = "the filter can raise";
+        return;
+    }
+    if (touches_varchar(prog_, prog_.filter_root)) {
+        reason_ = "the filter reads or computes VARCHAR";
+        return;
+    }
+    // the channels the predicate reads, compacted (the two sides together may have more than kFpMaxCols)
+    std::set<int> read;
+    prog_.inputs_of(prog_.filter_root, read);
+    if ((int)read.size() > kFpMaxCols) {
+        reason_ = "the filter reads more than " + std::to_string(kFpMaxCols) + " channels";
+        return;
+    }
+    std::vector<int> remap(prog_.input_types.size(), -1);
+    std::vector<int32_t> types;
+    for (int ch : read) {
+        TG_CHECK_ARG(ch >= 0 && ch < (int)remap.size(), "nested loop filter: input channel out of range");
+        remap[(size_t)ch] = (int)types.size();
+        types.push_back(prog_.input_types[(size_t)ch]);
+        sources_.push_back(ch);
+    }
+    for (auto &nd : prog_.nodes)
+        if (nd.kind == TGPU_EX_INPUT && nd.op >= 0 && nd.op < (int)remap.size() && remap[(size_t)nd.op] >= 0) nd.op = remap[(size_t)nd.op];
+        else if (nd.kind == TGPU_EX_INPUT) nd.op = -1;   // a reference the filter does not reach
+    prog_.input_types = types;
+
+    // Register-row mode of the shared emitter, unchanged: every input reference reads the pre-loaded row R.  (Read from memory at a row
+    // variable per channel instead, the loads sit under the predicate's short-circuit branches, where the compiler may not hoist them: the
+    // large row's values were loaded again for every small row.)  R has one field pair per channel; the probe side's and the build side's
+    // fields have a loader each, and the kernel decides which of them is the lane's own row.
+    Gen g(prog_);
+    g.reg_mode = true;
+    Val f = g.gen_root(prog_.filter_root, 2, 0);
+    if (f.type != TGPU_BOOLEAN) g.bad("filter must be boolean");
+    g.os << "    return !" << f.n << " && " << f.v << ";\n";
+    auto ftype = [&](int ch) { return prog_.input_types[(size_t)ch] == TGPU_BOOLEAN ? "unsigned char" : ctype(prog_.input_types[(size_t)ch]); };
+    std::ostringstream row;
+    row << "struct NlRow {\n";
+    for (int ch : g.reg_cols) row << "  " << ftype(ch) << " c" << ch << "; unsigned char n" << ch << ";\n";
+    if (g.reg_cols.empty()) row << "  int unused;\n";
+    row << "};\n";
+    for (int build = 0; build < 2; build++) {
+        row << "__device__ inline void tg_load_" << (build ? "build" : "probe") << "(const FpArgs& A, long long row, NlRow& R) {\n";
+        for (int ch : g.reg_cols)
+            if (((size_t)sources_[(size_t)ch] >= n_probe_) == (build != 0))
+                row << "  R.c" << ch << " = ((const " << ftype(ch) << "*)A.col_values[" << ch << "])[row]; R.n" << ch << " = A.col_nulls[" << ch << "] ? A.col_nulls[" << ch
+                    << "][row] : 0;\n";
+        row << "  (void)A; (void)row; (void)R;\n}\n";
+    }
+    std::ostringstream src;
+    src << kPrelude << g.consts.str() << row.str();
+    src << "__device__ inline bool tg_pair_filter(const FpArgs& A, const NlRow& R) {\n" << g.os.str() << "  (void)A;\n}\n";
+    src << kNlKernels;
+    source_ = src.str();
+    supported_ = true;
+}
+
+static std::string nl_variant(const std::string &src, int build_large) { return "#define NL_BUILD_LARGE " + std::to_string(build_large) + "\n" + src; }
+
+void NestedLoopFilterGpu::precompile()
+{
+    if (!supported_) return;
+    for (int v = 0; v < 2; v++) (void)code_object_for(nl_variant(source_, v));
+}
+
+int64_t NestedLoopFilterGpu::pairs(Context *ctx, const DevicePage &probe, const DevicePage &build, bool build_large, int64_t s0, int64_t S, int64_t l0, int64_t Ln,
+                                   BufferPtr &probe_idx, BufferPtr &build_idx)
+{
+    TG_CHECK_STATE(supported_, "the nested loop filter is not fused");
+    const DevicePage &large = build_large ? build : probe, &small = build_large ? probe : build;
+    TG_CHECK_ARG(S > 0 && Ln > 0 && s0 >= 0 && l0 >= 0 && s0 + S <= small.n && l0 + Ln <= large.n, "nested loop filter: row range outside its page");
+    JitModule *module;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!module_[build_large ? 1 : 0]) module_[build_large ? 1 : 0] = load_module(nl_variant(source_, build_large ? 1 : 0));
+        module = module_[build_large ? 1 : 0].get();
+    }
+    NlArgs N{};
+    for (size_t i = 0; i < sources_.size(); i++) {
+        const size_t ch = (size_t)sources_[i];
+        const DeviceColumn &c = ch < n_probe_ ? probe.cols.at(ch) : build.cols.at(ch - n_probe_);
+        TG_CHECK_ARG(c.type == prog_.input_types[i], "nested loop filter: page channel type differs from the operator's types");
+        N.fp.col_values[i] = c.values;
+        N.fp.col_nulls[i] = c.nulls;
+    }
+    N.s0 = s0; N.S = S; N.l0 = l0; N.Ln = Ln;
+    N.W = ceil_div(Ln, 64);
+    N.build_large = build_large ? 1 : 0;
+    const int64_t entries = S * N.W, units = ceil_div(S, kNlStrip) * N.W;
+    TG_CHECK_ARG(entries < 0x7fffffffLL && S * Ln <= 0x7fffffffLL, "nested loop filter: step too large");
+    BufferPtr masks = ctx->alloc((size_t)entries * 8), counts = ctx->alloc((size_t)entries * 4), offsets = ctx->alloc((size_t)entries * 4), total = ctx->alloc(8);
+    N.masks = masks->as<unsigned long long>();
+    N.counts = counts->as<int32_t>();
+    N.offsets = offsets->as<int32_t>();
+    {
+        ProfileScope ps(ctx, "nlj_pair_count");
+        launch_args(module->fn("nlj_pair_count"), (int)ceil_div(units, 4), N, ctx->stream());
+    }
+    k::exclusive_scan_i32(ctx, counts->as<int32_t>(), offsets->as<int32_t>(), entries, total->as<int64_t>());
+    const int64_t n = ctx->read_scalar(total->as<int64_t>());
+    if (n == 0) return 0;
+    probe_idx = ctx->alloc((size_t)n * 4);
+    build_idx = ctx->alloc((size_t)n * 4);
+    N.pair_probe = probe_idx->as<int32_t>();
+    N.pair_build = build_idx->as<int32_t>();
+    ProfileScope ps(ctx, "nlj_pair_emit");
+    launch_args(module->fn("nlj_pair_emit"), (int)ceil_div(entries, 256), N, ctx->stream());
+    return n;
+}
+
 }  // namespace tgpu

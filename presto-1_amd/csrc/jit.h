@@ -310,6 +310,52 @@ private:
     std::shared_ptr<JitModule> module_, module_nn_, module_g8_, module_nn_g8_;
 };
 
+// ---- the predicate of a nested loop join, evaluated over the VIRTUAL product of a probe page and a build page -------------------------
+// Channel k < probe types of the spec is probe channel k, the following ones the build page's (probe first: the order of the join's output
+// page).  The predicate becomes tg_pair_filter(A, R) over a pre-loaded register row R (one loader per side); nlj_pair_count evaluates it for a strip of rows of the small side against
+// every row of the large side (a lane keeps its large row, the small row is wave-uniform) and keeps one 64-bit ballot and its popcount per
+// (small row, wave of the large side); after the scan of the counts nlj_pair_emit writes the surviving (probe row, build row) pairs in the
+// order of the reference's output pages: small row major, large row minor.
+struct NlArgs {  // must match the struct declared in the generated source
+    FpArgs fp;
+    unsigned long long *masks;
+    int32_t *counts;
+    const int32_t *offsets;
+    int32_t *pair_probe, *pair_build;
+    long long s0, S;     // rows [s0, s0 + S) of the small side ...
+    long long l0, Ln;    // ... against rows [l0, l0 + Ln) of the large side
+    long long W;         // waves over the large rows: ceil(Ln / 64)
+    int32_t build_large, pad;
+};
+constexpr int kNlStrip = 32;   // small rows one wave evaluates for its 64 large rows (= NL_STRIP of the generated source)
+
+class NestedLoopFilterGpu {
+public:
+    NestedLoopFilterGpu(std::vector<int32_t> probe_types, std::vector<int32_t> build_types, const tgpu_page_processor_spec *spec);
+    static std::shared_ptr<NestedLoopFilterGpu> shared(const std::vector<int32_t> &probe_types, const std::vector<int32_t> &build_types,
+                                                       const tgpu_page_processor_spec *spec);   // see PageProcessorGpu::shared
+    // false: the operator evaluates the filter over materialised product pieces instead (`reason` says why: no filter, a filter that can
+    // raise, VARCHAR in the predicate, more than kFpMaxCols channels read)
+    bool supported() const { return supported_; }
+    const std::string &reason() const { return reason_; }
+    const std::string &source() const { return source_; }
+    void precompile();
+    // the pairs of small rows [s0, s0 + S) x large rows [l0, l0 + Ln) that pass, in sequence order; returns their number.  The large side
+    // is the build page iff build_large.  S * ceil(Ln / 64) and S * Ln stay below 2^31.
+    int64_t pairs(Context *ctx, const DevicePage &probe, const DevicePage &build, bool build_large, int64_t s0, int64_t S, int64_t l0, int64_t Ln, BufferPtr &probe_idx,
+                  BufferPtr &build_idx);
+
+private:
+    void generate();
+    std::mutex mu_;
+    size_t n_probe_;
+    ExprProgram prog_;            // the filter alone, over the compacted channels
+    std::vector<int> sources_;    // compacted channel -> channel of the spec
+    bool supported_ = false;
+    std::string reason_, source_;
+    std::shared_ptr<JitModule> module_[2];   // [build_large]
+};
+
 std::string resource_dir();
 void set_resource_dir(const std::string &dir);
 

@@ -2272,6 +2272,400 @@ static void validate(Context *, const HashSemiJoinConfig &cfg)
 }
 
 // =====================================================================================================================
+// NestedLoopBuildOperator (M/operator/NestedLoopBuildOperator.java:96-190): a sink.  Its pages stay in HBM as delivered
+// (NestedLoopJoinPagesBuilder.java:45-110: empty pages dropped, pages without channels only counted and re-cut into pages of
+// PageProcessor.MAX_BATCH_SIZE positions); finish() publishes them to the probes through the bridge.  Like the hash builder it then stays
+// alive, blocked, until every probe operator has closed and the probe factories have seen noMoreOperators (:131-150).
+// =====================================================================================================================
+class NestedLoopBuildOperator : public Operator {
+public:
+    enum class State { CONSUMING_INPUT, PAGES_PUBLISHED, CLOSED };
+    static constexpr int64_t kMaxBatchSize = 8192;   // PageProcessor.MAX_BATCH_SIZE
+
+    NestedLoopBuildOperator(Context *ctx, int32_t id, std::shared_ptr<NestedLoopBridge> bridge)
+        : Operator(ctx, id), bridge_(std::move(bridge)), pages_(std::make_shared<NestedLoopPages>())
+    {
+    }
+
+    bool needs_input() override { return state_ == State::CONSUMING_INPUT; }
+    void add_input(const tgpu_page *page) override
+    {
+        TG_CHECK_STATE(state_ == State::CONSUMING_INPUT, "Operator is already finishing");
+        TG_CHECK_ARG(page != nullptr, "page is null");
+        if (bridge_->build_types().empty()) {
+            TG_CHECK_ARG(page->channel_count == 0 && page->position_count >= 0, "page channel count does not match the operator's types");
+            count(page->position_count);
+            return;
+        }
+        add(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        TG_CHECK_STATE(state_ == State::CONSUMING_INPUT, "Operator is already finishing");
+        add(DevicePage(page));
+    }
+    std::unique_ptr<OutputPage> get_output() override { return nullptr; }   // :176-180
+
+    void finish() override   // :152-164
+    {
+        if (state_ != State::CONSUMING_INPUT) return;
+        if (counter_ > 0) push_count(counter_);   // NestedLoopJoinPagesBuilder.build :100-105
+        counter_ = 0;
+        bridge_->publish(pages_);
+        state_ = State::PAGES_PUBLISHED;
+    }
+    bool is_blocked() override { return state_ == State::PAGES_PUBLISHED && !bridge_->destroyed(); }
+    bool is_finished() override
+    {
+        if (state_ == State::PAGES_PUBLISHED && bridge_->destroyed()) close();
+        return state_ == State::CLOSED;
+    }
+    int64_t memory_bytes() override { return state_ == State::CLOSED || !pages_ ? 0 : pages_->bytes; }
+    void close() override
+    {
+        state_ = State::CLOSED;
+        pages_.reset();   // (the probes hold the published pages through the bridge)
+    }
+
+private:
+    void add(DevicePage in)
+    {
+        check_page_types(in, bridge_->build_types());
+        if (in.n == 0) return;
+        if (in.cols.empty()) {
+            count(in.n);
+            return;
+        }
+        pages_->positions += in.n;
+        pages_->bytes += in.size_in_bytes();
+        pages_->pages.push_back(nl_keep(ctx_, std::move(in)));
+    }
+    void count(int64_t positions)   // updatePagePositionCounter :64-76
+    {
+        counter_ += positions;
+        for (; counter_ >= kMaxBatchSize; counter_ -= kMaxBatchSize) push_count(kMaxBatchSize);
+    }
+    void push_count(int64_t positions)
+    {
+        NlPage pg;
+        pg.page.n = positions;
+        pages_->pages.push_back(std::move(pg));
+        pages_->positions += positions;
+    }
+
+    std::shared_ptr<NestedLoopBridge> bridge_;
+    std::shared_ptr<NestedLoopPages> pages_;
+    int64_t counter_ = 0;
+    State state_ = State::CONSUMING_INPUT;
+};
+
+NestedLoopBuildOperatorFactory::NestedLoopBuildOperatorFactory(Context *ctx, int32_t operator_id, std::shared_ptr<NestedLoopBridge> bridge)
+    : ctx_(ctx), operator_id_(operator_id), bridge_(std::move(bridge))
+{
+    for (int32_t t : bridge_->build_types()) TG_CHECK_ARG(valid_type(t), "unknown type");
+}
+
+std::unique_ptr<Operator> NestedLoopBuildOperatorFactory::create_operator()
+{
+    check_open();
+    return std::make_unique<NestedLoopBuildOperator>(ctx_, operator_id_, bridge_);
+}
+
+// =====================================================================================================================
+// NestedLoopJoinOperator (M/operator/NestedLoopJoinOperator.java:154-274), alone or with a FilterAndProjectOperator fused behind it.
+//
+// The sequence: one probe page against each build page in turn; within a pair, one reference page per row of the small side, each the
+// large side's L rows with the small row repeated (nested_loop.h) -- row r of the pair is (small row r / L, large row r % L).  The build
+// page is the large side iff it has more rows; with no probe output channel a tie goes to the build page as well (PageRepeatingIterator,
+// :265-267).  The operator hands that sequence out in pieces of its own size.
+//
+// Alone: every get_output materialises the next piece (nlj_product), at most max_rows rows and cut short where a VARCHAR channel's pool
+// would reach 2^31 bytes; without output channels only counts come out, as few pages as the int32 position count allows.
+//
+// Fused: the spec's channels are (probe channels..., build channels...).  A filter the generator covers and that cannot raise is
+// evaluated over the virtual product (NestedLoopFilterGpu: nlj_pair_count / nlj_pair_emit), whole small rows at a time or, where one
+// small row's L pairs exceed max_rows, a range of large rows; the channels the projections read are gathered by the surviving pairs and
+// a projection-only page processor runs over them.  Every other spec takes the unfused composition inside the operator: product pieces of
+// the channels the spec reads, then the whole page processor.
+//
+// Errors.  The reference composition throws at the first reference page that fails, within it the filter before projection 0 before
+// projection 1, then the first row.  Pieces are processed in sequence order, so the first piece that reports an error holds that page;
+// which one it is, and what it throws, is found by running the piece's reference pages again one at a time, each WHOLE (a piece may hold
+// part of one; the parts before it raised nothing): slow, exact, and only on the error path.
+// =====================================================================================================================
+struct NestedLoopPrograms {
+    std::shared_ptr<NestedLoopFilterGpu> filter;          // the fused route when filter->supported()
+    std::shared_ptr<PageProcessorGpu> all, proj;          // the whole spec / its projections alone, over the channels each reads
+    std::vector<int> all_sources, proj_sources;           // compacted channel -> channel of the spec
+};
+
+namespace {
+std::shared_ptr<PageProcessorGpu> compact_processor(const std::vector<int32_t> &types, const NestedLoopJoinConfig &cfg, bool with_filter, std::vector<int> &sources)
+{
+    tgpu_page_processor_spec spec{cfg.nodes.data(), (int32_t)cfg.nodes.size(), cfg.pool.data(), (int32_t)cfg.pool.size(), with_filter ? cfg.filter_root : -1,
+                                  (int32_t)cfg.projection_roots.size(), cfg.projection_roots.data()};
+    ExprProgram prog(types, &spec);
+    std::set<int> read;
+    if (spec.filter_root >= 0) prog.inputs_of(spec.filter_root, read);
+    for (int32_t r : cfg.projection_roots) prog.inputs_of(r, read);
+    // compacted as apply_join_filter does: the two sides together may have more than kFpMaxCols channels
+    std::vector<int> remap(types.size(), -1);
+    std::vector<int32_t> ctypes;
+    for (int ch : read) {
+        TG_CHECK_ARG(ch >= 0 && ch < (int)types.size(), "nested loop join: input channel out of range");
+        remap[(size_t)ch] = (int)ctypes.size();
+        ctypes.push_back(types[(size_t)ch]);
+        sources.push_back(ch);
+    }
+    std::vector<tgpu_expr_node> nodes = cfg.nodes;
+    for (auto &nd : nodes)
+        if (nd.kind == TGPU_EX_INPUT && nd.op >= 0 && nd.op < (int)remap.size() && remap[(size_t)nd.op] >= 0) nd.op = remap[(size_t)nd.op];
+    spec.nodes = nodes.data();
+    return PageProcessorGpu::shared(ctypes, &spec);
+}
+
+bool is_expression_error(int32_t code)
+{
+    return code == TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE || code == TGPU_ERR_DIVISION_BY_ZERO || code == TGPU_ERR_INVALID_CAST_ARGUMENT || code == TGPU_ERR_INVALID_ARGUMENT;
+}
+}  // namespace
+
+class NestedLoopJoinOperator : public Operator {
+public:
+    NestedLoopJoinOperator(Context *ctx, int32_t id, const NestedLoopJoinConfig &cfg, std::shared_ptr<NestedLoopBridge> bridge, std::shared_ptr<NestedLoopPrograms> programs)
+        : Operator(ctx, id), cfg_(cfg), bridge_(std::move(bridge)), programs_(std::move(programs))
+    {
+        const bool counts_only = !cfg_.fused && cfg_.probe_channels.empty() && cfg_.build_channels.empty();
+        cap_ = cfg_.max_rows > 0 ? std::min(cfg_.max_rows, kNlMaxPositions) : (cfg_.fused ? kNlDefaultProductRows : counts_only ? kNlMaxPositions : kNlDefaultOutputRows);
+        bridge_->probe_created();
+    }
+    ~NestedLoopJoinOperator() override { close(); }
+
+    // blocked until the build side has published its pages (:171-175); an operator that is finishing without them has had no page
+    bool is_blocked() override { return !closed_ && !finishing_ && !bridge_->pages(); }
+    bool needs_input() override { return !closed_ && !finishing_ && !active_ && !is_blocked(); }   // :177-191
+    void add_input(const tgpu_page *page) override
+    {
+        ready();
+        start(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        ready();
+        start(DevicePage(page));
+    }
+    void finish() override { finishing_ = true; }
+    bool is_finished() override   // :160-169
+    {
+        const bool done = closed_ || (finishing_ && !active_);
+        if (done) close();
+        return done;
+    }
+    int64_t memory_bytes() override { return active_ ? probe_.page.size_in_bytes() : 0; }
+    void close() override
+    {
+        if (closed_) return;
+        closed_ = true;
+        end_page();
+        build_.reset();
+        bridge_->probe_closed();
+    }
+
+    std::unique_ptr<OutputPage> get_output() override   // :208-228
+    {
+        if (!active_) return nullptr;
+        if (counts_left_ >= 0) {   // no output channel at all: position counts
+            DevicePage out;
+            out.n = std::min(cap_, counts_left_);
+            counts_left_ -= out.n;
+            if (counts_left_ == 0) end_page();
+            return wrap(std::move(out));
+        }
+        const NlPage &bp = build_->pages[j_];
+        Pair pr;
+        pr.build = &bp;
+        const int64_t p = probe_.page.n, b = bp.page.n;
+        const bool probe_out = cfg_.fused ? !cfg_.probe_types.empty() : !cfg_.probe_channels.empty();
+        const bool build_out = cfg_.fused ? !bridge_->build_types().empty() : !cfg_.build_channels.empty();
+        pr.build_large = b > p || (b == p && !probe_out && build_out);
+        pr.L = pr.build_large ? b : p;
+        pr.S = pr.build_large ? p : b;
+        const int64_t total = pr.S * pr.L;
+        DevicePage out;
+        int64_t rows = 0;
+        bool have;
+        if (!cfg_.fused) {
+            rows = cut(pr, cfg_.probe_channels, cfg_.build_channels, r_, std::min(cap_, total - r_));
+            out = product(pr, cfg_.probe_channels, cfg_.build_channels, r_, rows);
+            have = true;
+        }
+        else have = filter_step(pr, total, out, rows);
+        r_ += rows;
+        if (r_ == total) {
+            r_ = 0;
+            if (++j_ == build_->pages.size()) end_page();
+        }
+        return have ? wrap(std::move(out)) : nullptr;
+    }
+
+private:
+    struct Pair {
+        const NlPage *build;
+        bool build_large;
+        int64_t L, S;
+    };
+
+    void ready()
+    {
+        TG_CHECK_STATE(!finishing_ && !closed_, "Operator is finishing");                                   // :197
+        TG_CHECK_STATE(bridge_->pages() != nullptr, "Page source has not been built yet");                 // :198
+        TG_CHECK_STATE(!active_, "Current page has not been completely processed yet");                    // :199
+    }
+    void start(DevicePage in)
+    {
+        check_page_types(in, cfg_.probe_types);
+        build_ = bridge_->pages();
+        if (in.n == 0 || build_->pages.empty()) return;   // :202-205; an empty build side gives nothing at all
+        if (!cfg_.fused && cfg_.probe_channels.empty() && cfg_.build_channels.empty()) counts_left_ = in.n * build_->positions;
+        probe_ = nl_keep(ctx_, std::move(in));
+        active_ = true;
+        j_ = 0;
+        r_ = 0;
+    }
+    void end_page()
+    {
+        active_ = false;
+        counts_left_ = -1;
+        probe_ = NlPage();
+    }
+
+    // rows [r, r + n) of the pair: the probe channels, then the build channels
+    DevicePage product(const Pair &pr, const std::vector<int32_t> &probe_channels, const std::vector<int32_t> &build_channels, int64_t r, int64_t n)
+    {
+        ProfileScope ps(ctx_, "nlj_product");
+        DevicePage out;
+        out.n = n;
+        for (int32_t ch : probe_channels) out.cols.push_back(nl_product_column(ctx_, probe_, ch, !pr.build_large, pr.L, r, n));
+        for (int32_t ch : build_channels) out.cols.push_back(nl_product_column(ctx_, *pr.build, ch, pr.build_large, pr.L, r, n));
+        return out;
+    }
+    int64_t cut(const Pair &pr, const std::vector<int32_t> &probe_channels, const std::vector<int32_t> &build_channels, int64_t r, int64_t want)
+    {
+        return std::min(nl_cut_rows(probe_, probe_channels, !pr.build_large, pr.L, r, want), nl_cut_rows(*pr.build, build_channels, pr.build_large, pr.L, r, want));
+    }
+
+    // ---- fused ----
+    void split_sources(const std::vector<int> &sources, std::vector<int32_t> &probe_channels, std::vector<int32_t> &build_channels) const
+    {
+        const int np = (int)cfg_.probe_types.size();
+        for (int src : sources) (src < np ? probe_channels : build_channels).push_back(src < np ? src : src - np);
+    }
+    // the unfused composition over rows [r, r + n): product of the channels the spec reads, then the page processor
+    bool process_rows(const Pair &pr, int64_t r, int64_t n, DevicePage &out)
+    {
+        std::vector<int32_t> pc, bc;
+        split_sources(programs_->all_sources, pc, bc);   // (sources ascend: the probe's channels come first, as in the compacted page)
+        DevicePage in = product(pr, pc, bc, r, n);
+        return programs_->all->process(ctx_, in, out);
+    }
+    // the fused route over small rows [s, s + Sn) x large rows [l, l + Ln)
+    bool process_pairs(const Pair &pr, int64_t s, int64_t Sn, int64_t l, int64_t Ln, DevicePage &out)
+    {
+        BufferPtr probe_idx, build_idx;
+        const int64_t n = programs_->filter->pairs(ctx_, probe_.page, pr.build->page, pr.build_large, s, Sn, l, Ln, probe_idx, build_idx);
+        if (n == 0) return false;
+        DevicePage survivors;
+        survivors.n = n;
+        const int np = (int)cfg_.probe_types.size();
+        {
+            ProfileScope ps(ctx_, "nlj_gather");
+            for (int src : programs_->proj_sources)
+                survivors.cols.push_back(src < np ? k::gather_column(ctx_, probe_.page.cols[(size_t)src], probe_idx->as<int32_t>(), n, false)
+                                                  : k::gather_column(ctx_, pr.build->page.cols[(size_t)(src - np)], build_idx->as<int32_t>(), n, false));
+        }
+        return programs_->proj->process(ctx_, survivors, out);
+    }
+    bool filter_step(const Pair &pr, int64_t total, DevicePage &out, int64_t &rows)
+    {
+        const bool fused_route = programs_->filter->supported();
+        const int64_t s = r_ / pr.L, l = r_ - s * pr.L;
+        int64_t Sn = 1, Ln = 0;
+        if (fused_route) {
+            if (l == 0 && pr.L <= cap_) {
+                Sn = std::min(pr.S - s, cap_ / pr.L);
+                Ln = pr.L;
+            }
+            else Ln = std::min(pr.L - l, cap_);
+            rows = Sn * Ln;
+        }
+        else {
+            std::vector<int32_t> pc, bc;
+            split_sources(programs_->all_sources, pc, bc);
+            rows = cut(pr, pc, bc, r_, std::min(cap_, total - r_));
+        }
+        try {
+            return fused_route ? process_pairs(pr, s, Sn, l, Ln, out) : process_rows(pr, r_, rows, out);
+        }
+        catch (const Error &e) {
+            if (!is_expression_error(e.code)) throw;
+            // which reference page fails first, and with what: each page of the piece again, whole, in order
+            for (int64_t page = s; page <= (r_ + rows - 1) / pr.L; page++) {
+                DevicePage ignored;
+                if (fused_route) process_pairs(pr, page, 1, 0, pr.L, ignored);
+                else process_rows(pr, page * pr.L, pr.L, ignored);
+            }
+            throw;
+        }
+    }
+
+    NestedLoopJoinConfig cfg_;
+    std::shared_ptr<NestedLoopBridge> bridge_;
+    std::shared_ptr<NestedLoopPrograms> programs_;
+    std::shared_ptr<const NestedLoopPages> build_;
+    NlPage probe_;
+    size_t j_ = 0;               // the build page of the current pair
+    int64_t r_ = 0;              // the next row of the pair's sequence
+    int64_t counts_left_ = -1;   // >= 0: no output channel, the positions still to hand out for the probe page
+    int64_t cap_ = 0;
+    bool active_ = false, finishing_ = false, closed_ = false;
+};
+
+NestedLoopJoinOperatorFactory::NestedLoopJoinOperatorFactory(Context *ctx, int32_t operator_id, NestedLoopJoinConfig cfg, std::shared_ptr<NestedLoopBridge> bridge)
+    : ctx_(ctx), operator_id_(operator_id), cfg_(std::move(cfg)), bridge_(std::move(bridge))
+{
+    for (int32_t t : cfg_.probe_types) TG_CHECK_ARG(valid_type(t), "unknown type");
+    for (int32_t ch : cfg_.probe_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)cfg_.probe_types.size(), "probe channel out of range");
+    for (int32_t ch : cfg_.build_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)bridge_->build_types().size(), "build channel out of range");
+    TG_CHECK_ARG(cfg_.max_rows >= 0, "the row limit must be at least zero");
+    if (cfg_.fused) {
+        std::vector<int32_t> types = cfg_.probe_types;
+        types.insert(types.end(), bridge_->build_types().begin(), bridge_->build_types().end());
+        programs_ = std::make_shared<NestedLoopPrograms>();
+        programs_->all = compact_processor(types, cfg_, true, programs_->all_sources);   // (checks the spec, whichever route it takes)
+        tgpu_page_processor_spec spec{cfg_.nodes.data(), (int32_t)cfg_.nodes.size(), cfg_.pool.data(), (int32_t)cfg_.pool.size(), cfg_.filter_root,
+                                      (int32_t)cfg_.projection_roots.size(), cfg_.projection_roots.data()};
+        programs_->filter = NestedLoopFilterGpu::shared(cfg_.probe_types, bridge_->build_types(), &spec);
+        if (programs_->filter->supported()) programs_->proj = compact_processor(types, cfg_, false, programs_->proj_sources);
+    }
+    bridge_->probe_factory_created();
+}
+
+std::unique_ptr<Operator> NestedLoopJoinOperatorFactory::create_operator()
+{
+    check_open();
+    return std::make_unique<NestedLoopJoinOperator>(ctx_, operator_id_, cfg_, bridge_, programs_);
+}
+
+std::unique_ptr<OperatorFactory> NestedLoopJoinOperatorFactory::duplicate() { return std::make_unique<NestedLoopJoinOperatorFactory>(ctx_, operator_id_, cfg_, bridge_); }
+
+void NestedLoopJoinOperatorFactory::no_more_operators()
+{
+    if (closed_) return;
+    closed_ = true;
+    bridge_->no_more_probes();
+}
+
+// =====================================================================================================================
 // MarkDistinctOperator (M/operator/MarkDistinctOperator.java:94-203): the input page's channels unchanged, then one BOOLEAN channel
 // without nulls that is true on the first row of every key the operator has not seen before (MarkDistinctHash.java:52-69); one output
 // page per input page.  A null key is a group like any other.  DistinctLimitOperator (M/operator/DistinctLimitOperator.java:101-263):

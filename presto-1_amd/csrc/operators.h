@@ -10,6 +10,7 @@
 #include "distinct.h"
 #include "groupby.h"
 #include "jit.h"
+#include "nested_loop.h"
 #include "rownumber.h"
 #include "join.h"
 #include "semijoin.h"
@@ -379,6 +380,110 @@ struct HashSemiJoinConfig {
 };
 using HashSemiJoinOperatorFactory = SimpleOperatorFactory<HashSemiJoinConfig, class HashSemiJoinOperator>;
 
+// ---- nested loop join bridge: NestedLoopJoinPagesSupplier / NestedLoopJoinBridge (M/operator/NestedLoopJoinPagesSupplier.java) --------
+// The build pages as NestedLoopJoinPagesBuilder keeps them (M/operator/NestedLoopJoinPagesBuilder.java:45-110): empty pages dropped, pages
+// of a build side without channels only counted and re-cut into pages of 8192 positions plus a remainder.  Page boundaries decide which
+// side of a (probe page, build page) pair is the large one, so the pages stay as delivered.
+struct NestedLoopPages {
+    std::vector<NlPage> pages;
+    int64_t positions = 0, bytes = 0;
+};
+// Shared by the build operator and every probe operator (different drivers, i.e. threads): guarded by one mutex.  The published pages are
+// immutable.  The probe accounting is the hash join bridge's (LookupSourceFactory above).
+class NestedLoopBridge {
+public:
+    explicit NestedLoopBridge(std::vector<int32_t> build_types) : build_types_(std::move(build_types)) {}
+    const std::vector<int32_t> &build_types() const { return build_types_; }
+    std::shared_ptr<const NestedLoopPages> pages() const
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        return pages_;
+    }
+    void publish(std::shared_ptr<const NestedLoopPages> p)   // NestedLoopJoinPagesSupplier.setPages -> SettableFuture: one setter only
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        TG_CHECK_STATE(!pages_, "pagesFuture already set");
+        pages_ = std::move(p);
+    }
+    void probe_created()
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        live_probes_++;
+    }
+    void probe_closed()
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        live_probes_--;
+    }
+    void probe_factory_created()
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        probe_factories_++;
+    }
+    void no_more_probes()
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (probe_factories_ > 0) probe_factories_--;
+        if (probe_factories_ == 0) no_more_probes_ = true;
+    }
+    // the build operator may end once every probe operator has closed and every probe factory has seen noMoreOperators
+    bool destroyed() const
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        return no_more_probes_ && live_probes_ == 0;
+    }
+
+private:
+    const std::vector<int32_t> build_types_;
+    mutable std::mutex mu_;
+    std::shared_ptr<const NestedLoopPages> pages_;
+    int live_probes_ = 0, probe_factories_ = 0;
+    bool no_more_probes_ = false;
+};
+
+// ---- NestedLoopBuildOperator (M/operator/NestedLoopBuildOperator.java:33-190) -------------------------------------------------------
+class NestedLoopBuildOperatorFactory : public OperatorFactory {
+public:
+    NestedLoopBuildOperatorFactory(Context *ctx, int32_t operator_id, std::shared_ptr<NestedLoopBridge> bridge);
+    std::unique_ptr<Operator> create_operator() override;
+    // duplicate(): the base class's NOT_SUPPORTED -- a duplicate would publish to the same bridge a second time
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    std::shared_ptr<NestedLoopBridge> bridge_;
+};
+
+// ---- NestedLoopJoinOperator (M/operator/NestedLoopJoinOperator.java:44-274) and the same with a FilterAndProjectOperator fused behind it ----
+struct NestedLoopJoinConfig {
+    std::vector<int32_t> probe_types, probe_channels, build_channels;
+    int64_t max_rows = 0;   // rows of one output page (join) / pairs evaluated by one get_output (fused); 0 = the default
+    // fused operator only: the page processor over (probe channels..., build channels...)
+    bool fused = false;
+    std::vector<tgpu_expr_node> nodes;
+    std::string pool;
+    int32_t filter_root = -1;
+    std::vector<int32_t> projection_roots;
+};
+constexpr int64_t kNlDefaultOutputRows = 1 << 22;          // rows of one output page of the join (any channel lists): 32 MB per 8-byte channel and launch
+constexpr int64_t kNlDefaultProductRows = 1ll << 26;       // pairs one step of the fused operator evaluates
+constexpr int64_t kNlMaxPositions = 0x7fffffffLL;          // a page's position count is an int32
+
+class NestedLoopJoinOperatorFactory : public OperatorFactory {
+public:
+    NestedLoopJoinOperatorFactory(Context *ctx, int32_t operator_id, NestedLoopJoinConfig cfg, std::shared_ptr<NestedLoopBridge> bridge);
+    std::unique_ptr<Operator> create_operator() override;
+    std::unique_ptr<OperatorFactory> duplicate() override;
+    void no_more_operators() override;
+
+private:
+    Context *ctx_;
+    int32_t operator_id_;
+    NestedLoopJoinConfig cfg_;
+    std::shared_ptr<NestedLoopBridge> bridge_;
+    std::shared_ptr<struct NestedLoopPrograms> programs_;   // fused operator: the compiled filter and page processors
+};
+
 // ---- MarkDistinctOperator (M/operator/MarkDistinctOperator.java:37-203) ---------------------------------------------------------------
 struct MarkDistinctConfig {
     std::vector<int32_t> types, mark_channels;
@@ -504,6 +609,10 @@ struct tgpu_lookup_source_factory {
 };
 struct tgpu_set_supplier {
     std::shared_ptr<tgpu::SetSupplier> supplier;
+    tgpu::Context *ctx = nullptr;
+};
+struct tgpu_nested_loop_bridge {
+    std::shared_ptr<tgpu::NestedLoopBridge> bridge;
     tgpu::Context *ctx = nullptr;
 };
 struct tgpu_group_by_hash {

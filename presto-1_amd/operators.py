@@ -785,6 +785,92 @@ class HashSemiJoinOperatorFactory(OperatorFactory):
         self._supplier = set_supplier
 
 
+class NestedLoopBridge:
+    """NestedLoopJoinPagesSupplier (M/operator/NestedLoopJoinPagesSupplier.java): the bridge from the nested loop build operator to the probes."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def stats(self):
+        """valid once the build operator finished: kept pages (zero-channel pages re-cut to 8192 positions), their positions, their HBM bytes"""
+        pages, positions, nbytes = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().tgpu_nested_loop_bridge_stats(self.handle, C.byref(pages), C.byref(positions), C.byref(nbytes)))
+        return dict(pages=pages.value, positions=positions.value, bytes=nbytes.value)
+
+    def close(self):
+        if self.handle:
+            _lib.lib().tgpu_nested_loop_bridge_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # a constructor that failed before `handle` existed, or interpreter shutdown
+            pass
+
+
+class NestedLoopBuildOperatorFactory(OperatorFactory):
+    """NestedLoopBuildOperator.NestedLoopBuildOperatorFactory (M/operator/NestedLoopBuildOperator.java:33-94).  `bridge` goes to the
+    NestedLoopJoinOperatorFactory / FilterProjectNestedLoopJoinOperatorFactory."""
+
+    def __init__(self, ctx: Context, operator_id, types):
+        t, nt = _i32(types)
+        b, h = C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().tgpu_nested_loop_build_factory_create(ctx.handle, operator_id, nt, t, C.byref(b), C.byref(h)))
+        super().__init__(h)
+        self.bridge = NestedLoopBridge(b)
+
+
+class NestedLoopJoinOperatorFactory(OperatorFactory):
+    """NestedLoopJoinOperator.NestedLoopJoinOperatorFactory (M/operator/NestedLoopJoinOperator.java:44-108): the rows of the reference's
+    output pages in their order, `probe_channels` then `build_channels`, at most `max_output_rows` rows per output page (0 = default)."""
+
+    def __init__(self, ctx: Context, operator_id, bridge: NestedLoopBridge, probe_types, probe_channels, build_channels, max_output_rows=0):
+        t, nt = _i32(probe_types)
+        pc, npc = _i32(probe_channels)
+        bc, nbc = _i32(build_channels)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_nested_loop_join_factory_create(ctx.handle, operator_id, bridge.handle, nt, t, npc, pc, nbc, bc, int(max_output_rows), C.byref(h)))
+        super().__init__(h)
+        self._bridge = bridge
+
+
+class FilterProjectNestedLoopJoinOperatorFactory(OperatorFactory):
+    """NestedLoopJoin(all probe channels, all build channels) -> FilterAndProject as one operator.  Channel k < len(probe_types) of the
+    expressions is probe channel k, the following ones are the build side's (probe first)."""
+
+    def __init__(self, ctx: Context, operator_id, bridge: NestedLoopBridge, probe_types, filter_expr, projections, max_product_rows=0):
+        self.program = FlatProgram(filter_expr, projections)
+        spec, keep = self.program.to_c()
+        t, nt = _i32(probe_types)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_filter_project_nested_loop_join_factory_create(ctx.handle, operator_id, bridge.handle, nt, t, C.byref(spec), int(max_product_rows),
+                                                                                  C.byref(h)))
+        super().__init__(h, keep)
+        self._bridge = bridge
+
+
+def precompile_nested_loop_filter(probe_types, build_types, filter_expr):
+    """Compile the pair filter's kernels into the on-disk cache (no GPU needed).  TgpuError NOT_SUPPORTED for a filter that is not fused."""
+    spec, keep = FlatProgram(filter_expr, []).to_c()
+    pt, npt = _i32(probe_types)
+    bt, nbt = _i32(build_types)
+    _lib.check(_lib.lib().tgpu_precompile_nested_loop_filter(npt, pt, nbt, bt, C.byref(spec)))
+
+
+def nested_loop_filter_source(probe_types, build_types, filter_expr):
+    """The generated source of the pair filter (tg_pair_filter, nlj_pair_count, nlj_pair_emit).  TgpuError NOT_SUPPORTED, with the reason
+    as its message, for a filter that takes the unfused route."""
+    spec, keep = FlatProgram(filter_expr, []).to_c()
+    pt, npt = _i32(probe_types)
+    bt, nbt = _i32(build_types)
+    L = _lib.lib()
+    need = _lib.check(L.tgpu_nested_loop_filter_source(npt, pt, nbt, bt, C.byref(spec), None, 0))
+    buf = C.create_string_buffer(int(need))
+    L.tgpu_nested_loop_filter_source(npt, pt, nbt, bt, C.byref(spec), buf, need)
+    return buf.value.decode()
+
+
 class MarkDistinctOperatorFactory(OperatorFactory):
     """MarkDistinctOperator.MarkDistinctOperatorFactory (M/operator/MarkDistinctOperator.java:39-92): the input page plus one BOOLEAN
     channel, true on the first row of every value of `mark_distinct_channels` the operator has not seen before."""
