@@ -155,6 +155,56 @@ __global__ void __launch_bounds__(kBlock) scan_one_tile_i32(const int32_t *__res
     if (threadIdx.x == 0 && total_out) *total_out = total;
 }
 
+// up to 16 384 elements: still one launch -- one workgroup of 1 024 lanes, 16 consecutive elements per lane (four 16-byte loads where
+// the array is 16-byte aligned), every load issued before the first add; a wave scan, then every wave scans the 16 wave totals from
+// LDS itself.  (The three-launch route takes 11-16 us at these sizes -- the per-step scans of the filter's tile counts and of the
+// fused probe's chunk counts -- for a few microseconds of work.)  A lane stores only where it loaded, so in == out is fine.
+constexpr int kScanMidBlock = 1024, kScanMidItems = 16, kScanMid = kScanMidBlock * kScanMidItems;
+
+__global__ void __launch_bounds__(kScanMidBlock) scan_mid_i32(const int32_t *__restrict__ in, int32_t *__restrict__ out, int64_t n, int64_t *total_out)
+{
+    __shared__ int64_t wave_total[kScanMidBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0, out_aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const int64_t base = (int64_t)threadIdx.x * kScanMidItems;
+    int32_t v[kScanMidItems];
+#pragma unroll
+    for (int q = 0; q < kScanMidItems; q += 4) {
+        if (aligned && base + q + 4 <= n) {
+            const int4 a = *reinterpret_cast<const int4 *>(in + base + q);
+            v[q] = a.x; v[q + 1] = a.y; v[q + 2] = a.z; v[q + 3] = a.w;
+        } else {
+#pragma unroll
+            for (int i = q; i < q + 4; i++) v[i] = base + i < n ? in[base + i] : 0;
+        }
+    }
+    int64_t s = 0;
+#pragma unroll
+    for (int i = 0; i < kScanMidItems; i++) s += v[i];
+    const int64_t inc = wave_inclusive_scan<int64_t>(s);
+    if (lane == 63) wave_total[wave] = inc;
+    __syncthreads();
+    const int64_t t = lane < kScanMidBlock / 64 ? wave_total[lane] : 0;
+    const int64_t tinc = wave_inclusive_scan<int64_t>(t);
+    int64_t prefix = __shfl(tinc - t, wave, 64) + inc - s;
+    int32_t o[kScanMidItems];
+#pragma unroll
+    for (int i = 0; i < kScanMidItems; i++) {
+        o[i] = (int32_t)prefix;
+        prefix += v[i];
+    }
+#pragma unroll
+    for (int q = 0; q < kScanMidItems; q += 4) {
+        if (out_aligned && base + q + 4 <= n) *reinterpret_cast<int4 *>(out + base + q) = make_int4(o[q], o[q + 1], o[q + 2], o[q + 3]);
+        else {
+#pragma unroll
+            for (int i = q; i < q + 4; i++)
+                if (base + i < n) out[base + i] = o[i];
+        }
+    }
+    if (threadIdx.x == kScanMidBlock - 1 && total_out) *total_out = tinc;   // lanes past the 16 totals add 0: the last lane holds the sum
+}
+
 void exclusive_scan_i32(Context *ctx, const int32_t *in, int32_t *out, int64_t n, int64_t *total_dev)
 {
     if (n <= 0) {
@@ -163,6 +213,11 @@ void exclusive_scan_i32(Context *ctx, const int32_t *in, int32_t *out, int64_t n
     }
     if (n <= kScanTile) {
         scan_one_tile_i32<<<1, kBlock, 0, ctx->stream()>>>(in, out, n, total_dev);
+        check_launch("exclusive_scan_i32");
+        return;
+    }
+    if (n <= kScanMid) {
+        scan_mid_i32<<<1, kScanMidBlock, 0, ctx->stream()>>>(in, out, n, total_dev);
         check_launch("exclusive_scan_i32");
         return;
     }

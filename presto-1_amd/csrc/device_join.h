@@ -32,7 +32,9 @@ struct TgPrefilter {
     // plus the set bits below the key's own bit) indexes direct[], the build positions in key order.  Both side arrays are
     // dense: 4 bytes per 64 key values + 4 bytes per build row, whatever the spread of the keys.
     const int *direct;      // nullptr with rank_base set: build positions ARE the ranks (build side in strictly ascending key order)
-    const int *rank_base;   // non-null = DIRECT layout
+    const int *rank_base;   // non-null = DIRECT layout.  With direct == nullptr an entry is defined only where bitmap[word] != 0 (the
+                            // build pass writes it from the first row of the word's run, join.hip build_direct_kernel): read it for a
+                            // key whose bit is set, or speculatively and unused -- never sum or scan the array
 };
 
 // DIRECT layout: build position of the present key at offset d = key - key_min, `word` = its bitmap word

@@ -83,7 +83,8 @@ public:
     // they emitted; unvisited_positions = OuterPositionIterator, every build position nobody matched, ascending
     void mark_visited(const int32_t *build_positions, int64_t n);
     // DIRECT layout: the rank structure (rank_base + positions in key order) is built on first demand when the table has no output
-    // channels; everything that reads build positions calls this first
+    // channels; everything that reads build positions calls this first.  (Nothing to do for a build side in strictly ascending key
+    // order: its build pass wrote rank_base already.)
     void ensure_rank() const;
     void unvisited_positions(BufferPtr &positions, int64_t &count);
 
@@ -105,7 +106,9 @@ private:
     int64_t bloom_words_ = 0;
     BufferPtr bitmap_;           // fast path: exact bitmap over [key_min_, key_max_] (dense key domains)
     BufferPtr direct_;           // fast path, DIRECT layout: int32 build positions in key order (no hash table)
-    BufferPtr rank_base_;        //   present keys in front of every bitmap word (device_join.h tg_direct_position)
+    BufferPtr rank_base_;        //   present keys in front of every bitmap word (device_join.h tg_direct_position).  A build side in
+                                 //   strictly ascending key order writes it from the build pass (the first row of every word's run), and
+                                 //   then an entry is DEFINED ONLY WHERE THE BITMAP WORD IS NOT 0: nothing may sum or scan the array
     long long key_min_ = 0, key_max_ = -1;
     BufferPtr tags_;             // uint8[n]                           (PagesHash.positionToHashes)
     BufferPtr links_;            // int32[n] or empty when no duplicates (ArrayPositionLinks)

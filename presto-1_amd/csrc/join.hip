@@ -334,15 +334,57 @@ __global__ void __launch_bounds__(kBlock) links_kernel(const unsigned long long 
 
 // DIRECT layout, step 1: smallest / largest non-null key; minmax[2] is set when some key is not larger than its predecessor
 // (it stays 0 for a build side in strictly ascending key order: no repeated key, and a key's rank is its build position)
+// Few, long-running blocks: every block ends in two atomics on the same two words, which serialise in L2 -- so the bytes in
+// flight come from the width and the number of the loads per lane, not from the grid.
+// A BIGINT column without a null vector whose base is 16-byte aligned is read as pairs of rows, U independent 16-byte loads per
+// lane and iteration (the rows of one wave-wide load are consecutive: 128 of them); the scalar loop behind it takes the odd
+// last row of such a column and every other column (INTEGER / DATE keys, null vectors, a base that is 8 mod 16).  Every
+// adjacent pair of rows is compared exactly once: the halves of a load inside the lane, a lane's first row with the previous
+// lane's second, the first lane's first row with the row in front of the wave's load (a load of its own: `before`).
+// Measured on 3.0 M and 14.6 M keys (DESIGN.md section 5 "Ascending builds"): 8 loads from ONE workgroup per CU -- the atomics
+// cost about 10 ns each, 2 / 4 workgroups per CU took 5 / 16 us longer, 16 loads were no faster, 4 and 2 slower.
+constexpr int kRangeLoads = 8, kRangeBlocksPerCu = 1;
+
+template <int U>
 __global__ void __launch_bounds__(kBlock) key_range_kernel(ColView key, int64_t n, long long *minmax)
 {
-    long long lo = 0x7fffffffffffffffLL, hi = -0x7fffffffffffffffLL - 1;
+    constexpr long long kMin = -0x7fffffffffffffffLL - 1;
+    long long lo = 0x7fffffffffffffffLL, hi = kMin;
     bool descent = false;
-    // four independent loads per lane and iteration; few, long-running blocks: every block ends in two atomics on the same
-    // two words, which serialise in L2
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     const int lane = threadIdx.x & 63;
-    for (int64_t r0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; r0 < n; r0 += 4 * stride) {
+    const bool wide = key.type == TGPU_BIGINT && key.nulls == nullptr && (reinterpret_cast<uintptr_t>(key.values) & 15) == 0;
+    const int64_t pairs = wide ? n / 2 : 0;
+    if (wide) {
+        const longlong2 *__restrict__ kv = (const longlong2 *)key.values;
+        const long long *__restrict__ ks = (const long long *)key.values;
+        for (int64_t p0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; p0 < pairs; p0 += U * stride) {
+            longlong2 k[U];
+            long long before[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {   // loads only
+                const int64_t p = p0 + u * stride, pc = p < pairs ? p : p0;
+                k[u] = kv[pc];
+                // the row in front of the wave's load, loaded by every lane (one address, one request) and without a condition:
+                // a branch around a load puts a wait in front of the loads behind it
+                const int64_t first = pc - lane;
+                before[u] = ks[first > 0 ? 2 * first - 1 : 0];
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int64_t p = p0 + u * stride;
+                const bool live = p < pairs;
+                const long long a = k[u].x < k[u].y ? k[u].x : k[u].y, z = k[u].x < k[u].y ? k[u].y : k[u].x;
+                lo = (live && a < lo) ? a : lo;
+                hi = (live && z > hi) ? z : hi;
+                const long long up = __shfl_up(k[u].y, 1, 64);
+                const long long pred = lane == 0 ? before[u] : up;
+                descent |= live & ((k[u].x >= k[u].y) | ((p > 0) & (pred >= k[u].x)));   // (no short circuit: no branches between the waits)
+            }
+        }
+    }
+    // four independent loads per lane and iteration
+    for (int64_t r0 = 2 * pairs + (int64_t)blockIdx.x * kBlock + threadIdx.x; r0 < n; r0 += 4 * stride) {
         long long k[4], before[4];
         bool live[4];
 #pragma unroll
@@ -352,7 +394,7 @@ __global__ void __launch_bounds__(kBlock) key_range_kernel(ColView key, int64_t 
             const int64_t rc = live[u] ? r : r0;
             live[u] = live[u] && !(key.nulls && key.nulls[rc]);
             k[u] = int_key_at(key, rc);
-            before[u] = (lane == 0 && r < n && r > 0) ? int_key_at(key, r - 1) : (-0x7fffffffffffffffLL - 1);
+            before[u] = (lane == 0 && r < n && r > 0) ? int_key_at(key, r - 1) : kMin;
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -371,8 +413,14 @@ __global__ void __launch_bounds__(kBlock) key_range_kernel(ColView key, int64_t 
 
 // DIRECT layout, step 2: one pass sets the key's bit in the (zeroed) bitmap.  A bit that was already set means a repeated build
 // key: counted in counters[0]; the caller then drops this layout (position links need the hash table).
+// ASC = the build side is known to be strictly ascending without a null vector (key_range_kernel): no key repeats, so nothing is
+// counted and the atomic's result is unused (counters is not touched); and a key's rank is its row, so the first row of every
+// run of rows that share a bitmap word stores rank_base[word] = row -- the number of present keys in front of the word.  A run
+// that straddles a wave, a workgroup or a grid-stride iteration is written by its first row only: the wave's first lane looks
+// at the row in front of it.  Words without a key are never written.
+template <bool ASC>
 __global__ void __launch_bounds__(kBlock) build_direct_kernel(ColView key, int64_t n, long long key_min, unsigned long long *bitmap,
-                                                               unsigned long long *counters)
+                                                               unsigned long long *counters, int32_t *__restrict__ rank_base)
 {
     // Neighbouring rows often fall into the same bitmap word (build sides clustered by key: consecutive customer keys share one
     // word, TPCH order keys every other one): the lanes of a contiguous run with the same word OR their bits together first and
@@ -381,12 +429,14 @@ __global__ void __launch_bounds__(kBlock) build_direct_kernel(ColView key, int64
     unsigned int my_dups = 0;
     for (int64_t base = (int64_t)blockIdx.x * kBlock; base < n; base += (int64_t)gridDim.x * kBlock) {
         const int64_t r = base + threadIdx.x;
-        const bool active = r < n && !(key.nulls && key.nulls[r]);   // PagesHash.java:94-96: rows with a null key are not indexed
+        const bool active = r < n && (ASC || !(key.nulls && key.nulls[r]));   // PagesHash.java:94-96: rows with a null key are not indexed
         unsigned long long d = 0;
         if (active) {
             d = (unsigned long long)int_key_at(key, r) - (unsigned long long)key_min;
         }
         const unsigned int word = active ? (unsigned int)(d >> 6) : 0xffffffffu;
+        unsigned int word_before = 0xffffffffu;   // ASC, first lane: the word of the row in front of the wave's rows (no such row: no word)
+        if (ASC && lane == 0 && active && r > 0) word_before = (unsigned int)(((unsigned long long)int_key_at(key, r - 1) - (unsigned long long)key_min) >> 6);
         unsigned long long bits = active ? (1ULL << (d & 63)) : 0ULL;
         unsigned int rows = active ? 1u : 0u;
         const unsigned int word_prev = __shfl_up(word, 1, 64);
@@ -404,11 +454,18 @@ __global__ void __launch_bounds__(kBlock) build_direct_kernel(ColView key, int64
             }
         }
         if (head && active) {
-            const unsigned long long old = atomicOr(&bitmap[word], bits);
-            // repeated build keys: a bit that was already set, or two rows of the run with the same bit
-            my_dups += (unsigned int)__popcll(old & bits) + (rows - (unsigned int)__popcll(bits));
+            if (ASC) {
+                atomicOr(&bitmap[word], bits);   // stays atomic: a run that straddles waves meets in one word
+                if (lane != 0 || word_before != word) rank_base[word] = (int32_t)r;
+            }
+            else {
+                const unsigned long long old = atomicOr(&bitmap[word], bits);
+                // repeated build keys: a bit that was already set, or two rows of the run with the same bit
+                my_dups += (unsigned int)__popcll(old & bits) + (rows - (unsigned int)__popcll(bits));
+            }
         }
     }
+    if (ASC) return;
     __shared__ unsigned int s_dups[kBlock / 64];
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) my_dups += __shfl_down(my_dups, d, 64);
@@ -894,8 +951,9 @@ void LookupSourceGpu::build()
 // order, addressed by the key's rank among the present keys (rank_base[word] + popcount of the lower bits of the word): the
 // build is one atomicOr per row, a scan over the bitmap words and one dense store per row (no probing, no key comparison, no
 // write amplification from scattering 4-byte entries over the key range); a probe is a bit test, and only a MATCH pays the two
-// further loads; inputs clustered by key walk all three arrays front to back.  Returns false (nothing kept) when the keys do
-// not qualify; the hash table is built then.
+// further loads; inputs clustered by key walk all three arrays front to back.  (A build side in strictly ascending key order
+// needs neither the scan nor the store per row: position = rank, and the build pass writes rank_base from the run heads.)
+// Returns false (nothing kept) when the keys do not qualify; the hash table is built then.
 bool LookupSourceGpu::build_direct(const KeyCols &keys)
 {
     const int g = grid_for(ctx_, n_);
@@ -905,7 +963,15 @@ bool LookupSourceGpu::build_direct(const KeyCols &keys)
     long long host_mm[3];
     {
         ProfileScope ps(ctx_, "join_build_range");
-        key_range_kernel<<<std::min(g, ctx_->cu_count() * 2), kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, mm->as<long long>());
+        // kernel study: TGPU_KEY_RANGE_LOADS (16-byte loads per lane and iteration: 2, 4, 8, 16) and TGPU_KEY_RANGE_BLOCKS (workgroups per CU)
+        const char *loads_env = getenv("TGPU_KEY_RANGE_LOADS"), *blocks_env = getenv("TGPU_KEY_RANGE_BLOCKS");
+        const int loads = loads_env ? atoi(loads_env) : kRangeLoads;
+        const int grid = std::min(g, ctx_->cu_count() * (blocks_env ? std::min(std::max(atoi(blocks_env), 1), 8) : kRangeBlocksPerCu));
+        long long *out = mm->as<long long>();
+        if (loads == 2) key_range_kernel<2><<<grid, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, out);
+        else if (loads == 4) key_range_kernel<4><<<grid, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, out);
+        else if (loads == 16) key_range_kernel<16><<<grid, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, out);
+        else key_range_kernel<kRangeLoads><<<grid, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, out);
         check_launch("key_range");
     }
     ctx_->download(host_mm, mm->ptr(), 24);
@@ -919,22 +985,34 @@ bool LookupSourceGpu::build_direct(const KeyCols &keys)
     BufferPtr bitmap = ctx_->alloc_zero((size_t)words * 8);
     BufferPtr direct = ascending ? nullptr : ctx_->alloc((size_t)n_ * 4);
     BufferPtr rank_base = ctx_->alloc((size_t)words * 4);
-    BufferPtr counters = ctx_->alloc_zero(16);
-    {
+    // ascending: the build pass itself leaves rank_base behind (the first row of every word's run stores its row number), for the
+    // words that hold a key -- nothing reads the others.  TGPU_DIRECT_RANK_FROM_HEADS=0 (tests, kernel studies) keeps the
+    // popcount + scan of ensure_rank for such a table.
+    const char *from_heads_env = getenv("TGPU_DIRECT_RANK_FROM_HEADS");
+    const bool rank_from_heads = ascending && !(from_heads_env && atoi(from_heads_env) == 0);
+    if (rank_from_heads) {
         ProfileScope ps(ctx_, "join_build_insert");
-        build_direct_kernel<<<g, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, host_mm[0], bitmap->as<unsigned long long>(), counters->as<unsigned long long>());
+        build_direct_kernel<true><<<g, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, host_mm[0], bitmap->as<unsigned long long>(), nullptr, rank_base->as<int32_t>());
         check_launch("build_direct");
     }
-    if (!ascending && ctx_->read_scalar(counters->as<unsigned long long>()) != 0) return false;   // repeated build keys: position links needed
+    else {
+        BufferPtr counters = ctx_->alloc_zero(16);
+        {
+            ProfileScope ps(ctx_, "join_build_insert");
+            build_direct_kernel<false><<<g, kBlock, 0, ctx_->stream()>>>(keys.c[0], n_, host_mm[0], bitmap->as<unsigned long long>(), counters->as<unsigned long long>(), nullptr);
+            check_launch("build_direct");
+        }
+        if (!ascending && ctx_->read_scalar(counters->as<unsigned long long>()) != 0) return false;   // repeated build keys: position links needed
+    }
     key_min_ = host_mm[0];
     key_max_ = host_mm[1];
     bitmap_ = bitmap;
     direct_ = direct;
     rank_base_ = rank_base;
     direct_key_ = keys.c[0];
-    rank_pending_ = true;
-    // a table without output channels is usually probed for membership only (the build side of a semi-join-like filter, Q3's
-    // customer table): the rank structure is then built on first demand (ensure_rank), i.e. normally never
+    rank_pending_ = !rank_from_heads;
+    // a table without output channels is usually probed for membership only (the build side of a semi-join-like filter): where
+    // the rank structure is still pending it is then built on first demand (ensure_rank), i.e. normally never
     if (!output_channels_.empty()) ensure_rank();
     return true;
 }
