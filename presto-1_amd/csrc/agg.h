@@ -37,7 +37,8 @@ public:
 
     // raw input (SINGLE / PARTIAL): gids == nullptr means one global group 0
     // gids_ascending: the caller knows that the ids never decrease from row to row (the group-by's run route): the ORDERED mode then
-    // skips its own check of that, and the read-back the check costs
+    // skips its own check of that, and the read-back the check costs, and (no id is negative on that route) accumulates from the ids
+    // themselves, without the (key, row) lists (agg.hip agg_ordered_runs_kernel; TGPU_AGG_RUN_ORDERED=0 keeps the lists)
     void add_input(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending = false);
     // intermediate input (FINAL): aggregate k reads its state from channel spec.input_channel (count) and, for sum / avg,
     // spec.input_channel + 1 (sum)
@@ -59,7 +60,7 @@ public:
     // (group id + 1, row) pairs in (group, row) order -- the caller then adds the rows of every group in that order.
     bool begin_ordered(const int32_t *gids, int64_t n, int64_t groups, int64_t lowcard_max_groups, BufferPtr &keys, BufferPtr &rows);
     // the chained kernels' input: {first, end} index of every group id's stretch of the sorted keys (ids pairs of int32; {0, 0} = no rows)
-    BufferPtr group_stretches(const unsigned int *keys, int64_t n, int64_t ids);
+    BufferPtr group_stretches(const unsigned int *keys, int64_t n, int64_t ids, const int32_t *ascending_gids = nullptr);   // keys == nullptr: key(i) = ascending_gids[i] + 1
     // the JIT-fused accumulate kernels address the exact (limb) state directly: they keep the accumulators out of ORDERED mode
     void set_allow_ordered(bool on) { allow_ordered_ = on; }
     // TGPU_SUM_ORDER_JAVA: ORDERED whatever the number of groups (every group's rows are added in row order)

@@ -104,14 +104,24 @@ __global__ void __launch_bounds__(kBlock) ordered_keys_kernel(const int32_t *__r
     if (unsorted && __any(bad) && (threadIdx.x & 63) == 0) *unsorted = 1u;   // idempotent plain store (null: the caller knows the order)
 }
 
+// The (key, row) lists as the kernels below read them.  Group ids that ascend with the rows and exclude none (the group-by's run route) need
+// no lists: with keys == nullptr the key of index i is gids[i] + 1 and its row is i.
+struct OrdOrder {
+    const unsigned int *keys;
+    const int *rows;
+    const int32_t *gids;
+    __device__ __forceinline__ unsigned int key(int64_t i) const { return keys ? keys[i] : (unsigned int)(gids[i] + 1); }
+    __device__ __forceinline__ int64_t row(int64_t i) const { return keys ? (int64_t)rows[i] : i; }
+};
+
 // {first, end} of every group's stretch of the sorted keys (the words start at 0)
-__global__ void __launch_bounds__(kBlock) ordered_stretches_kernel(const unsigned int *__restrict__ keys, int64_t n, int *__restrict__ stretches)
+__global__ void __launch_bounds__(kBlock) ordered_stretches_kernel(OrdOrder ord, int64_t n, int *__restrict__ stretches)
 {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const unsigned int k = keys[i];
+        const unsigned int k = ord.key(i);
         if (k == 0) continue;
-        if (i == 0 || keys[i - 1] != k) stretches[(size_t)(k - 1) * 2] = (int)i;
-        if (i == n - 1 || keys[i + 1] != k) stretches[(size_t)(k - 1) * 2 + 1] = (int)(i + 1);
+        if (i == 0 || ord.key(i - 1) != k) stretches[(size_t)(k - 1) * 2] = (int)i;
+        if (i == n - 1 || ord.key(i + 1) != k) stretches[(size_t)(k - 1) * 2 + 1] = (int)(i + 1);
     }
 }
 
@@ -202,7 +212,7 @@ __device__ inline long long wave_sum_i64(long long v)
     return v;
 }
 
-__device__ inline void ordered_chain_group(const AggArgs &args, const OrdChainPlan &plan, const int *__restrict__ rows, int64_t g, long long s, long long e, double *vals,
+__device__ inline void ordered_chain_group(const AggArgs &args, const OrdChainPlan &plan, const OrdOrder &ord, int64_t g, long long s, long long e, double *vals,
                                            unsigned long long *cnt_lds, unsigned long long *lo_lds, long long *hi_lds)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -222,12 +232,12 @@ __device__ inline void ordered_chain_group(const AggArgs &args, const OrdChainPl
     __syncthreads();
     const long long tiles = (e - s + TG_ORD_TILE - 1) / TG_ORD_TILE;
     const int r = (wave - 1) * 64 + lane;
-    long long row_next = (wave > 0 && s + r < e) ? rows[s + r] : 0;
+    long long row_next = (wave > 0 && s + r < e) ? ord.row(s + r) : 0;
     for (long long t = 0; t <= tiles; t++) {
         if (wave > 0 && t < tiles) {
             const long long j = s + t * TG_ORD_TILE + r;
             const long long row = row_next;
-            if (j + TG_ORD_TILE < e) row_next = rows[j + TG_ORD_TILE];
+            if (j + TG_ORD_TILE < e) row_next = ord.row(j + TG_ORD_TILE);
             double *out = vals + (t & 1) * (TG_ORD_MAX_DOUBLES * TG_ORD_STRIDE) + r;
             const bool live = j < e;
 #pragma unroll
@@ -284,8 +294,7 @@ __device__ inline void ordered_chain_group(const AggArgs &args, const OrdChainPl
 }
 
 // stretches: workgroup b = group b (every group of the page); else the workgroups share the list the lane-per-group kernel handed over
-__global__ void __launch_bounds__(TG_ORD_WAVES * 64) agg_ordered_chain_kernel(AggArgs args, OrdChainPlan plan, const int *__restrict__ stretches,
-                                                                               const unsigned int *__restrict__ keys, const int *__restrict__ rows, int64_t n,
+__global__ void __launch_bounds__(TG_ORD_WAVES * 64) agg_ordered_chain_kernel(AggArgs args, OrdChainPlan plan, const int *__restrict__ stretches, OrdOrder ord, int64_t n,
                                                                                const long long *__restrict__ list, const unsigned int *__restrict__ list_count)
 {
     __shared__ __attribute__((aligned(16))) double vals[2 * TG_ORD_MAX_DOUBLES * TG_ORD_STRIDE];
@@ -293,15 +302,230 @@ __global__ void __launch_bounds__(TG_ORD_WAVES * 64) agg_ordered_chain_kernel(Ag
     __shared__ long long hi_lds[kMaxAggs];
     if (stretches) {
         const long long s = stretches[(size_t)blockIdx.x * 2], e = stretches[(size_t)blockIdx.x * 2 + 1];
-        if (e > s) ordered_chain_group(args, plan, rows, blockIdx.x, s, e, vals, cnt_lds, lo_lds, hi_lds);
+        if (e > s) ordered_chain_group(args, plan, ord, blockIdx.x, s, e, vals, cnt_lds, lo_lds, hi_lds);
         return;
     }
     const unsigned int count = *list_count;
     for (unsigned int b = blockIdx.x; b < count; b += gridDim.x) {
         const long long g = list[(size_t)b * 2], s = list[(size_t)b * 2 + 1];
         long long lo = s, hi = n;            // the end of the group's stretch: first index whose key is larger
-        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (keys[mid] <= (unsigned int)(g + 1)) lo = mid + 1; else hi = mid; }
-        if (lo > s) ordered_chain_group(args, plan, rows, g, s, lo, vals, cnt_lds, lo_lds, hi_lds);
+        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (ord.key(mid) <= (unsigned int)(g + 1)) lo = mid + 1; else hi = mid; }
+        if (lo > s) ordered_chain_group(args, plan, ord, g, s, lo, vals, cnt_lds, lo_lds, hi_lds);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// ORDERED mode straight from ascending group ids (the group-by's run route: no row excluded, a group's rows are one run).  The result is
+// agg_ordered_kernel<false>'s -- one lane walks a run in row order and read-modify-writes the group's state -- but the rows reach the walk
+// through LDS and the runs reach the lanes evenly.  A workgroup takes tiles of kOrdRunTile consecutive rows:
+//   stage    every lane loads the ids of its kOrdRunIters rows and of the rows in front of them and, per aggregate, input cells / null
+//            bytes / mask bytes (lane-consecutive, unconditional -- a row beyond the page reads the page's last row -- and a channel's
+//            presence a uniform branch around its eight loads: all loads of an aggregate are in flight before the first use).  Per row it
+//            leaves an 8-byte addend per valued aggregate and one "counted" bit per aggregate; a row an aggregate skips travels as the
+//            identity of its update: -0.0 (DOUBLE sums), 0 (BIGINT sums, min / max codes).
+//   compact  the rows that start a run (row i with i == 0 or gid[i - 1] != gid[i]) are listed in row order: ballot per wave, the 32 wave
+//            counts through LDS.  A tile's leading rows that continue the run of the tile before start none and belong to that run's lane.
+//   walk     lane t takes runs t, t + 256, ...: every lane has work although only ~38 % of Q3's rows start a run, and a run ends where the
+//            next one starts (no search).  The stored sums of all aggregates are loaded before the first walk; the addends come from LDS
+//            kOrdRunChunk rows at a time (the reads in flight together, the adds in row order), past the tile's end from the global
+//            arrays; at most `handoff` rows, the rest goes to the chain kernel as in agg_ordered_kernel.
+// LDS: kOrdRunTile x 8 B per valued aggregate + 16,608 B (ids, counted bits, run list, wave counts): kOrdRunStaged = 3 valued aggregates
+// are 65,760 B, two workgroups per CU (the launch asks for what its aggregates need: one is 32,992 B, four workgroups per CU).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kOrdRunIters = 8, kOrdRunTile = kBlock * kOrdRunIters, kOrdRunStaged = 3, kOrdRunChunk = 8;
+constexpr size_t kOrdRunFixedLds = 64 + 2 * (size_t)(kOrdRunTile + 8) * 2 + (size_t)kOrdRunTile * 4 + 32 * 4;
+static_assert(kOrdHandoffRows >= kOrdRunTile, "a walk that is handed over ends beyond its tile");
+
+struct OrdRunPlan {
+    int32_t slot[kMaxAggs];   // aggregate -> its addend plane in LDS, or -1 (counts need the bit only)
+    int32_t staged, pad;
+};
+
+// the 8 bytes row r adds to aggregate a: `take` = the row counts (mask and null byte looked at by the caller)
+__device__ __forceinline__ unsigned long long ord_run_addend(int function, unsigned long long raw, bool take)
+{
+    switch (function) {
+    case TGPU_AGG_SUM_BIGINT: return take ? raw : 0ULL;
+    case TGPU_AGG_MIN_BIGINT:
+    case TGPU_AGG_MAX_BIGINT:
+    case TGPU_AGG_MIN_DOUBLE:
+    case TGPU_AGG_MAX_DOUBLE: return take ? tg_minmax_encode(function, raw) : 0ULL;
+    case TGPU_AGG_AVG_BIGINT: return take ? (unsigned long long)__double_as_longlong((double)(long long)raw) : 0x8000000000000000ULL;
+    default: return take ? raw : 0x8000000000000000ULL;   // SUM_DOUBLE / AVG_DOUBLE: -0.0
+    }
+}
+
+enum { kOrdCount = 0, kOrdDouble = 1, kOrdBig = 2, kOrdMinMax = 3 };
+
+// rows [j, e) of the tile into one aggregate's running values, in row order
+template <int KIND>
+__device__ __forceinline__ void ord_run_walk(const unsigned long long *v, const unsigned short *cnt_lds, int k, int j, int e, int &cnt, double &s, __int128 &big,
+                                             unsigned long long &best)
+{
+    for (int jj = j; jj < e; jj += kOrdRunChunk) {
+        unsigned short c[kOrdRunChunk];
+        unsigned long long x[kOrdRunChunk];
+#pragma unroll
+        for (int u = 0; u < kOrdRunChunk; u++) {   // (up to kOrdRunChunk - 1 entries past the run, the tile or the plane: read, never used)
+            c[u] = cnt_lds[jj + u];
+            x[u] = KIND == kOrdCount ? 0ULL : v[jj + u];
+        }
+#pragma unroll
+        for (int u = 0; u < kOrdRunChunk; u++) {
+            const bool in = jj + u < e;
+            cnt += in ? (c[u] >> k) & 1 : 0;
+            if (KIND == kOrdDouble) s = in ? s + __longlong_as_double((long long)x[u]) : s;
+            if (KIND == kOrdBig) big += in ? (long long)x[u] : 0LL;
+            if (KIND == kOrdMinMax) best = (in && x[u] > best) ? x[u] : best;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) agg_ordered_runs_kernel(AggArgs args, OrdRunPlan plan, const int32_t *__restrict__ gids, int64_t n, int64_t handoff,
+                                                                   long long *list, unsigned int *list_count)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    unsigned long long *val_lds = (unsigned long long *)lds;                                           // [plane][kOrdRunTile], then 64 B
+    unsigned short *cnt_lds = (unsigned short *)(lds + (size_t)plan.staged * kOrdRunTile * 8 + 64);    // bit k: row j counts for aggregate k
+    unsigned short *head_lds = cnt_lds + kOrdRunTile + 8;                                              // row of the h-th run's first row; [runs] = m
+    int32_t *gid_lds = (int32_t *)(head_lds + kOrdRunTile + 8);
+    int *wave_lds = (int *)(gid_lds + kOrdRunTile);                                                    // runs that start in (it, wave)'s 64 rows
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t tiles = (n + kOrdRunTile - 1) / kOrdRunTile;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t base = t * kOrdRunTile;
+        const int m = (int)(n - base < kOrdRunTile ? n - base : kOrdRunTile);
+        // ---- stage ----
+        int32_t gid[kOrdRunIters], before[kOrdRunIters];
+        unsigned int counted[kOrdRunIters];
+        int64_t row[kOrdRunIters];
+#pragma unroll
+        for (int it = 0; it < kOrdRunIters; it++) {
+            const int j = it * kBlock + threadIdx.x;
+            row[it] = base + (j < m ? j : m - 1);
+            gid[it] = gids[row[it]];
+            before[it] = gids[row[it] > 0 ? row[it] - 1 : 0];
+            counted[it] = 0;
+        }
+#pragma unroll
+        for (int k = 0; k < kMaxAggs; k++) {   // constant indices into the by-value argument block (no scratch copy)
+            if (k >= args.n_aggs) break;
+            const AggView &a = args.a[k];
+            const int slot = plan.slot[k];
+            unsigned long long raw[kOrdRunIters];
+            uint8_t mk[kOrdRunIters], mkn[kOrdRunIters], inn[kOrdRunIters];
+#pragma unroll
+            for (int it = 0; it < kOrdRunIters; it++) {
+                raw[it] = 0ULL;
+                mk[it] = 1;
+                mkn[it] = 0;
+                inn[it] = 0;
+            }
+            if (slot >= 0) {
+#pragma unroll
+                for (int it = 0; it < kOrdRunIters; it++) raw[it] = ((const unsigned long long *)a.input)[row[it]];
+            }
+            if (a.mask) {
+#pragma unroll
+                for (int it = 0; it < kOrdRunIters; it++) mk[it] = a.mask[row[it]];
+            }
+            if (a.mask && a.mask_nulls) {
+#pragma unroll
+                for (int it = 0; it < kOrdRunIters; it++) mkn[it] = a.mask_nulls[row[it]];
+            }
+            if (a.function != TGPU_AGG_COUNT_ALL && a.input_nulls) {
+#pragma unroll
+                for (int it = 0; it < kOrdRunIters; it++) inn[it] = a.input_nulls[row[it]];
+            }
+#pragma unroll
+            for (int it = 0; it < kOrdRunIters; it++) {
+                const bool take = (mk[it] != 0) & (mkn[it] == 0) & (inn[it] == 0);
+                counted[it] |= (take ? 1u : 0u) << k;
+                if (slot >= 0) val_lds[(size_t)slot * kOrdRunTile + it * kBlock + threadIdx.x] = ord_run_addend(a.function, raw[it], take);
+            }
+        }
+        // ---- compact ----
+        int rank[kOrdRunIters];   // among the runs that start in this wave's 64 rows of `it`, or -1
+#pragma unroll
+        for (int it = 0; it < kOrdRunIters; it++) {
+            const int j = it * kBlock + threadIdx.x;
+            cnt_lds[j] = (unsigned short)counted[it];   // (rows beyond the page: never used)
+            gid_lds[j] = gid[it];
+            const bool head = j < m && (base + j == 0 || before[it] != gid[it]);
+            const unsigned long long heads = __ballot(head);
+            rank[it] = head ? __popcll(heads & ((1ULL << lane) - 1ULL)) : -1;
+            if (lane == 0) wave_lds[it * (kBlock / 64) + wave] = __popcll(heads);
+        }
+        __syncthreads();
+        int runs = 0;
+#pragma unroll
+        for (int w = 0; w < kOrdRunIters * (kBlock / 64); w++) {   // (the same 32 words for every lane: broadcast reads)
+            if ((w & 3) == wave) {                                   // (wave is uniform: a scalar branch)
+                const int it = w >> 2;
+                if (rank[it] >= 0) head_lds[runs + rank[it]] = (unsigned short)(it * kBlock + threadIdx.x);
+            }
+            runs += wave_lds[w];
+        }
+        if (threadIdx.x == 0) head_lds[runs] = (unsigned short)m;
+        __syncthreads();
+        // ---- walk ----
+        for (int h = threadIdx.x; h < runs; h += kBlock) {
+            const int j = head_lds[h], e = head_lds[h + 1];
+            const int32_t g32 = gid_lds[j];
+            const int64_t g = g32, i = base + j;
+            double start[kMaxAggs];   // the group's stored sums, every aggregate's load in flight before the first walk
+#pragma unroll
+            for (int k = 0; k < kMaxAggs; k++) {
+                start[k] = 0.0;
+                if (k < args.n_aggs && args.a[k].dsum) start[k] = args.a[k].dsum[g];
+            }
+            const int64_t stop = handoff > 0 ? (i + handoff < n ? i + handoff : n) : n;   // (the walk ends there at the latest: beyond the tile)
+            int64_t ge = base + e;                                                        // the run's end in the page
+            if (e == m)
+                while (ge < stop && gids[ge] == g32) ge++;
+            if (handoff > 0 && ge == stop && stop < n && gids[stop] == g32) {
+                const unsigned int at = atomicAdd(list_count, 1u);
+                list[(size_t)at * 2] = g;
+                list[(size_t)at * 2 + 1] = stop;
+            }
+#pragma unroll
+            for (int k = 0; k < kMaxAggs; k++) {
+                if (k >= args.n_aggs) break;
+                const AggView &a = args.a[k];
+                const int slot = plan.slot[k];
+                const unsigned long long *v = val_lds + (size_t)(slot >= 0 ? slot : 0) * kOrdRunTile;
+                int c = 0;
+                double s = start[k];
+                __int128 big = 0;
+                unsigned long long best = 0;   // min / max: the best code among the rows walked (0 = none)
+                if (slot < 0) ord_run_walk<kOrdCount>(v, cnt_lds, k, j, e, c, s, big, best);
+                else if (a.function == TGPU_AGG_SUM_BIGINT) ord_run_walk<kOrdBig>(v, cnt_lds, k, j, e, c, s, big, best);
+                else if (tg_is_minmax(a.function)) ord_run_walk<kOrdMinMax>(v, cnt_lds, k, j, e, c, s, big, best);
+                else ord_run_walk<kOrdDouble>(v, cnt_lds, k, j, e, c, s, big, best);
+                long long cnt = c;
+                for (int64_t r = base + e; r < ge; r++) {   // past the tile: from the global arrays, as agg_ordered_kernel<false> reads them
+                    if (a.mask && ((a.mask_nulls && a.mask_nulls[r]) || !a.mask[r])) continue;
+                    if (a.function != TGPU_AGG_COUNT_ALL && a.input_nulls && a.input_nulls[r]) continue;
+                    cnt++;
+                    if (slot < 0) continue;
+                    const unsigned long long x = ord_run_addend(a.function, ((const unsigned long long *)a.input)[r], true);
+                    if (a.function == TGPU_AGG_SUM_BIGINT) big += (long long)x;
+                    else if (tg_is_minmax(a.function)) best = x > best ? x : best;
+                    else s += __longlong_as_double((long long)x);
+                }
+                // (a group has one run in the page, so one lane: the count goes as an atomic that returns nothing, not as a load and a store)
+                if (cnt) atomicAdd((unsigned long long *)&a.counts[g], (unsigned long long)cnt);
+                if (a.dsum) a.dsum[g] = s;
+                if (best) tg_minmax_update(&a.i128[g * 2], best);
+                if (a.i128 && big != 0) {
+                    const unsigned __int128 cur = ((unsigned __int128)a.i128[g * 2 + 1] << 64) | a.i128[g * 2];
+                    const unsigned __int128 nxt = cur + (unsigned __int128)big;
+                    a.i128[g * 2] = (unsigned long long)nxt;
+                    a.i128[g * 2 + 1] = (unsigned long long)(nxt >> 64);
+                }
+            }
+        }
+        __syncthreads();   // (the next tile of this workgroup overwrites the LDS)
     }
 }
 
@@ -876,10 +1100,10 @@ bool GroupedAccumulators::begin_ordered(const int32_t *gids, int64_t n, int64_t 
     return true;
 }
 
-BufferPtr GroupedAccumulators::group_stretches(const unsigned int *keys, int64_t n, int64_t ids)
+BufferPtr GroupedAccumulators::group_stretches(const unsigned int *keys, int64_t n, int64_t ids, const int32_t *ascending_gids)
 {
     BufferPtr st = ctx_->alloc_zero((size_t)ids * 8);
-    ordered_stretches_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(keys, n, st->as<int>());
+    ordered_stretches_kernel<<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(OrdOrder{keys, nullptr, ascending_gids}, n, st->as<int>());
     check_launch("ordered_stretches");
     return st;
 }
@@ -968,13 +1192,24 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
         const int64_t long_groups = n / kOrdHandoffRows;   // at most this many groups can be that long
         const bool handoff = !chained && long_groups > 0 && doubles <= TG_ORD_MAX_DOUBLES && getenv("TGPU_DISABLE_ORDERED_CHAIN") == nullptr;
         BufferPtr list, list_count;
+        // ids from the group-by's run route ascend and exclude no row: the kernels read them as they are, without the (key, row) lists
+        // (TGPU_AGG_RUN_ORDERED=0: the lists, for tests and kernel studies).  The lane-per-run kernel stages kOrdRunStaged valued
+        // aggregates in LDS; an operator with more keeps the lists.
+        OrdRunPlan run_plan{};
+        for (int k = 0; k < kMaxAggs; k++) run_plan.slot[k] = (k < args.n_aggs && !is_count(args.a[k].function)) ? run_plan.staged++ : -1;
+        const char *run_switch = getenv("TGPU_AGG_RUN_ORDERED");
+        const bool list_free = gids_ascending && getenv("TGPU_ALWAYS_SORT") == nullptr && !(run_switch && atoi(run_switch) == 0) &&
+                               (chained || run_plan.staged <= kOrdRunStaged);
+        OrdOrder ord{nullptr, nullptr, gids};
         {
             ProfileScope ps(ctx_, chained ? "agg_accumulate_ordered_chain" : "agg_accumulate_ordered");
-            sort_rows_by_group(gids, n, group_count, keys, rows, gids_ascending);
+            if (!list_free) {
+                sort_rows_by_group(gids, n, group_count, keys, rows, gids_ascending);
+                ord = OrdOrder{keys->as<unsigned int>(), rows->as<int>(), gids};
+            }
             if (chained) {
-                BufferPtr stretches = group_stretches(keys->as<unsigned int>(), n, ids);
-                agg_ordered_chain_kernel<<<(int)ids, TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(args, plan, stretches->as<int>(), keys->as<unsigned int>(), rows->as<int>(), n,
-                                                                                              nullptr, nullptr);
+                BufferPtr stretches = group_stretches(ord.keys, n, ids, gids);
+                agg_ordered_chain_kernel<<<(int)ids, TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(args, plan, stretches->as<int>(), ord, n, nullptr, nullptr);
                 check_launch("agg_accumulate_ordered_chain");
                 return;
             }
@@ -982,15 +1217,30 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
                 list = ctx_->alloc((size_t)long_groups * 16);
                 list_count = ctx_->alloc_zero(8);
             }
-            agg_ordered_kernel<false><<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(args, keys->as<unsigned int>(), rows->as<int>(), n, error_->as<unsigned int>(),
-                                                                                          handoff ? kOrdHandoffRows : 0, handoff ? list->as<long long>() : nullptr,
-                                                                                          handoff ? list_count->as<unsigned int>() : nullptr);
+            if (list_free) {
+                const size_t lds_bytes = (size_t)run_plan.staged * kOrdRunTile * 8 + kOrdRunFixedLds;
+                static bool attr_set = false;
+                if (!attr_set) {
+                    HIP_CHECK(hipFuncSetAttribute((const void *)agg_ordered_runs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (int)((size_t)kOrdRunStaged * kOrdRunTile * 8 + kOrdRunFixedLds)));
+                    attr_set = true;
+                }
+                int64_t blocks = grid_for(ctx_, n, kOrdRunTile);
+                if (const char *cap = getenv("TGPU_AGG_RUN_MAX_BLOCKS")) blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, atoll(cap)));   // (tests: several tiles per workgroup)
+                agg_ordered_runs_kernel<<<(int)blocks, kBlock, lds_bytes, ctx_->stream()>>>(args, run_plan, gids, n, handoff ? kOrdHandoffRows : 0,
+                                                                                           handoff ? list->as<long long>() : nullptr,
+                                                                                           handoff ? list_count->as<unsigned int>() : nullptr);
+            }
+            else
+                agg_ordered_kernel<false><<<grid_for(ctx_, n), kBlock, 0, ctx_->stream()>>>(args, ord.keys, ord.rows, n, error_->as<unsigned int>(),
+                                                                                              handoff ? kOrdHandoffRows : 0, handoff ? list->as<long long>() : nullptr,
+                                                                                              handoff ? list_count->as<unsigned int>() : nullptr);
             check_launch("agg_accumulate_ordered");
         }
         if (handoff) {   // (a scope of its own, like the fused operator's: a profile tells the two launches apart)
             ProfileScope ps(ctx_, "agg_accumulate_ordered_handoff");
             agg_ordered_chain_kernel<<<(int)std::min<int64_t>(long_groups, ctx_->cu_count()), TG_ORD_WAVES * 64, 0, ctx_->stream()>>>(
-                args, plan, nullptr, keys->as<unsigned int>(), rows->as<int>(), n, list->as<long long>(), list_count->as<unsigned int>());
+                args, plan, nullptr, ord, n, list->as<long long>(), list_count->as<unsigned int>());
             check_launch("agg_accumulate_ordered_handoff");
         }
         return;
