@@ -792,6 +792,52 @@ int32_t tgpu_scan_operator_add_record_cursor(tgpu_operator *op, const tgpu_recor
 /* OperatorStats the scan side feeds (:354-397): positions pulled from the page sources, lazy blocks loaded / skipped */
 int32_t tgpu_scan_operator_stats(tgpu_operator *op, int64_t *processed_positions, int64_t *lazy_blocks_loaded, int64_t *lazy_blocks_skipped);
 
+/* ---- MergeOperator (M/operator/MergeOperator.java:44-256; the same routine behind LocalMergeSourceOperator, M/operator/exchange/
+ * LocalMergeSourceOperator.java:39-): a SOURCE operator that merges k sorted page streams into one sorted stream, MergeSortedPages
+ * (M/util/MergeSortedPages.java:41-142, WorkProcessorUtils.java:110-152).  `types` = the channels of every stream's pages,
+ * output_channels the channels of the output page, sort channels / orders as for TopN above.  A stream is a tgpu_page_source
+ * (tgpu_merge_operator_add_page_source = addSplit :155-177; load_block is never called: TGPU_LAZY blocks are refused); its pages
+ * may be host or device memory, FLAT / DICTIONARY / RLE.  The source's arrays are valid until the next call on that source: a
+ * pulled page is ingested (host), copied or owner-shared (device) at once.
+ *   Source operator  needs_input is 0; tgpu_operator_add_input fails with TGPU_ERR_NOT_SUPPORTED (:222-231).
+ *   Blocked          is_blocked is 1 until no_more_splits (blockedOnSplits, :208-219).  Afterwards it is 1 while some stream has no
+ *                    buffered row, is not finished and its get_next_page last returned 0.  Like the reference, which blocks on its
+ *                    sources one after the other, the operator waits on the FIRST such stream in split order: where that source has
+ *                    an is_blocked callback the operator is unblocked as soon as the callback returns 0 (the next get_output pulls
+ *                    again); without a callback it stays blocked until the next get_output has pulled.  get_output returns a NULL
+ *                    page with TGPU_WOULD_BLOCK while the operator is blocked.
+ *   Splits           add_page_source after no_more_splits fails ("noMoreSplits has been called already", :159).  No split at all
+ *                    followed by no_more_splits: a finished operator without output.
+ *   finish           is close (:196-199): the operator is finished at once and emits nothing further.
+ *   close callbacks  every source's close is called exactly once: when its stream ends, or when the operator closes or finishes.
+ *   Pulling          get_output pulls from every unfinished stream that holds fewer than half an internal read-ahead of rows, until
+ *                    the source returns 0, is finished or the read-ahead is reached.  A negative return of get_next_page fails the
+ *                    call with that value as its error code.  A page whose channel count or types differ from `types`:
+ *                    TGPU_ERR_INVALID_ARGUMENT.  After such a failure the operator is still usable: the pages pulled before the
+ *                    failing one stay buffered, only the failing page is lost, and the next get_output pulls again.
+ *   Rounds           one get_output runs at most one round and returns at most one page (cut by tgpu_context_set_max_output_page as
+ *                    for every operator; page cuts are not part of the contract).  Let B be the smallest (last buffered row, stream
+ *                    index) over the unfinished streams -- rows compare with the comparator, then by stream index -- and t_B its
+ *                    stream.  A buffered row (r, s) is SETTLED when (r, s) <= (B, t_B); with every stream finished every buffered
+ *                    row is.  A round emits exactly the settled rows, merged.  With a stream that is unfinished and empty there is
+ *                    no round (blocked, or the source yielded).
+ *   Order            SimplePageWithPositionComparator (as TopN above).  Rows that compare equal come out lower stream first (in
+ *                    add_page_source order) and, inside a stream, in arrival order; the reference's binary heap leaves the order of
+ *                    cross-stream ties unspecified.
+ *   Unsorted input   is not detected (neither does the reference).  Which row comes out where is then unspecified -- a row may come out
+ *                    twice and another not at all; the row count is kept -- and nothing else is: no kernel reads outside its buffers
+ *                    or loops without bound.
+ *   Limits           more than 2^31 - 1 settled rows: the round is cut and the rest comes out of the next.  A VARCHAR output
+ *                    channel over 2 GB fails with "variable width block cannot exceed 2GB".
+ *   memory_bytes     the streams' buffered input rows (no page is ever pending: a round's page leaves with the get_output that built
+ *                    it); 0 once the operator is finished. */
+int32_t tgpu_merge_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                  int32_t output_channel_count, const int32_t *output_channels,
+                                  int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                  tgpu_operator_factory **out);
+int32_t tgpu_merge_operator_add_page_source(tgpu_operator *op, const tgpu_page_source *source);   /* addSplit: one sorted stream */
+int32_t tgpu_merge_operator_no_more_splits(tgpu_operator *op);
+
 /* OperatorFactory.createOperator / noMoreOperators (M/operator/OperatorFactory.java:18-50) */
 int32_t tgpu_operator_factory_create_operator(tgpu_operator_factory *factory, tgpu_operator **out);
 int32_t tgpu_operator_factory_no_more_operators(tgpu_operator_factory *factory);

@@ -144,6 +144,8 @@ public final class GpuNative
     public static native long createLimitFactory(long context, int operatorId, int[] types, long limit);
     public static native long createTopNFactory(long context, int operatorId, int[] types, long n, int[] sortChannels, int[] sortOrders);
     public static native long createOrderByFactory(long context, int operatorId, int[] types, int[] outputChannels, int expectedPositions, int[] sortChannels, int[] sortOrders);
+    /** MergeOperatorFactory (tgpu_merge_factory_create): the k-way merge of sorted page streams; the streams arrive through mergeAddPageSource */
+    public static native long createMergeFactory(long context, int operatorId, int[] types, int[] outputChannels, int[] sortChannels, int[] sortOrders);
     public static native long createMergePagesFactory(long context, int operatorId, int[] types, long minPageSizeInBytes, int minRowCount, long maxPageSizeInBytes);
     public static native long createPartitionedOutputFactory(long context, int operatorId, int[] types, int[] partitionChannels, int hashChannel, int partitionCount,
             boolean replicatesAnyRow, int nullChannel, int partitionFunction);
@@ -161,6 +163,9 @@ public final class GpuNative
     public static native void scanAddPageSource(long operator, GpuPageSource source, int[] types);
     public static native void scanNoMoreSplits(long operator);
     public static native void scanStats(long operator, long[] positionsLoadedSkipped);
+    // ---- the merge operator's splits: one sorted stream each, through the same GpuPageSource upcalls (every channel is loaded at once) ----
+    public static native void mergeAddPageSource(long operator, GpuPageSource source, int[] types);
+    public static native void mergeNoMoreSplits(long operator);
 
     // ---- scan-side decode (tgpu_orc_decode_*): the decompressed streams of one ORC column of one stripe / row group -> a device-resident page ----
     /** LongColumnReader: PRESENT (or null) + DATA; type = GpuPages.T_BIGINT / T_INTEGER / T_DATE, encoding = the ColumnEncoding kind's ordinal */

@@ -722,6 +722,26 @@ public final class GpuOperatorFactories
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuOrderByOperator", types, poller, factory));
     }
 
+    /**
+     * MergeOperator.MergeOperatorFactory (operator/MergeOperator.java:47-107; LocalExecutionPlanner.java:783) and, with local sources behind
+     * `pageSourceForSplit`, LocalMergeSourceOperator (operator/exchange/LocalMergeSourceOperator.java:39-; LocalExecutionPlanner.java:2687): the k-way merge
+     * of sorted streams.  Every split added to the operator is one stream.
+     */
+    public Optional<SourceOperatorFactory> merge(int operatorId, PlanNodeId planNodeId, PlanNodeId sourceId, List<Type> types, List<Integer> outputChannels,
+            List<Integer> sortChannels, List<SortOrder> sortOrders, Function<Split, ConnectorPageSource> pageSourceForSplit)
+    {
+        int[] codes;
+        try {
+            codes = GpuPages.typeCodes(types);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createMergeFactory(context, operatorId, codes, ints(outputChannels), ints(sortChannels), sortOrders.stream().mapToInt(SortOrder::ordinal).toArray());
+        List<Type> outputTypes = outputChannels.stream().map(types::get).collect(java.util.stream.Collectors.toList());
+        return Optional.of(new GpuMergeOperatorFactory(operatorId, planNodeId, sourceId, types, outputTypes, pageSourceForSplit, poller, factory));
+    }
+
     /** MergePages (operator/project/MergePages.java:64-190) as an operator in front of GPU operators that want large pages (DESIGN.md "Page granularity") */
     public OperatorFactory mergePages(int operatorId, PlanNodeId planNodeId, List<Type> types, DataSize minPageSize, int minRowCount, DataSize maxPageSize)
     {

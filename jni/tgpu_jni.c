@@ -305,6 +305,7 @@ VOID_OP_CALL(finish, tgpu_operator_finish)
 VOID_OP_CALL(startMemoryRevoke, tgpu_operator_start_memory_revoke)     /* Operator.startMemoryRevoke / finishMemoryRevoke (spill-enabled hash aggregations) */
 VOID_OP_CALL(finishMemoryRevoke, tgpu_operator_finish_memory_revoke)
 VOID_OP_CALL(scanNoMoreSplits, tgpu_scan_operator_no_more_splits)
+VOID_OP_CALL(mergeNoMoreSplits, tgpu_merge_operator_no_more_splits)
 
 JFN(jlong, memoryBytes)(JNIEnv *env, jclass c, jlong op) { UNUSED(env); UNUSED(c); return tgpu_operator_memory_bytes(H(tgpu_operator, op)); }
 JFN(jlong, revocableMemoryBytes)(JNIEnv *env, jclass c, jlong op) { UNUSED(env); UNUSED(c); return tgpu_operator_revocable_memory_bytes(H(tgpu_operator, op)); }
@@ -1107,6 +1108,21 @@ JFN(jlong, createOrderByFactory)(JNIEnv *env, jclass c, jlong ctx, jint operator
     return factory_result(env, rc, f);
 }
 
+/* MergeOperator.MergeOperatorFactory (M/operator/MergeOperator.java:47-107) */
+JFN(jlong, createMergeFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray outputChannels, jintArray sortChannels, jintArray sortOrders)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types), oc = ints_get(env, outputChannels), sc = ints_get(env, sortChannels), so = ints_get(env, sortOrders);
+    tgpu_operator_factory *f = NULL;
+    const int malformed = sc.n != so.n;
+    int32_t rc = malformed ? TGPU_ERR_INVALID_ARGUMENT
+                           : tgpu_merge_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, oc.n, (const int32_t *)oc.p, sc.n, (const int32_t *)sc.p,
+                                                       (const int32_t *)so.p, &f);
+    ints_release(env, &so); ints_release(env, &sc); ints_release(env, &oc); ints_release(env, &t);
+    if (malformed) { throw_native_message(env, rc, "sort channels and sort orders differ in length"); return 0; }
+    return factory_result(env, rc, f);
+}
+
 /* MergePages as an operator (M/operator/project/MergePages.java:64-190) */
 JFN(jlong, createMergePagesFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jlong minPageSizeInBytes, jint minRowCount, jlong maxPageSizeInBytes)
 {
@@ -1328,10 +1344,25 @@ static void source_close(void *user)
     free(s->owned); free(s->dicts); free(s->lazy); free(s->types); free(s);
 }
 
-/* SourceOperator.addSplit: the split's page source (one at a time).  `types` = the channels it produces. */
-JFN(void, scanAddPageSource)(JNIEnv *env, jclass c, jlong op, jobject adapter, jintArray types)
+/* the same source for the merge operator, which takes loaded pages only (it reads every channel of every row): each channel is loaded
+ * right after the page was announced and replaces its TGPU_LAZY placeholder */
+static int32_t source_get_next_loaded_page(void *user, tgpu_page *page)
 {
-    UNUSED(c);
+    jni_source *s = (jni_source *)user;
+    const int32_t rc = source_get_next_page(user, page);
+    if (rc <= 0) return rc;
+    for (int32_t ch = 0; ch < s->channels; ch++) {
+        tgpu_block loaded;
+        const int32_t lrc = source_load_block(user, ch, &loaded);
+        if (lrc < 0) return lrc;
+        s->lazy[ch] = loaded;
+    }
+    return 1;
+}
+
+/* wraps the Java adapter into a tgpu_page_source and hands it to the scan operator, or (merged) as one sorted stream to the merge operator */
+static void add_page_source(JNIEnv *env, jlong op, jobject adapter, jintArray types, int merged)
+{
     jclass cls = (*env)->GetObjectClass(env, adapter);
     jni_source *s = (jni_source *)calloc(1, sizeof(jni_source));
     s->next_page = (*env)->GetMethodID(env, cls, "nextPage", "()I");
@@ -1352,14 +1383,18 @@ JFN(void, scanAddPageSource)(JNIEnv *env, jclass c, jlong op, jobject adapter, j
     s->dicts = (tgpu_block *)calloc((size_t)(s->channels > 0 ? s->channels : 1), sizeof(tgpu_block));
     s->owned = (void **)calloc((size_t)(7 * s->channels + 1), sizeof(void *));
     s->adapter = (*env)->NewGlobalRef(env, adapter);
-    tgpu_page_source src = {s, source_get_next_page, source_is_finished, source_is_blocked, source_load_block, source_close};
-    int32_t rc = tgpu_scan_operator_add_page_source(H(tgpu_operator, op), &src);
+    tgpu_page_source src = {s, merged ? source_get_next_loaded_page : source_get_next_page, source_is_finished, source_is_blocked, source_load_block, source_close};
+    int32_t rc = merged ? tgpu_merge_operator_add_page_source(H(tgpu_operator, op), &src) : tgpu_scan_operator_add_page_source(H(tgpu_operator, op), &src);
     if (rc < 0) {
         (*env)->DeleteGlobalRef(env, s->adapter);
         free(s->owned); free(s->dicts); free(s->lazy); free(s->types); free(s);
         throw_native(env, rc);
     }
 }
+/* SourceOperator.addSplit: the split's page source (one at a time).  `types` = the channels it produces. */
+JFN(void, scanAddPageSource)(JNIEnv *env, jclass c, jlong op, jobject adapter, jintArray types) { UNUSED(c); add_page_source(env, op, adapter, types, 0); }
+/* MergeOperator.addSplit (M/operator/MergeOperator.java:155-177): one sorted stream */
+JFN(void, mergeAddPageSource)(JNIEnv *env, jclass c, jlong op, jobject adapter, jintArray types) { UNUSED(c); add_page_source(env, op, adapter, types, 1); }
 /* OperatorStats of the scan side (:354-397): out = {processed positions, lazy blocks loaded, lazy blocks skipped} */
 JFN(void, scanStats)(JNIEnv *env, jclass c, jlong op, jlongArray out)
 {

@@ -143,6 +143,9 @@ SYMBOLS = {
     "tgpu_order_by_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, i32, P(i32), P(i32), P(vp)]),
     "tgpu_filter_project_lookup_join_factory_create": (i32, [vp, i32, vp, i32, P(i32), P(PageProcessorSpec), i32, P(i32), i32, i32, P(i32), i32, P(vp)]),
     "tgpu_filter_project_hash_aggregation_factory_create": (i32, [vp, i32, i32, P(i32), P(PageProcessorSpec), i32, P(i32), P(i32), i32, i32, i32, P(AggSpec), i32, P(vp)]),
+    "tgpu_merge_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), P(i32), P(vp)]),
+    "tgpu_merge_operator_add_page_source": (i32, [vp, P(PageSource)]),
+    "tgpu_merge_operator_no_more_splits": (i32, [vp]),
     "tgpu_scan_filter_project_factory_create": (i32, [vp, i32, i32, P(i32), P(PageProcessorSpec), P(vp)]),
     "tgpu_scan_operator_add_page_source": (i32, [vp, P(PageSource)]),
     "tgpu_scan_operator_add_record_cursor": (i32, [vp, P(RecordCursor), i32, P(i32)]),

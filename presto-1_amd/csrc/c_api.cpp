@@ -530,6 +530,33 @@ int32_t tgpu_order_by_factory_create(tgpu_context *ctx, int32_t operator_id, int
     });
 }
 
+int32_t tgpu_merge_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
+                                  int32_t output_channel_count, const int32_t *output_channels,
+                                  int32_t sort_channel_count, const int32_t *sort_channels, const int32_t *sort_orders,
+                                  tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        make_factory<MergeOperatorFactory>(ctx, out, operator_id, MergeConfig{vec(types, type_count), vec(output_channels, output_channel_count),
+                                                                                vec(sort_channels, sort_channel_count), vec(sort_orders, sort_channel_count)});
+    });
+}
+
+int32_t tgpu_merge_operator_add_page_source(tgpu_operator *op, const tgpu_page_source *source)
+{
+    return guard_on(ctx_of(op), [&] {
+        TG_CHECK_ARG(op != nullptr && op->op && source, "null argument");
+        merge_add_page_source(op->op.get(), source);
+    });
+}
+
+int32_t tgpu_merge_operator_no_more_splits(tgpu_operator *op)
+{
+    return guard_on(ctx_of(op), [&] {
+        TG_CHECK_ARG(op != nullptr && op->op, "operator is null or closed");
+        merge_no_more_splits(op->op.get());
+    });
+}
+
 void tgpu_lookup_source_factory_destroy(tgpu_lookup_source_factory *bridge)
 {
     if (!bridge) return;
@@ -706,6 +733,10 @@ int32_t tgpu_operator_add_input(tgpu_operator *op, const tgpu_page *page)
     return guard_on(ctx_of(op), [&] {
         TG_CHECK_ARG(op != nullptr && op->op, "operator is null or closed");
         TG_CHECK_ARG(page != nullptr, "page is null");
+        if (op->op->is_source()) {   // refused with the operator's own error (MergeOperator.java:228-231: UnsupportedOperationException)
+            op->op->add_input(page);
+            return;
+        }
         TG_CHECK_STATE(op->op->needs_input(), "Operator does not need input");
         op->op->add_input(page);
     });

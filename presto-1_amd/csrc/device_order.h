@@ -1,4 +1,4 @@
-// device_order.h -- the row order of the sort channels on the device, shared by topn.hip and topn_ranking.hip: the 64-bit ORDER CODE of a
+// device_order.h -- the row order of the sort channels on the device, shared by topn.hip, topn_ranking.hip and merge.hip: the 64-bit ORDER CODE of a
 // row's first sort key and the full row comparator (SimplePageWithPositionComparator.java:58-79 + TypeOperators.java:578-596: nulls
 // placed by the SortOrder, values by the type's COMPARISON operator, negated for DESC).  AOT kernels only (not embedded into JIT sources).
 #pragma once
@@ -44,45 +44,46 @@ __device__ __forceinline__ unsigned long long cell_order_bits(const TgColView &c
     }
 }
 
-// the type's COMPARISON operator on two non-null cells: <0, 0, >0 (Long.compare / Integer.compare / Double.compare /
-// Boolean.compare / Slice.compareTo = unsigned bytes, then length)
-__device__ __forceinline__ int compare_cells(const TgColView &c, long long a, long long b)
+// the type's COMPARISON operator on two non-null cells, cell a of column x against cell b of column y (columns of one type): <0, 0, >0
+// (Long.compare / Integer.compare / Double.compare / Boolean.compare / Slice.compareTo = unsigned bytes, then length)
+__device__ __forceinline__ int compare_cells(const TgColView &x, long long a, const TgColView &y, long long b)
 {
-    if (c.type == TGPU_VARCHAR) {
-        const int oa = c.offsets[a], la = c.offsets[a + 1] - oa, ob = c.offsets[b], lb = c.offsets[b + 1] - ob;
-        const unsigned char *pa = (const unsigned char *)c.values + oa, *pb = (const unsigned char *)c.values + ob;
+    if (x.type == TGPU_VARCHAR) {
+        const int oa = x.offsets[a], la = x.offsets[a + 1] - oa, ob = y.offsets[b], lb = y.offsets[b + 1] - ob;
+        const unsigned char *pa = (const unsigned char *)x.values + oa, *pb = (const unsigned char *)y.values + ob;
         const int m = la < lb ? la : lb;
         for (int i = 0; i < m; i++)
             if (pa[i] != pb[i]) return pa[i] < pb[i] ? -1 : 1;
         return la < lb ? -1 : (la > lb ? 1 : 0);
     }
-    const unsigned long long x = cell_order_bits(c, a), y = cell_order_bits(c, b);
-    return x < y ? -1 : (x > y ? 1 : 0);
+    const unsigned long long p = cell_order_bits(x, a), q = cell_order_bits(y, b);
+    return p < q ? -1 : (p > q ? 1 : 0);
 }
+__device__ __forceinline__ int compare_cells(const TgColView &c, long long a, long long b) { return compare_cells(c, a, c, b); }
 
-// SimplePageWithPositionComparator.compareTo over the sort keys
-__device__ __forceinline__ int compare_rows(const TopNKeys &k, long long a, long long b)
+// SimplePageWithPositionComparator.compareTo over the sort keys: row a of the columns x against row b of the columns y (the same
+// channels of two pages; merge.hip compares rows of different streams)
+__device__ __forceinline__ int compare_rows(const TgKeyCols &x, long long a, const TgKeyCols &y, long long b, const int *order)
 {
-    for (int i = 0; i < k.cols.n; i++) {
-        const TgColView &c = k.cols.c[i];
-        const bool na = c.nulls && c.nulls[a], nb = c.nulls && c.nulls[b];
+    for (int i = 0; i < x.n; i++) {
+        const TgColView &c = x.c[i], &d = y.c[i];
+        const bool na = c.nulls && c.nulls[a], nb = d.nulls && d.nulls[b];
         if (na || nb) {   // TypeOperators.orderNulls
             if (na && nb) continue;
-            if (na) return nulls_first(k.order[i]) ? -1 : 1;
-            return nulls_first(k.order[i]) ? 1 : -1;
+            if (na) return nulls_first(order[i]) ? -1 : 1;
+            return nulls_first(order[i]) ? 1 : -1;
         }
-        const int cmp = compare_cells(c, a, b);
-        if (cmp) return asc(k.order[i]) ? cmp : -cmp;
+        const int cmp = compare_cells(c, a, d, b);
+        if (cmp) return asc(order[i]) ? cmp : -cmp;
     }
     return 0;
 }
+__device__ __forceinline__ int compare_rows(const TopNKeys &k, long long a, long long b) { return compare_rows(k.cols, a, k.cols, b, k.order); }
 
 // The order code of row r: the first sort key's order-preserving bit pattern, complemented for DESC, shifted right by one and topped
 // with a null bit placed by the SortOrder.  code(a) < code(b) implies a sorts before b; equal codes decide nothing.
-__device__ __forceinline__ unsigned long long order_code(const TopNKeys &k, long long r)
+__device__ __forceinline__ unsigned long long order_code(const TgColView &c, int order, long long r)
 {
-    const TgColView &c = k.cols.c[0];
-    const int order = k.order[0];
     const bool is_null = c.nulls && c.nulls[r];
     unsigned long long v = 0;
     if (!is_null) {
@@ -93,5 +94,6 @@ __device__ __forceinline__ unsigned long long order_code(const TopNKeys &k, long
     const unsigned long long top = (is_null == nulls_first(order)) ? 0ULL : 1ULL;
     return (top << 63) | (is_null ? 0ULL : (v >> 1));
 }
+__device__ __forceinline__ unsigned long long order_code(const TopNKeys &k, long long r) { return order_code(k.cols.c[0], k.order[0], r); }
 
 }  // namespace tgpu

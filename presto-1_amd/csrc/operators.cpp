@@ -1855,6 +1855,244 @@ static void validate(Context *ctx, const OrderByConfig &cfg)
 }
 
 // =====================================================================================================================
+// MergeOperator (M/operator/MergeOperator.java:44-256; the same routine behind LocalMergeSourceOperator.java:39-): a source operator
+// over k sorted page streams, MergeSortedPages.mergeSortedPages (M/util/MergeSortedPages.java:41-142) as ROUNDS on the device.
+// get_output pulls from every unfinished stream that holds fewer than half its read-ahead of rows, then runs at most one round (merge.h):
+// the rows no later row of any stream can precede are merged and emitted, the others stay buffered.  A stream's buffered rows are ONE
+// page: a pulled page is kept as it came (owners shared) while it is the only one, and rows left over from earlier pages are
+// concatenated with the new ones into a buffer of the stream's own (PagesIndexGpu) when it pulls again.
+// =====================================================================================================================
+class MergeOperator : public Operator {
+public:
+    MergeOperator(Context *ctx, int32_t id, const MergeConfig &cfg)
+        : Operator(ctx, id), cfg_(cfg), merge_(std::make_unique<MergeGpu>(ctx, cfg.types, cfg.output_channels, cfg.sort_channels, cfg.sort_orders))
+    {
+    }
+    ~MergeOperator() override { close(); }
+
+    bool is_source() const override { return true; }
+    bool needs_input() override { return false; }                                                                    // :222-225
+    void add_input(const tgpu_page *) override { fail(TGPU_ERR_NOT_SUPPORTED, "MergeOperator is a source operator"); }   // :228-231
+
+    void add_page_source(const tgpu_page_source *src)                                                                // addSplit :155-177
+    {
+        TG_CHECK_ARG(src && src->get_next_page && src->is_finished, "page source callbacks are null");
+        TG_CHECK_STATE(!no_more_splits_, "noMoreSplits has been called already");                                    // :159
+        if (closed_) {   // a split that arrives after close: nothing will read it
+            if (src->close) src->close(src->user);
+            return;
+        }
+        streams_.emplace_back();
+        streams_.back().source = *src;
+    }
+    void no_more_splits() { no_more_splits_ = true; }                                                                // :180-184
+
+    // blockedOnSplits (:208-219) until noMoreSplits; afterwards the future of the first stream (in split order) that has no buffered row and
+    // is waiting for its source -- the reference blocks on its sources one after the other (WorkProcessorUtils.mergeSorted :124-139)
+    bool is_blocked() override
+    {
+        if (closed_) return false;
+        if (!no_more_splits_) return true;
+        for (Stream &s : streams_)
+            if (waiting(s)) return !s.source.is_blocked || s.source.is_blocked(s.source.user) == 1;
+        return false;
+    }
+
+    std::unique_ptr<OutputPage> get_output() override
+    {
+        if (closed_ || !no_more_splits_) return nullptr;
+        const int64_t read_ahead = std::max<int64_t>(kMergeMinReadAheadRows, kMergeRoundRows / std::max<int64_t>(1, (int64_t)streams_.size()));
+        for (Stream &s : streams_) pull(s, read_ahead);
+        int64_t buffered = 0;
+        for (Stream &s : streams_) {
+            if (!s.finished && s.available() == 0) return nullptr;   // blocked on this stream: nothing is settled yet
+            buffered += s.available();
+        }
+        if (buffered == 0) {   // every stream is finished and drained
+            close();
+            return nullptr;
+        }
+        // more buffered rows than one page may hold: every stream takes part with a window of its first rows, and a cut window counts
+        // as an unfinished stream (its next row bounds the round); the rest comes out in later rounds
+        const int64_t k = (int64_t)streams_.size(), share = std::max<int64_t>(1, kMergeMaxRoundRows / k);
+        const bool cut = buffered > kMergeMaxRoundRows;
+        std::vector<const DevicePage *> pages;
+        std::vector<int64_t> head, window, settled;
+        std::vector<bool> open;
+        for (Stream &s : streams_) {
+            const int64_t w = cut ? std::min(s.available(), share) : s.available();
+            pages.push_back(s.has_buf ? &s.buf : nullptr);
+            head.push_back(s.head);
+            window.push_back(w);
+            open.push_back(!s.finished || w < s.available());
+        }
+        DevicePage out = merge_->round(pages, head, window, open, settled);
+        for (size_t i = 0; i < streams_.size(); i++) {
+            Stream &s = streams_[i];
+            s.head += settled[i];
+            if (s.has_buf && s.available() == 0) s.drop();
+        }
+        bool done = true;
+        for (Stream &s : streams_) done = done && s.finished && s.available() == 0;
+        if (done) close();
+        if (out.n == 0) return nullptr;
+        return wrap(std::move(out));
+    }
+
+    void finish() override { close(); }                                                                              // :196-199
+    bool is_finished() override
+    {
+        if (closed_) return true;
+        if (!no_more_splits_) return false;
+        for (Stream &s : streams_)
+            if (!s.finished || s.available() > 0) return false;
+        return true;   // (also: no split at all)
+    }
+    // the buffered input rows (whole buffers: rows already emitted leave with their buffer).  A round's page is handed out by the
+    // get_output that built it, so no output page is ever pending here.
+    int64_t memory_bytes() override
+    {
+        int64_t b = 0;
+        for (Stream &s : streams_)
+            if (s.has_buf) b += s.buf.size_in_bytes();
+        return b;
+    }
+    void close() override                                                                                            // :240-255
+    {
+        for (Stream &s : streams_) {
+            end(s);
+            s.drop();
+        }
+        merge_.reset();
+        closed_ = true;
+    }
+
+private:
+    struct Stream {
+        tgpu_page_source source{};
+        bool source_open = true;   // its close callback has not been called
+        bool finished = false;     // no further page will come
+        bool last_zero = false;    // get_next_page returned 0 last
+        bool has_buf = false;
+        DevicePage buf;            // rows [head, buf.n) are buffered
+        int64_t head = 0;
+        int64_t available() const { return has_buf ? buf.n - head : 0; }
+        void drop()
+        {
+            buf = DevicePage();
+            has_buf = false;
+            head = 0;
+        }
+    };
+    static bool waiting(const Stream &s) { return !s.finished && s.available() == 0 && s.last_zero; }
+
+    // the stream has ended (or the operator closes): its source is closed exactly once
+    void end(Stream &s)
+    {
+        s.finished = true;
+        if (s.source_open && s.source.close) s.source.close(s.source.user);
+        s.source_open = false;
+    }
+
+    // Pulls once the stream holds fewer than HALF its read-ahead, then up to the read-ahead: rows left over from earlier pages are copied
+    // when the stream pulls again (absorb), and a stream that can deliver takes in at least as many new rows as it carries over.
+    void pull(Stream &s, int64_t read_ahead)
+    {
+        if (s.finished || s.available() >= std::max<int64_t>(1, read_ahead / 2)) return;
+        std::vector<DevicePage> fresh;
+        try {
+            int64_t rows = s.available();
+            while (rows < read_ahead) {
+                if (s.source.is_finished(s.source.user) == 1) {
+                    end(s);
+                    break;
+                }
+                tgpu_page page{};
+                const int32_t rc = s.source.get_next_page(s.source.user, &page);
+                if (rc < 0) fail(rc, "the page source of a merged stream failed");
+                if (rc == 0) {
+                    if (s.source.is_finished(s.source.user) == 1) end(s);
+                    else s.last_zero = true;
+                    break;
+                }
+                s.last_zero = false;
+                TG_CHECK_ARG(page.channel_count == (int32_t)cfg_.types.size(), "page channel count does not match the operator's types");
+                for (int32_t ch = 0; ch < page.channel_count; ch++) {
+                    TG_CHECK_ARG(page.blocks && page.blocks[ch].type == cfg_.types[(size_t)ch], "page channel type does not match the operator's types");
+                    TG_CHECK_ARG(page.blocks[ch].encoding != TGPU_LAZY, "a merged stream's pages must be loaded");
+                }
+                if (page.position_count == 0) continue;
+                TG_CHECK_STATE(rows + page.position_count <= 0xffffffffLL, "a merged stream buffers more rows than a row reference can address");
+                DevicePage in = ingest_page(ctx_, &page);   // (host arrays are consumed when it returns)
+                own_borrowed_columns(ctx_, in);             // device arrays are valid until the next call on the source only
+                rows += in.n;
+                fresh.push_back(std::move(in));
+            }
+        }
+        catch (...) {
+            // the pages this call took in before the failure are rows of the stream like any other: they stay buffered, so a caller that
+            // goes on after the error loses nothing but the page that failed
+            try {
+                absorb(s, fresh);
+            }
+            catch (...) {
+            }
+            throw;
+        }
+        absorb(s, fresh);
+    }
+
+    // the stream's buffer becomes (rows not emitted yet, fresh pages...): one page kept as it came while it is the only one, else one
+    // concatenation into a buffer of the stream's own
+    void absorb(Stream &s, std::vector<DevicePage> &fresh)
+    {
+        if (fresh.empty()) return;
+        if (s.available() == 0 && fresh.size() == 1) {
+            s.buf = std::move(fresh[0]);
+            s.head = 0;
+            s.has_buf = true;
+            fresh.clear();
+            return;
+        }
+        PagesIndexGpu index(ctx_, cfg_.types);
+        if (s.available() > 0) {
+            DevicePage rest;
+            rest.n = s.available();
+            for (const DeviceColumn &c : s.buf.cols) rest.cols.push_back(k::region_of(ctx_, c, s.head, rest.n));
+            index.add_page(rest);
+        }
+        for (const DevicePage &p : fresh) index.add_page(p);
+        DevicePage all;
+        all.n = index.position_count();
+        for (size_t i = 0; i < cfg_.types.size(); i++) all.cols.push_back(index.column((int)i));
+        s.buf = std::move(all);
+        s.head = 0;
+        s.has_buf = true;
+        fresh.clear();
+    }
+
+    MergeConfig cfg_;
+    std::unique_ptr<MergeGpu> merge_;
+    std::vector<Stream> streams_;
+    bool no_more_splits_ = false, closed_ = false;
+};
+
+static void validate(Context *ctx, const MergeConfig &cfg)
+{
+    MergeGpu check(ctx, cfg.types, cfg.output_channels, cfg.sort_channels, cfg.sort_orders);   // its constructor checks the arguments
+    (void)check;
+}
+
+static MergeOperator *as_merge(Operator *op)
+{
+    auto *p = dynamic_cast<MergeOperator *>(op);
+    TG_CHECK_ARG(p != nullptr, "not a MergeOperator");
+    return p;
+}
+void merge_add_page_source(Operator *op, const tgpu_page_source *source) { as_merge(op)->add_page_source(source); }
+void merge_no_more_splits(Operator *op) { as_merge(op)->no_more_splits(); }
+
+// =====================================================================================================================
 // DynamicFilterSourceOperator (M/operator/DynamicFilterSourceOperator.java:145-425).  Pages pass through unchanged (:375-381);
 // per filter channel the operator keeps the set of distinct values (TypedSet -> a GroupByHash per channel here) while no
 // channel exceeds max_distinct_values and the collected blocks stay within max_filter_size_in_bytes (:238-262); beyond that it
@@ -3324,6 +3562,7 @@ template class SimpleOperatorFactory<ScanFilterAndProjectConfig, ScanFilterAndPr
 template class SimpleOperatorFactory<HashAggregationConfig, HashAggregationOperator>;
 template class SimpleOperatorFactory<TopNConfig, TopNOperator>;
 template class SimpleOperatorFactory<OrderByConfig, OrderByOperator>;
+template class SimpleOperatorFactory<MergeConfig, MergeOperator>;
 template class SimpleOperatorFactory<DynamicFilterSourceConfig, DynamicFilterSourceOperator>;
 template class SimpleOperatorFactory<HashSemiJoinConfig, HashSemiJoinOperator>;
 template class SimpleOperatorFactory<MarkDistinctConfig, MarkDistinctOperator>;

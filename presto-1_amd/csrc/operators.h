@@ -13,6 +13,7 @@
 #include "nested_loop.h"
 #include "rownumber.h"
 #include "join.h"
+#include "merge.h"
 #include "semijoin.h"
 #include "topn.h"
 #include "topn_ranking.h"
@@ -33,6 +34,8 @@ public:
     virtual void finish() = 0;
     virtual bool is_finished() = 0;
     virtual bool is_blocked() { return false; }
+    // a source operator that refuses every addInput with an error of its own (MergeOperator: TGPU_ERR_NOT_SUPPORTED)
+    virtual bool is_source() const { return false; }
     virtual int64_t memory_bytes() { return 0; }
     // Operator.startMemoryRevoke / finishMemoryRevoke (M/operator/Operator.java:53-79) and OperatorContext.getReservedRevocableBytes:
     // only a spill-enabled hash aggregation holds revocable memory
@@ -546,6 +549,14 @@ struct OrderByConfig {
     std::vector<int32_t> types, output_channels, sort_channels, sort_orders;
 };
 using OrderByOperatorFactory = SimpleOperatorFactory<OrderByConfig, class OrderByOperator>;
+
+// ---- MergeOperator (M/operator/MergeOperator.java:44-256) over MergeSortedPages (M/util/MergeSortedPages.java:41-142) ------------------
+struct MergeConfig {
+    std::vector<int32_t> types, output_channels, sort_channels, sort_orders;
+};
+using MergeOperatorFactory = SimpleOperatorFactory<MergeConfig, class MergeOperator>;   // (a SourceOperatorFactory: the reference has no duplicate(); the copy here is harmless)
+void merge_add_page_source(Operator *op, const tgpu_page_source *source);
+void merge_no_more_splits(Operator *op);
 
 // ---- DynamicFilterSourceOperator (M/operator/DynamicFilterSourceOperator.java:46-425) ---------------------------------------------
 // Passes the build side's pages through and collects, per join-key channel, what the probe side's scan may be narrowed to.

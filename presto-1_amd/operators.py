@@ -380,6 +380,37 @@ class ScanFilterAndProjectOperatorFactory(OperatorFactory):
         return ScanOperator(h)
 
 
+class MergeOperator(Operator):
+    """MergeOperator (M/operator/MergeOperator.java:109-256): a source operator over sorted page streams"""
+
+    def addSplit(self, source: PageSource):
+        """SourceOperator.addSplit (:155-177): one sorted stream, as a PageSource (its load callback is never used)"""
+        self._sources = getattr(self, "_sources", []) + [source]   # the callbacks must outlive the operator
+        _lib.check(_lib.lib().tgpu_merge_operator_add_page_source(self.handle, C.byref(source.struct)))
+
+    def noMoreSplits(self):
+        _lib.check(_lib.lib().tgpu_merge_operator_no_more_splits(self.handle))
+
+
+class MergeOperatorFactory(OperatorFactory):
+    """MergeOperator.MergeOperatorFactory (M/operator/MergeOperator.java:47-107): the k-way merge of sorted streams (MergeSortedPages);
+    rows that compare equal come out lower stream first, inside a stream in arrival order"""
+
+    def __init__(self, ctx: Context, operator_id, types, output_channels, sort_channels, sort_orders):
+        t, n = _i32(types)
+        oc, no = _i32(output_channels)
+        sc, ns = _i32(sort_channels)
+        so, _ = _i32(sort_orders)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_merge_factory_create(ctx.handle, operator_id, n, t, no, oc, ns, sc, so, C.byref(h)))
+        super().__init__(h)
+
+    def createOperator(self):
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_operator_factory_create_operator(self.handle, C.byref(h)))
+        return MergeOperator(h)
+
+
 def precompile_page_processor(input_types, filter_expr, projections):
     """Compile the kernels of a page processor into the on-disk cache (no GPU needed)."""
     prog = FlatProgram(filter_expr, projections)
