@@ -363,6 +363,35 @@ int32_t tgpu_hash_aggregation_factory_create(tgpu_context *ctx, int32_t operator
                                              int32_t expected_groups, int32_t produce_default_output,
                                              tgpu_operator_factory **out);
 
+/* StreamingAggregationOperator.createOperatorFactory (M/operator/StreamingAggregationOperator.java:50-69; process / processInput :216-347):
+ * the aggregation the planner chooses when its input is already grouped on the keys (M/sql/planner/LocalExecutionPlanner.java:3022-3031).
+ * `types` are the source types; the group-by types are those of `group_by_channels`.
+ *   Groups        a group is a maximal run of consecutive rows of the stream whose key rows are NOT DISTINCT from each other
+ *                 (rowNotDistinctFromRow: null equals null, any NaN equals any NaN, -0.0 equals +0.0, VARCHAR by bytes), across any
+ *                 number of pages.  No order among the groups is needed or checked; a key that comes back later is a new group.
+ *   Output        channels: the group-by keys, then the aggregates in the layouts of tgpu_hash_aggregation_factory_create (SINGLE /
+ *                 PARTIAL / FINAL); no hash channel.  One row per group, in stream order.  A group leaves with the add_input whose
+ *                 page holds the first row of the NEXT group, the last one with finish.
+ *   Key cells     those of the row the reference reads (:283-305,317-324), bit for bit (NaN payload, sign of zero): a group that ends
+ *                 inside page P takes the first row of its segment in P -- row 0 of P when it began on an earlier page; a group whose
+ *                 last row is the last row of P (flushed by the next page's first row or by finish) takes that last row of P.
+ *   Sums          DOUBLE sums and averages are the sequential additions of the group's rows in row order (the Java loop), always:
+ *                 tgpu_context_set_double_sum_order does not apply.  FINAL combines its intermediate rows in row order, too.
+ *                 sum(bigint): 128-bit accumulation, the total decides, as on the hash aggregation's paths.  An overflow fails the call
+ *                 that completes the group -- that add_input, or finish for the last group -- with TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE;
+ *                 no row of that page is emitted, pages handed out earlier stay valid.
+ *   Protocol      needs_input until finish, except while an output page waits to be fetched (:237-242); a page without rows is a
+ *                 no-op; no input, no output; is_finished once finish was called and the output is drained.
+ *   memory_bytes  the accumulator states of one page's groups, the carried key row and the pending output page: independent of the
+ *                 length of the stream.
+ * group_by_count == 0 is TGPU_ERR_INVALID_ARGUMENT (the planner streams only on non-empty pre-grouped keys; the global aggregation stays
+ * with the hash operator); more than 16 aggregates, unknown functions, channels out of range: TGPU_ERR_INVALID_ARGUMENT. */
+int32_t tgpu_streaming_aggregation_factory_create(tgpu_context *ctx, int32_t operator_id,
+                                                  int32_t type_count, const int32_t *types,
+                                                  int32_t group_by_count, const int32_t *group_by_channels, int32_t step,
+                                                  int32_t agg_count, const tgpu_agg_spec *aggs,
+                                                  tgpu_operator_factory **out);
+
 /* HashBuilderOperatorFactory + its JoinBridge (M/operator/HashBuilderOperator.java:54-152;
  * PartitionedLookupSourceFactory.java:110-124 with one partition per GPU). */
 int32_t tgpu_hash_builder_factory_create(tgpu_context *ctx, int32_t operator_id,

@@ -93,6 +93,8 @@ public final class GpuNative
             byte[] stringPool, int filterRoot, int[] projectionRoots);
     public static native long createHashAggregationFactory(long context, int operatorId, int[] groupByTypes, int[] groupByChannels, int hashChannel, int step,
             int[] aggregates, int expectedGroups, boolean produceDefaultOutput);
+    /** StreamingAggregationOperator (tgpu_streaming_aggregation_factory_create): aggregation over input grouped on the keys; aggregates as for createHashAggregationFactory */
+    public static native long createStreamingAggregationFactory(long context, int operatorId, int[] types, int[] groupByChannels, int step, int[] aggregates);
     /** FilterAndProject feeding HashAggregation as one fused pipeline (tgpu_filter_project_hash_aggregation_factory_create) */
     public static native long createFilterProjectHashAggregationFactory(long context, int operatorId, int[] inputTypes, int[][] nodes, long[] longValues, double[] doubleValues,
             byte[] stringPool, int filterRoot, int[] projectionRoots, int[] groupByTypes, int[] groupByChannels, int hashChannel, int step, int[] aggregates, int expectedGroups);

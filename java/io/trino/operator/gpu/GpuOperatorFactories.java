@@ -150,6 +150,29 @@ public final class GpuOperatorFactories
     }
 
     /**
+     * StreamingAggregationOperator.createOperatorFactory (operator/StreamingAggregationOperator.java:50-69), which the planner chooses when the input is
+     * already grouped on the keys (sql/planner/LocalExecutionPlanner.java:3022-3031).  The arguments are the reference's -- the AccumulatorFactories as the
+     * {tgpu_agg_function, input channel, mask channel} triples of hashAggregation, no JoinCompiler -- and the operator runs through the generic GpuOperator.
+     * No group-by channel, an unsupported type or an aggregate the caller could not resolve -> Optional.empty() (the Java operator stays).
+     */
+    public Optional<OperatorFactory> streamingAggregation(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Type> groupByTypes, List<Integer> groupByChannels, Step step,
+            Optional<int[]> aggregates)
+    {
+        if (aggregates.isEmpty() || stepCode(step) < 0 || groupByChannels.isEmpty() || groupByTypes.size() != groupByChannels.size()) {
+            return Optional.empty();
+        }
+        int[] types;
+        try {
+            types = GpuPages.typeCodes(sourceTypes);
+        }
+        catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        long factory = GpuNative.createStreamingAggregationFactory(context, operatorId, types, ints(groupByChannels), stepCode(step), aggregates.get());
+        return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuStreamingAggregationOperator", sourceTypes, poller, factory));
+    }
+
+    /**
      * A FilterNode / ProjectNode directly under an AggregationNode (LocalExecutionPlanner.visitAggregation over a filter/project source, :1198,2965-3056) as ONE
      * fused pipeline: tgpu_filter_project_hash_aggregation_factory_create, the operator bench.py's Q1 line times.  groupByChannels, hashChannel and the
      * aggregates' channels index the PROJECTIONS.  Same results as filterAndProject(...) feeding hashAggregation(...); SINGLE and PARTIAL steps.

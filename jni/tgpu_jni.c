@@ -439,6 +439,21 @@ JFN(jlong, createHashAggregationFactory)(JNIEnv *env, jclass c, jlong ctx, jint 
     return factory_result(env, rc, f);
 }
 
+/* StreamingAggregationOperator.createOperatorFactory (M/operator/StreamingAggregationOperator.java:50-69); aggregates as above */
+JFN(jlong, createStreamingAggregationFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray types, jintArray groupByChannels, jint step, jintArray aggregates)
+{
+    UNUSED(c);
+    ints t = ints_get(env, types), gc = ints_get(env, groupByChannels), ag = ints_get(env, aggregates);
+    tgpu_operator_factory *f = NULL;
+    const int malformed = ag.n % 3 != 0;
+    int32_t rc = malformed ? TGPU_ERR_INVALID_ARGUMENT
+                           : tgpu_streaming_aggregation_factory_create(H(tgpu_context, ctx), operatorId, t.n, (const int32_t *)t.p, gc.n, (const int32_t *)gc.p, step, ag.n / 3,
+                                                                       (const tgpu_agg_spec *)ag.p, &f);
+    ints_release(env, &ag); ints_release(env, &gc); ints_release(env, &t);
+    if (malformed) { throw_native_message(env, rc, "streaming aggregation: malformed aggregate array"); return 0; }
+    return factory_result(env, rc, f);
+}
+
 /* the fused FilterAndProject -> HashAggregation pipeline (tgpu_filter_project_hash_aggregation_factory_create): what bench.py's Q1 line times */
 JFN(jlong, createFilterProjectHashAggregationFactory)(JNIEnv *env, jclass c, jlong ctx, jint operatorId, jintArray inputTypes, PROGRAM_PARAMS, jintArray groupByTypes,
                                                       jintArray groupByChannels, jint hashChannel, jint step, jintArray aggregates, jint expectedGroups)

@@ -16,6 +16,7 @@ from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_
                         DistinctLimitOperatorFactory, MarkDistinctOperatorFactory,
                         LimitOperatorFactory, RowNumberOperatorFactory,
                         MergeOperator, MergeOperatorFactory,
+                        StreamingAggregationOperatorFactory,
                         DENSE_RANK, RANK, ROW_NUMBER, TopNRankingOperatorFactory,
                         FRAME_PARTITION, FRAME_RANGE_TO_CURRENT, FRAME_ROWS_TO_CURRENT, WINDOW_AGGREGATE, WINDOW_CUME_DIST, WINDOW_DENSE_RANK, WINDOW_FIRST_VALUE,
                         WINDOW_LAG, WINDOW_LAST_VALUE, WINDOW_LEAD, WINDOW_PERCENT_RANK, WINDOW_RANK, WINDOW_ROW_NUMBER, WindowFunction, WindowOperatorFactory,

@@ -131,6 +131,7 @@ SYMBOLS = {
     "tgpu_profile_dump": (i64, [vp, cp, i64]),
     "tgpu_filter_project_factory_create": (i32, [vp, i32, i32, P(i32), P(PageProcessorSpec), P(vp)]),
     "tgpu_hash_aggregation_factory_create": (i32, [vp, i32, i32, P(i32), P(i32), i32, i32, i32, P(AggSpec), i32, i32, P(vp)]),
+    "tgpu_streaming_aggregation_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, i32, P(AggSpec), P(vp)]),
     "tgpu_hash_builder_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, i32, P(vp), P(vp)]),
     "tgpu_partitioned_hash_builder_factory_create": (i32, [vp, i32, i32, P(i32), i32, P(i32), i32, P(i32), i32, i32, i32, P(vp), P(vp)]),
     "tgpu_partitioned_join_position_encode": (i64, [i32, i32, i32]),

@@ -33,7 +33,9 @@ inline int64_t ord_chain_max_groups() { const char *e = getenv("TGPU_ORD_CHAIN_M
 
 class GroupedAccumulators {
 public:
-    GroupedAccumulators(Context *ctx, std::vector<tgpu_agg_spec> specs, int32_t step);
+    // ordered_from_start: ORDERED from the first row on, whatever the number of groups (StreamingAggregationOperator: the reference has
+    // no other order there, and there is no mode prefix to wait for)
+    GroupedAccumulators(Context *ctx, std::vector<tgpu_agg_spec> specs, int32_t step, bool ordered_from_start = false);
 
     // raw input (SINGLE / PARTIAL): gids == nullptr means one global group 0
     // gids_ascending: the caller knows that the ids never decrease from row to row (the group-by's run route): the ORDERED mode then
@@ -45,6 +47,10 @@ public:
     void add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending = false);
     // appends the output channels for groups [0, group_count)
     void evaluate(int64_t group_count, std::vector<DeviceColumn> &out);
+    // ORDERED mode, page-local group ids (StreamingAggregationOperator): the state of group groups - 1, the group the page left open,
+    // moves to group 0 and groups [1, groups) are cleared -- counts, running sums, the 128-bit / extreme words -- and so is the error word.
+    // One launch, no read-back.
+    void carry_last_group(int64_t groups);
     // device state of aggregate k for groups [0, reserve()d): used by the JIT-fused project+accumulate kernels
     struct DeviceState {
         int32_t function;

@@ -757,8 +757,12 @@ BufferPtr grow(Context *ctx, BufferPtr old, int64_t old_elems, int64_t new_elems
 
 }  // namespace
 
-GroupedAccumulators::GroupedAccumulators(Context *ctx, std::vector<tgpu_agg_spec> specs, int32_t step) : ctx_(ctx), step_(step)
+GroupedAccumulators::GroupedAccumulators(Context *ctx, std::vector<tgpu_agg_spec> specs, int32_t step, bool ordered_from_start) : ctx_(ctx), step_(step)
 {
+    if (ordered_from_start) {   // (before any state exists: ensure() gives DOUBLE states their running sums, no limbs)
+        mode_ = Mode::ORDERED;
+        allow_ordered_ = force_ordered_ = true;
+    }
     TG_CHECK_ARG((int)specs.size() <= kMaxAggs, "at most 16 aggregates per operator");
     for (auto &s : specs) {
         TG_CHECK_ARG(s.function >= TGPU_AGG_COUNT_ALL && s.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
@@ -963,6 +967,58 @@ void GroupedAccumulators::merge(const int32_t *gids, const HostStates &run, int6
     agg_merge_states_kernel<<<grid_for(ctx_, run.groups * kLimbs), kBlock, 0, ctx_->stream()>>>(args, gids, run.groups);
     check_launch("agg_merge_states");
     ctx_->sync();
+}
+
+namespace {
+struct CarryArgs {
+    int32_t n_aggs, pad;
+    struct A {
+        long long *counts;
+        double *dsum;
+        unsigned long long *i128;
+    } a[kMaxAggs];
+};
+
+// one thread per group in [1, groups): the thread of the last group copies its state to group 0 first; every thread clears its own group.
+// Nobody else reads or writes group 0 or the last group, so the launch needs no order among its threads.
+__global__ void __launch_bounds__(kBlock) agg_carry_kernel(CarryArgs args, int64_t groups, unsigned int *error)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *error = 0;
+    for (int64_t g = 1 + (int64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += (int64_t)gridDim.x * kBlock) {
+        const bool last = g == groups - 1;
+        for (int k = 0; k < args.n_aggs; k++) {
+            const CarryArgs::A &a = args.a[k];
+            if (last) {
+                a.counts[0] = a.counts[g];
+                if (a.dsum) a.dsum[0] = a.dsum[g];
+                if (a.i128) {
+                    a.i128[0] = a.i128[g * 2];
+                    a.i128[1] = a.i128[g * 2 + 1];
+                }
+            }
+            a.counts[g] = 0;
+            if (a.dsum) a.dsum[g] = 0.0;
+            if (a.i128) a.i128[g * 2] = a.i128[g * 2 + 1] = 0ULL;
+        }
+    }
+}
+}  // namespace
+
+void GroupedAccumulators::carry_last_group(int64_t groups)
+{
+    if (states_.empty() || groups <= 1) return;   // (one group: it is group 0 already)
+    TG_CHECK_STATE(mode_ == Mode::ORDERED, "carrying a group needs row-order states");
+    ensure(groups);
+    CarryArgs args{};
+    args.n_aggs = (int32_t)states_.size();
+    for (size_t k = 0; k < states_.size(); k++) {
+        const DeviceState d = device_state((int)k);
+        TG_CHECK_STATE(d.limbs == nullptr, "carrying a group needs row-order states");
+        args.a[k] = {d.counts, d.dsum, d.i128};
+    }
+    ProfileScope ps(ctx_, "sagg_carry");
+    agg_carry_kernel<<<grid_for(ctx_, groups - 1), kBlock, 0, ctx_->stream()>>>(args, groups, error_->as<unsigned int>());
+    check_launch("sagg_carry");
 }
 
 GroupedAccumulators::DeviceState GroupedAccumulators::device_state(int k) const

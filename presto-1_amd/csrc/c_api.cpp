@@ -459,6 +459,28 @@ int32_t tgpu_hash_aggregation_factory_create(tgpu_context *ctx, int32_t operator
     });
 }
 
+int32_t tgpu_streaming_aggregation_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types, int32_t group_by_count,
+                                                  const int32_t *group_by_channels, int32_t step, int32_t agg_count, const tgpu_agg_spec *aggs,
+                                                  tgpu_operator_factory **out)
+{
+    return guard_on(ctx_of(ctx), [&] {
+        TG_CHECK_ARG(ctx && out, "null argument");
+        TG_CHECK_ARG(type_count >= 0 && (type_count == 0 || types != nullptr), "null type array");
+        TG_CHECK_ARG(group_by_count > 0 && group_by_channels != nullptr, "streaming aggregation needs at least one group-by channel");
+        TG_CHECK_ARG(agg_count >= 0 && (agg_count == 0 || aggs != nullptr), "null aggregate array");
+        StreamingAggregationConfig cfg;
+        cfg.types = vec(types, type_count);
+        cfg.group_by_channels = vec(group_by_channels, group_by_count);
+        for (int32_t ch : cfg.group_by_channels) {
+            TG_CHECK_ARG(ch >= 0 && ch < type_count, "group-by channel out of range");
+            cfg.group_by_types.push_back(cfg.types[(size_t)ch]);
+        }
+        cfg.step = step;
+        cfg.aggs.assign(aggs, aggs + agg_count);
+        make_factory<StreamingAggregationOperatorFactory>(ctx, out, operator_id, std::move(cfg));
+    });
+}
+
 int32_t tgpu_hash_builder_factory_create(tgpu_context *ctx, int32_t operator_id, int32_t type_count, const int32_t *types,
                                          int32_t output_channel_count, const int32_t *output_channels, int32_t hash_channel_count,
                                          const int32_t *hash_channels, int32_t precomputed_hash_channel, int32_t expected_positions,

@@ -784,6 +784,150 @@ static void validate(Context *, const HashAggregationConfig &cfg)
 }
 
 // =====================================================================================================================
+// StreamingAggregationOperator (M/operator/StreamingAggregationOperator.java:216-347): the input arrives grouped on the keys, a group is a
+// maximal run of consecutive rows whose key rows are not distinct (rowNotDistinctFromRow), across any number of pages.
+//   per page   sagg_detect numbers the page's runs 0.. (id 0 = the group the previous page left open, if row 0 continues it -- or a
+//              group without a row here, if it does not), the accumulators -- ORDERED from the start -- add the rows in row order from
+//              those ascending ids, groups [0, g - 1) are evaluated and leave as one page, group g - 1's state moves to group 0
+//              (GroupedAccumulators::carry_last_group) and the page's last row becomes the carried key row (currentGroup, :303).
+//   key cells  :283-305,317-324: a group that ends inside the page takes the first row of its segment in this page (row 0 for a group that
+//              began earlier); a group flushed by the next page's first row or by finish takes the carried row = the last row of its page.
+//   raises     sum(bigint) overflow: the add_input whose page completes the group, or finish for the last group; nothing of that page
+//              is emitted.
+// Input pages are not coalesced: every page pays its launches and its read-back.
+// =====================================================================================================================
+class StreamingAggregationOperator : public Operator {
+public:
+    StreamingAggregationOperator(Context *ctx, int32_t id, const StreamingAggregationConfig &cfg)
+        : Operator(ctx, id), cfg_(cfg), accs_(ctx, cfg.aggs, cfg.step, /*ordered_from_start=*/true)
+    {
+    }
+
+    bool needs_input() override { return !finishing_ && output_.empty(); }   // :237-242: queued output goes out before the next page comes in
+    void add_input(const tgpu_page *page) override
+    {
+        ready();
+        process(ingest_page(ctx_, page));
+    }
+    void add_input_owned(const DevicePage &page) override
+    {
+        ready();
+        process(page);
+    }
+    std::unique_ptr<OutputPage> get_output() override
+    {
+        if (output_.empty()) return nullptr;
+        std::unique_ptr<OutputPage> out = std::move(output_.front());
+        output_.pop_front();
+        return out;
+    }
+    // :219-235: the open group is evaluated and flushed
+    void finish() override
+    {
+        if (finishing_) return;
+        finishing_ = true;
+        if (carry_.empty()) return;
+        DevicePage out;
+        out.n = 1;
+        out.cols = std::move(carry_);
+        carry_.clear();
+        accs_.evaluate(1, out.cols);
+        output_.push_back(wrap(std::move(out)));
+    }
+    bool is_finished() override { return finishing_ && output_.empty(); }
+    int64_t memory_bytes() override
+    {
+        int64_t s = accs_.estimated_size();
+        for (const DeviceColumn &c : carry_) s += c.size_in_bytes();
+        for (const auto &p : output_) s += p->page.size_in_bytes();
+        return s;
+    }
+
+private:
+    void ready()
+    {
+        TG_CHECK_STATE(!finishing_, "Operator is already finishing");
+        TG_CHECK_STATE(output_.empty(), "Operator still has pending output");
+    }
+
+    DeviceColumn gather_keys(const DeviceColumn &src, const int32_t *positions, int64_t rows)
+    {
+        DeviceColumn c = k::gather_column(ctx_, src, positions, rows, false);
+        if (c.type == TGPU_VARCHAR) {   // the gather's offsets start at 0 and end at its byte total
+            c.pool_exact = true;
+            c.pool_first = 0;
+        }
+        return c;
+    }
+
+    void process(const DevicePage &in)
+    {
+        check_page_types(in, cfg_.types);
+        if (in.n == 0) return;
+        std::vector<const DeviceColumn *> keys;
+        for (int32_t ch : cfg_.group_by_channels) keys.push_back(&in.cols[(size_t)ch]);
+        const SaggGroups det = sagg_detect(ctx_, keys, in.n, carry_.empty() ? nullptr : &carry_);
+        const int64_t groups = det.groups();
+        const int32_t *gids = det.gids->as<int32_t>();
+        if (cfg_.step == TGPU_STEP_FINAL) accs_.add_intermediate(gids, in.n, in, groups, true);
+        else accs_.add_input(gids, in.n, in, groups, true);
+        const int64_t completed = groups - 1;
+        if (completed > 0) {
+            // every segment but the last is a completed group and brings its first row; with `shift` the carried group comes in front
+            const int64_t from_page = det.segments - 1;
+            DevicePage out;
+            out.n = completed;
+            if (from_page > 0)
+                for (const DeviceColumn *kc : keys) out.cols.push_back(gather_keys(*kc, det.starts->as<int32_t>(), from_page));
+            if (det.shift && from_page == 0) out.cols = carry_;
+            else if (det.shift) {
+                PagesIndexGpu both(ctx_, cfg_.group_by_types);
+                DevicePage first, rest;
+                first.n = 1;
+                first.cols = carry_;
+                rest.n = from_page;
+                rest.cols = std::move(out.cols);
+                both.add_page(first);
+                both.add_page(rest);
+                out.cols.clear();
+                for (int c = 0; c < (int)keys.size(); c++) out.cols.push_back(both.column(c));
+            }
+            accs_.evaluate(completed, out.cols);   // (may raise: nothing of this page has been queued)
+            output_.push_back(wrap(std::move(out)));
+            accs_.carry_last_group(groups);
+        }
+        // currentGroup = the page's last row, as an owned one-row page (:303)
+        BufferPtr last = ctx_->alloc(4);
+        k::fill_i32(ctx_, last->as<int32_t>(), (int32_t)(in.n - 1), 1);
+        std::vector<DeviceColumn> carry;
+        for (const DeviceColumn *kc : keys) carry.push_back(gather_keys(*kc, last->as<int32_t>(), 1));
+        carry_ = std::move(carry);
+    }
+
+    StreamingAggregationConfig cfg_;
+    GroupedAccumulators accs_;
+    std::vector<DeviceColumn> carry_;   // the key cells of the open group's reference row; empty: no group is open
+    std::deque<std::unique_ptr<OutputPage>> output_;
+    bool finishing_ = false;
+};
+
+static void validate(Context *, const StreamingAggregationConfig &cfg)
+{
+    TG_CHECK_ARG(!cfg.group_by_channels.empty(), "streaming aggregation needs at least one group-by channel (a global aggregation stays with the hash operator)");
+    TG_CHECK_ARG((int)cfg.group_by_channels.size() <= kMaxKeyChannels, "at most 8 group-by channels");
+    TG_CHECK_ARG(cfg.step >= TGPU_STEP_SINGLE && cfg.step <= TGPU_STEP_FINAL, "unknown aggregation step");
+    TG_CHECK_ARG((int)cfg.aggs.size() <= kMaxAggs, "at most 16 aggregates");
+    for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown channel type");
+    for (int32_t ch : cfg.group_by_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)cfg.types.size(), "group-by channel out of range");
+    for (auto &a : cfg.aggs) {
+        TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
+        TG_CHECK_ARG(a.function == TGPU_AGG_COUNT_ALL || (a.input_channel >= 0 && a.input_channel < (int)cfg.types.size()), "aggregate input channel out of range");
+        TG_CHECK_ARG(a.mask_channel < (int)cfg.types.size(), "aggregate mask channel out of range");
+        if (a.mask_channel >= 0) TG_CHECK_ARG(cfg.types[(size_t)a.mask_channel] == TGPU_BOOLEAN, "aggregate mask channel is not BOOLEAN");
+    }
+}
+
+// =====================================================================================================================
 // HashBuilderOperator (M/operator/HashBuilderOperator.java:155-191 state machine, spill states omitted: the GPU path reports
 // its memory as non-revocable and never spills)
 // =====================================================================================================================
@@ -3560,6 +3704,7 @@ void partitioned_output_info(Operator *op, int64_t *rows_added, int64_t *pages_a
 template class SimpleOperatorFactory<FilterAndProjectConfig, FilterAndProjectOperator>;
 template class SimpleOperatorFactory<ScanFilterAndProjectConfig, ScanFilterAndProjectOperator>;
 template class SimpleOperatorFactory<HashAggregationConfig, HashAggregationOperator>;
+template class SimpleOperatorFactory<StreamingAggregationConfig, StreamingAggregationOperator>;
 template class SimpleOperatorFactory<TopNConfig, TopNOperator>;
 template class SimpleOperatorFactory<OrderByConfig, OrderByOperator>;
 template class SimpleOperatorFactory<MergeConfig, MergeOperator>;

@@ -15,6 +15,7 @@
 #include "join.h"
 #include "merge.h"
 #include "semijoin.h"
+#include "streaming_agg.h"
 #include "topn.h"
 #include "topn_ranking.h"
 #include "window.h"
@@ -120,6 +121,16 @@ struct HashAggregationConfig {
 };
 
 using HashAggregationOperatorFactory = SimpleOperatorFactory<HashAggregationConfig, class HashAggregationOperator>;   // spill_enabled / max_partial_memory: config()
+
+// ---- StreamingAggregationOperator (M/operator/StreamingAggregationOperator.java:50-69,216-347): aggregation over input that arrives
+// grouped on the keys.  No table: a group is emitted as soon as the next key starts, the state is one group.
+struct StreamingAggregationConfig {
+    std::vector<int32_t> types;   // source types
+    std::vector<int32_t> group_by_types, group_by_channels;
+    int32_t step = TGPU_STEP_SINGLE;
+    std::vector<tgpu_agg_spec> aggs;
+};
+using StreamingAggregationOperatorFactory = SimpleOperatorFactory<StreamingAggregationConfig, class StreamingAggregationOperator>;   // duplicate(): :135-139
 
 // ---- JoinFilterFunction (M/operator/JoinHash.java:44-47,118-130; M/sql/gen/JoinFilterFunctionCompiler.java): a predicate over
 // (build row, probe row) that a join position must pass besides key equality.  Input channels [0, build types) of the expression

@@ -449,6 +449,24 @@ class HashAggregationOperatorFactory(OperatorFactory):
             self.setSpillEnabled(True)
 
 
+class StreamingAggregationOperatorFactory(OperatorFactory):
+    """StreamingAggregationOperator.createOperatorFactory (M/operator/StreamingAggregationOperator.java:50-69): aggregation over input that
+    arrives grouped on the keys.  types: the source types; aggs: list of (function, input_channel[, mask_channel]).  Output: the keys, then
+    the aggregates in HashAggregationOperatorFactory's layouts, one row per run of not-distinct key rows, in stream order."""
+
+    def __init__(self, ctx: Context, operator_id, types, group_by_channels, step, aggs):
+        t, nt = _i32(types)
+        gc, ng = _i32(group_by_channels)
+        if ng == 0:   # (the library says the same; said here, it needs neither the library nor a device)
+            raise _lib.TgpuError(-1, "streaming aggregation needs at least one group-by channel (a global aggregation stays with the hash operator)")
+        arr = (_lib.AggSpec * max(1, len(aggs)))()
+        for i, a in enumerate(aggs):
+            arr[i] = _lib.AggSpec(a[0], a[1], a[2] if len(a) > 2 else -1)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tgpu_streaming_aggregation_factory_create(ctx.handle, operator_id, nt, t, ng, gc, step, len(aggs), arr, C.byref(h)))
+        super().__init__(h)
+
+
 class LookupSourceFactory:
     """The JoinBridge between the build and probe pipelines (M/operator/PartitionedLookupSourceFactory.java)."""
 
