@@ -340,8 +340,24 @@ typedef enum tgpu_agg_function {
     TGPU_AGG_MIN_BIGINT = 7,    /* min(bigint)     AbstractMinMaxAggregationFunction.java:233-289 (LONG_INPUT / LONG_COMBINE, NullableLongState) */
     TGPU_AGG_MAX_BIGINT = 8,    /* max(bigint)     the same with the comparison turned round (MaxAggregationFunction.java) */
     TGPU_AGG_MIN_DOUBLE = 9,    /* min(double)     :227-230,291-306 with Double.compare (DoubleType.java:194-198): -0.0 < +0.0, NaN above +inf */
-    TGPU_AGG_MAX_DOUBLE = 10    /* max(double)     M/util/MinMaxCompare.java maxDouble: value > state || isNaN(state).  A NaN result is the canonical NaN; among
+    TGPU_AGG_MAX_DOUBLE = 10,   /* max(double)     M/util/MinMaxCompare.java maxDouble: value > state || isNaN(state).  A NaN result is the canonical NaN; among
                                  *                 zeros of both signs as the maximum +0.0 is returned (the reference: the one that came first) */
+    /* IntegerType and DateType are long.class types, so AbstractMinMaxAggregationFunction.java:118-128,160-190 picks NullableLongState and the
+     * LONG_INPUT / LONG_COMBINE methods for them as for BIGINT: signed 32-bit order, the intermediate value is BIGINT.  Hash aggregation (spilled
+     * or not), the fused filter/project aggregation and the streaming aggregation take them; window aggregates do not. */
+    TGPU_AGG_MIN_INTEGER = 11,  /* min(integer)    one INTEGER channel; output INTEGER */
+    TGPU_AGG_MAX_INTEGER = 12,  /* max(integer) */
+    TGPU_AGG_MIN_DATE = 13,     /* min(date)       one DATE channel (days since the epoch, int32); output DATE */
+    TGPU_AGG_MAX_DATE = 14,     /* max(date) */
+    /* VARCHAR is a Slice type: the state is the BlockPositionState of :118-128,160-190, whose input / combine keep the position the
+     * comparison prefers (:245,269,325) -- Slice.compareTo: unsigned bytes left to right, a proper prefix sorts first; '' is a value, not
+     * NULL; equal strings are byte-identical, so which one is kept cannot be observed.  Plain hash aggregation only (grouped or global,
+     * SINGLE / PARTIAL / FINAL, masks): tgpu_hash_aggregation_factory_set_spill_enabled(1) fails with TGPU_ERR_NOT_SUPPORTED, "min / max
+     * over VARCHAR cannot spill" (the factory stays usable unspilled), and the fused and the streaming aggregation factories fail with
+     * TGPU_ERR_NOT_SUPPORTED at creation.  A result channel of more than 2^31 - 1 bytes fails with TGPU_ERR_INSUFFICIENT_RESOURCES,
+     * "variable width block cannot exceed 2GB". */
+    TGPU_AGG_MIN_VARCHAR = 15,  /* min(varchar)    one VARCHAR channel; output VARCHAR */
+    TGPU_AGG_MAX_VARCHAR = 16   /* max(varchar) */
 } tgpu_agg_function;
 
 typedef struct tgpu_agg_spec {
@@ -355,7 +371,13 @@ typedef enum tgpu_agg_step { TGPU_STEP_SINGLE = 0, TGPU_STEP_PARTIAL = 1, TGPU_S
 /* HashAggregationOperatorFactory (M/operator/HashAggregationOperator.java:54-262).  Output channels: group-by keys,
  * [hash channel if hash_channel >= 0], then one channel per aggregate (PARTIAL: two channels per sum / avg / min / max = count BIGINT,
  * sum DOUBLE|BIGINT or the extreme BIGINT -- the flattened LongDoubleState / LongLongState / NullableLongState, count 0 = null state;
- * FINAL consumes that layout). */
+ * FINAL consumes that layout).  min / max over INTEGER and DATE: SINGLE / FINAL give one channel of the input's own type (int32
+ * storage), NULL for a group without an unmasked non-null row; PARTIAL gives count BIGINT, extreme BIGINT (the sign-extended value, 0
+ * where the count is 0) -- min(bigint)'s layout, the reference's intermediate type is BIGINT too -- and FINAL narrows it again.
+ * min / max over VARCHAR: SINGLE / FINAL give one VARCHAR channel, NULL for a group without an unmasked non-null row; PARTIAL gives
+ * count BIGINT, value VARCHAR, the cell NULL and empty where the count is 0; FINAL ignores the value cell of a row whose count is 0,
+ * whatever its null flag, and adds the counts.  A raw input channel of another type than the function's fails the first add_input with
+ * TGPU_ERR_INVALID_ARGUMENT. */
 int32_t tgpu_hash_aggregation_factory_create(tgpu_context *ctx, int32_t operator_id,
                                              int32_t group_by_count, const int32_t *group_by_types, const int32_t *group_by_channels,
                                              int32_t hash_channel /* -1 = none */, int32_t step,

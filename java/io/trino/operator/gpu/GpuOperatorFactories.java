@@ -123,7 +123,8 @@ public final class GpuOperatorFactories
 
     /**
      * HashAggregationOperatorFactory (operator/HashAggregationOperator.java:54-262).  aggregates: {tgpu_agg_function, input channel, mask channel} triples
-     * resolved by the caller from the AccumulatorFactories' bound signatures (count / sum / avg over BIGINT and DOUBLE, min / max over BIGINT and DOUBLE; anything else -> Optional.empty()).
+     * resolved by the caller from the AccumulatorFactories' bound signatures (count / sum / avg over BIGINT and DOUBLE, min / max over BIGINT, DOUBLE, INTEGER, DATE and VARCHAR; anything else -> Optional.empty()).
+     * min / max over VARCHAR cannot spill: with spillEnabled such a plan keeps the Java operator.
      */
     public Optional<OperatorFactory> hashAggregation(int operatorId, PlanNodeId planNodeId, List<Type> inputTypes, List<Type> groupByTypes, List<Integer> groupByChannels, Step step,
             Optional<int[]> aggregates, Optional<Integer> hashChannel, int expectedGroups, boolean produceDefaultOutput, Optional<DataSize> maxPartialMemory, boolean spillEnabled)
@@ -137,6 +138,9 @@ public final class GpuOperatorFactories
             keyTypes = GpuPages.typeCodes(groupByTypes);
         }
         catch (IllegalArgumentException unsupportedType) {
+            return Optional.empty();
+        }
+        if (spillEnabled && hasVarcharExtreme(aggregates.get())) {
             return Optional.empty();
         }
         long factory = GpuNative.createHashAggregationFactory(context, operatorId, keyTypes, ints(groupByChannels), hashChannel.orElse(-1), stepCode(step), aggregates.get(),
@@ -153,12 +157,13 @@ public final class GpuOperatorFactories
      * StreamingAggregationOperator.createOperatorFactory (operator/StreamingAggregationOperator.java:50-69), which the planner chooses when the input is
      * already grouped on the keys (sql/planner/LocalExecutionPlanner.java:3022-3031).  The arguments are the reference's -- the AccumulatorFactories as the
      * {tgpu_agg_function, input channel, mask channel} triples of hashAggregation, no JoinCompiler -- and the operator runs through the generic GpuOperator.
-     * No group-by channel, an unsupported type or an aggregate the caller could not resolve -> Optional.empty() (the Java operator stays).
+     * No group-by channel, an unsupported type, an aggregate the caller could not resolve or min / max over VARCHAR (hash aggregation only) ->
+     * Optional.empty() (the Java operator stays).
      */
     public Optional<OperatorFactory> streamingAggregation(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Type> groupByTypes, List<Integer> groupByChannels, Step step,
             Optional<int[]> aggregates)
     {
-        if (aggregates.isEmpty() || stepCode(step) < 0 || groupByChannels.isEmpty() || groupByTypes.size() != groupByChannels.size()) {
+        if (aggregates.isEmpty() || stepCode(step) < 0 || groupByChannels.isEmpty() || groupByTypes.size() != groupByChannels.size() || hasVarcharExtreme(aggregates.get())) {
             return Optional.empty();
         }
         int[] types;
@@ -176,12 +181,13 @@ public final class GpuOperatorFactories
      * A FilterNode / ProjectNode directly under an AggregationNode (LocalExecutionPlanner.visitAggregation over a filter/project source, :1198,2965-3056) as ONE
      * fused pipeline: tgpu_filter_project_hash_aggregation_factory_create, the operator bench.py's Q1 line times.  groupByChannels, hashChannel and the
      * aggregates' channels index the PROJECTIONS.  Same results as filterAndProject(...) feeding hashAggregation(...); SINGLE and PARTIAL steps.
+     * min / max over VARCHAR is not fused: Optional.empty(), and the caller composes filterAndProject(...) and hashAggregation(...).
      */
     public Optional<OperatorFactory> filterProjectHashAggregation(int operatorId, PlanNodeId planNodeId, List<Type> inputTypes, Optional<RowExpression> filter,
             List<RowExpression> projections, List<Type> groupByTypes, List<Integer> groupByChannels, Step step, Optional<int[]> aggregates, Optional<Integer> hashChannel,
             int expectedGroups, Optional<DataSize> maxPartialMemory, boolean spillEnabled)
     {
-        if (aggregates.isEmpty() || (step != Step.SINGLE && step != Step.PARTIAL)) {
+        if (aggregates.isEmpty() || (step != Step.SINGLE && step != Step.PARTIAL) || hasVarcharExtreme(aggregates.get())) {
             return Optional.empty();
         }
         int[] types;
@@ -206,6 +212,17 @@ public final class GpuOperatorFactories
             GpuNative.setSpillEnabled(factory, true);
         }
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuFilterProjectHashAggregationOperator", inputTypes, poller, factory));
+    }
+
+    /** TGPU_AGG_MIN_VARCHAR = 15 / TGPU_AGG_MAX_VARCHAR = 16 among the {function, input channel, mask channel} triples (include/tgpu.h) */
+    private static boolean hasVarcharExtreme(int[] aggregates)
+    {
+        for (int i = 0; i + 2 < aggregates.length; i += 3) {
+            if (aggregates[i] == 15 || aggregates[i] == 16) {
+                return true;
+            }
+        }
+        return false;
     }
 
     /** the join bridge handle (tgpu_lookup_source_factory*) plays the JoinBridgeManager's role (operator/PartitionedLookupSourceFactory.java:146-205) */

@@ -17,6 +17,7 @@ from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_
                         LimitOperatorFactory, RowNumberOperatorFactory,
                         MergeOperator, MergeOperatorFactory,
                         StreamingAggregationOperatorFactory,
+                        MIN_INTEGER, MAX_INTEGER, MIN_DATE, MAX_DATE, MIN_VARCHAR, MAX_VARCHAR,
                         DENSE_RANK, RANK, ROW_NUMBER, TopNRankingOperatorFactory,
                         FRAME_PARTITION, FRAME_RANGE_TO_CURRENT, FRAME_ROWS_TO_CURRENT, WINDOW_AGGREGATE, WINDOW_CUME_DIST, WINDOW_DENSE_RANK, WINDOW_FIRST_VALUE,
                         WINDOW_LAG, WINDOW_LAST_VALUE, WINDOW_LEAD, WINDOW_PERCENT_RANK, WINDOW_RANK, WINDOW_ROW_NUMBER, WindowFunction, WindowOperatorFactory,

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "minmax_varchar.h"
 
 namespace tgpu {
 
@@ -29,6 +30,24 @@ constexpr int kMaxAggs = 16;
 constexpr int64_t kOrdChainMaxGroups = 65536, kOrdChainMinRows = 256;
 // one lane per group: a lane hands its group over to the chained kernel after this many rows (0.5 ms of a lane's time)
 constexpr int64_t kOrdHandoffRows = 4096;
+// min / max over INTEGER and DATE (long.class types over NullableLongState like BIGINT): the kernels run them as the BIGINT functions over
+// the sign-extended value -- 4-byte signed load of raw input, 8-byte intermediates, 4-byte store of the output -- and never see these codes
+inline int32_t agg_kernel_function(int32_t f)
+{
+    if (f == TGPU_AGG_MIN_INTEGER || f == TGPU_AGG_MIN_DATE) return TGPU_AGG_MIN_BIGINT;
+    if (f == TGPU_AGG_MAX_INTEGER || f == TGPU_AGG_MAX_DATE) return TGPU_AGG_MAX_BIGINT;
+    return f;
+}
+// the int32-stored type of such an aggregate's input and output channel, 0 for every other function
+inline int32_t agg_narrow_type(int32_t f)
+{
+    if (f == TGPU_AGG_MIN_INTEGER || f == TGPU_AGG_MAX_INTEGER) return TGPU_INTEGER;
+    if (f == TGPU_AGG_MIN_DATE || f == TGPU_AGG_MAX_DATE) return TGPU_DATE;
+    return 0;
+}
+// min / max over VARCHAR: state of variable width, kept beside the fixed-width states and run as launches of their own (minmax_varchar.h)
+inline bool agg_is_varchar_extreme(int32_t f) { return f == TGPU_AGG_MIN_VARCHAR || f == TGPU_AGG_MAX_VARCHAR; }
+inline bool agg_function_known(int32_t f) { return f >= TGPU_AGG_COUNT_ALL && f <= TGPU_AGG_MAX_VARCHAR; }
 inline int64_t ord_chain_max_groups() { const char *e = getenv("TGPU_ORD_CHAIN_MAX_GROUPS"); return e ? atoll(e) : kOrdChainMaxGroups; }   // (the variable: kernel study)
 
 class GroupedAccumulators {
@@ -114,6 +133,7 @@ public:
     // from then on (a run's running double sums are added exactly, as one addend each)
     void merge(const int32_t *gids, const HostStates &run, int64_t live_groups);
     const std::vector<tgpu_agg_spec> specs() const;
+    bool has_varchar_extremes() const { return !vstates_.empty(); }
     int output_channel_count() const;
     int intermediate_channel_count() const;
     int64_t estimated_size() const;
@@ -128,6 +148,24 @@ private:
         BufferPtr dsum;     // double[g]: ORDERED mode running sums (instead of limbs / special)
         int64_t cap = 0;
     };
+    // min / max over VARCHAR are not among `states_`: none of the accumulate kernels, their LDS layouts, the mode decision, the fold
+    // scratch or the spill code knows them.  add_input / add_intermediate run them after the page's other aggregates, whatever the mode
+    // and whether or not the page has group ids; evaluate puts their channels where the caller's aggregate list has them.
+    struct VarcharState {
+        tgpu_agg_spec spec;
+        std::unique_ptr<VarcharExtremes> acc;
+    };
+    struct Slot {
+        bool varchar;
+        int index;   // into vstates_ or states_
+    };
+    std::vector<VarcharState> vstates_;
+    std::vector<Slot> order_;   // the caller's aggregate list
+    void add_varchar(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool intermediate);
+    void add_input_states(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending);
+    void add_intermediate_states(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending);
+    void evaluate_states(int64_t group_count, std::vector<DeviceColumn> &out);
+    std::vector<tgpu_agg_spec> state_specs() const;   // the fixed-width states' specs: what the LDS layouts are sized by
     enum class Mode { UNDECIDED, EXACT, ORDERED };
     void ensure(int64_t groups);
     void decide_mode(int64_t groups, int64_t lowcard_max_groups);

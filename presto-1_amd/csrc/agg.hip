@@ -15,8 +15,8 @@ namespace {
 constexpr int kBlock = 256;
 
 struct AggView {
-    int32_t function;
-    int32_t pad;
+    int32_t function;            // the function the kernels run (agg_kernel_function: INTEGER / DATE extremes arrive as the BIGINT ones)
+    int32_t narrow;              // 1: the raw input channel holds int32 (INTEGER / DATE), the kernels sign-extend it
     const void *input;           // values of the input channel (or nullptr for count(*))
     const uint8_t *input_nulls;
     const uint8_t *mask;         // BOOLEAN mask channel values
@@ -37,6 +37,11 @@ struct AggArgs {
 };
 
 #define kulisch_add tg_kulisch_add
+// the 8 bytes of row r's raw input cell as tg_minmax_encode takes them (min / max only: a.narrow is set for no other function)
+__device__ __forceinline__ unsigned long long minmax_raw(const AggView &a, int64_t r)
+{
+    return a.narrow ? (unsigned long long)(long long)((const int *)a.input)[r] : ((const unsigned long long *)a.input)[r];
+}
 #define i128_add tg_i128_add
 
 template <bool INTERMEDIATE>
@@ -73,7 +78,7 @@ __global__ void __launch_bounds__(kBlock) agg_accumulate_kernel(AggArgs args, co
             case TGPU_AGG_MIN_BIGINT:
             case TGPU_AGG_MAX_BIGINT:
             case TGPU_AGG_MIN_DOUBLE:
-            case TGPU_AGG_MAX_DOUBLE: tg_minmax_update(&a.i128[g * 2], tg_minmax_encode(a.function, ((const unsigned long long *)a.input)[r])); break;
+            case TGPU_AGG_MAX_DOUBLE: tg_minmax_update(&a.i128[g * 2], tg_minmax_encode(a.function, minmax_raw(a, r))); break;
             case TGPU_AGG_SUM_DOUBLE:
             case TGPU_AGG_AVG_DOUBLE: kulisch_add(&a.limbs[g * kLimbs], &a.special[g], ((const double *)a.input)[r]); break;
             case TGPU_AGG_AVG_BIGINT: kulisch_add(&a.limbs[g * kLimbs], &a.special[g], (double)((const long long *)a.input)[r]); break;
@@ -173,7 +178,7 @@ __global__ void __launch_bounds__(kBlock) agg_ordered_kernel(AggArgs args, const
                 case TGPU_AGG_MAX_BIGINT:
                 case TGPU_AGG_MIN_DOUBLE:
                 case TGPU_AGG_MAX_DOUBLE: {
-                    const unsigned long long c_ = tg_minmax_encode(a.function, ((const unsigned long long *)a.input)[r]);
+                    const unsigned long long c_ = tg_minmax_encode(a.function, minmax_raw(a, r));
                     best = c_ > best ? c_ : best;
                     break;
                 }
@@ -259,7 +264,7 @@ __device__ inline void ordered_chain_group(const AggArgs &args, const OrdChainPl
                     }
                 }
                 else if (tg_is_minmax(a.function)) {
-                    if (take) tg_minmax_update(&a.i128[g * 2], tg_minmax_encode(a.function, ((const unsigned long long *)a.input)[row]));
+                    if (take) tg_minmax_update(&a.i128[g * 2], tg_minmax_encode(a.function, minmax_raw(a, row)));
                 }
                 else if (plan.slot[k] >= 0 && live) {
                     double x = -0.0;
@@ -421,7 +426,11 @@ __global__ void __launch_bounds__(kBlock) agg_ordered_runs_kernel(AggArgs args, 
                 mkn[it] = 0;
                 inn[it] = 0;
             }
-            if (slot >= 0) {
+            if (slot >= 0 && a.narrow) {
+#pragma unroll
+                for (int it = 0; it < kOrdRunIters; it++) raw[it] = (unsigned long long)(long long)((const int *)a.input)[row[it]];
+            }
+            else if (slot >= 0) {
 #pragma unroll
                 for (int it = 0; it < kOrdRunIters; it++) raw[it] = ((const unsigned long long *)a.input)[row[it]];
             }
@@ -508,7 +517,7 @@ __global__ void __launch_bounds__(kBlock) agg_ordered_runs_kernel(AggArgs args, 
                     if (a.function != TGPU_AGG_COUNT_ALL && a.input_nulls && a.input_nulls[r]) continue;
                     cnt++;
                     if (slot < 0) continue;
-                    const unsigned long long x = ord_run_addend(a.function, ((const unsigned long long *)a.input)[r], true);
+                    const unsigned long long x = ord_run_addend(a.function, a.narrow ? minmax_raw(a, r) : ((const unsigned long long *)a.input)[r], true);
                     if (a.function == TGPU_AGG_SUM_BIGINT) big += (long long)x;
                     else if (tg_is_minmax(a.function)) best = x > best ? x : best;
                     else s += __longlong_as_double((long long)x);
@@ -562,7 +571,7 @@ __global__ void __launch_bounds__(kBlock) agg_lowcard_kernel(AggArgs args, LowCa
             if (a.function != TGPU_AGG_COUNT_ALL && a.input_nulls && a.input_nulls[r]) continue;
             cnt_base[plan.cnt_slot[k] * kBlock + threadIdx.x] += 1u;
             if (tg_is_minmax(a.function)) {   // (no lane-private slot: almost no row improves a group's extreme, see tg_minmax_update)
-                tg_minmax_update(&a.i128[(size_t)g * 2], tg_minmax_encode(a.function, ((const unsigned long long *)a.input)[r]));
+                tg_minmax_update(&a.i128[(size_t)g * 2], tg_minmax_encode(a.function, minmax_raw(a, r)));
                 continue;
             }
             const int w = plan.wide_slot[k];
@@ -661,6 +670,7 @@ __device__ double kulisch_round(const long long *limbs, unsigned int special)
 struct EvalView {
     int32_t function;
     int32_t partial;
+    int32_t narrow, pad;  // narrow: the final value is stored as int32 (INTEGER / DATE)
     const long long *counts;
     const long long *limbs;
     const unsigned int *special;
@@ -711,6 +721,8 @@ __global__ void __launch_bounds__(kBlock) agg_evaluate_kernel(EvalArgs args, int
         switch (a.function) {
         case TGPU_AGG_MIN_BIGINT:
         case TGPU_AGG_MAX_BIGINT:
+            if (a.narrow) { ((int *)a.out0)[g] = cnt ? (int)lsum : 0; break; }   // (the extreme of int32 values: the narrowing loses nothing)
+            [[fallthrough]];
         case TGPU_AGG_MIN_DOUBLE:
         case TGPU_AGG_MAX_DOUBLE:
         case TGPU_AGG_SUM_BIGINT: ((long long *)a.out0)[g] = cnt ? lsum : 0; break;
@@ -722,10 +734,11 @@ __global__ void __launch_bounds__(kBlock) agg_evaluate_kernel(EvalArgs args, int
 
 bool is_double_state(int32_t f) { return f == TGPU_AGG_SUM_DOUBLE || f == TGPU_AGG_AVG_DOUBLE || f == TGPU_AGG_AVG_BIGINT; }
 bool is_count(int32_t f) { return f == TGPU_AGG_COUNT_ALL || f == TGPU_AGG_COUNT_COLUMN; }
-bool is_minmax(int32_t f) { return f >= TGPU_AGG_MIN_BIGINT && f <= TGPU_AGG_MAX_DOUBLE; }
+// (these take a tgpu_agg_function as the caller gave it: INTEGER / DATE extremes answer as the BIGINT function they run as)
+bool is_minmax(int32_t f) { return f >= TGPU_AGG_MIN_BIGINT && f <= TGPU_AGG_MAX_DATE; }
 bool is_bigint_state(int32_t f) { return f == TGPU_AGG_SUM_BIGINT || is_minmax(f); }   // two 64-bit words per group (128-bit sum / extreme code)
-// the type of the aggregate's value channel (input, PARTIAL's second channel, output)
-bool bigint_valued(int32_t f) { return f == TGPU_AGG_SUM_BIGINT || f == TGPU_AGG_MIN_BIGINT || f == TGPU_AGG_MAX_BIGINT; }
+// the type of the aggregate's value channel (PARTIAL's second channel; input and output unless agg_narrow_type names an int32 type)
+bool bigint_valued(int32_t f) { f = agg_kernel_function(f); return f == TGPU_AGG_SUM_BIGINT || f == TGPU_AGG_MIN_BIGINT || f == TGPU_AGG_MAX_BIGINT; }
 
 // the regions a round of state growth has to clear, zeroed by ONE launch (an operator with 8 aggregates grows ~24 arrays: one
 // memset each would cost more in launch gaps than the clearing itself)
@@ -765,7 +778,13 @@ GroupedAccumulators::GroupedAccumulators(Context *ctx, std::vector<tgpu_agg_spec
     }
     TG_CHECK_ARG((int)specs.size() <= kMaxAggs, "at most 16 aggregates per operator");
     for (auto &s : specs) {
-        TG_CHECK_ARG(s.function >= TGPU_AGG_COUNT_ALL && s.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
+        TG_CHECK_ARG(agg_function_known(s.function), "unknown aggregate function");
+        if (agg_is_varchar_extreme(s.function)) {
+            order_.push_back(Slot{true, (int)vstates_.size()});
+            vstates_.push_back(VarcharState{s, std::make_unique<VarcharExtremes>(ctx, s.function == TGPU_AGG_MIN_VARCHAR)});
+            continue;
+        }
+        order_.push_back(Slot{false, (int)states_.size()});
         State st;
         st.spec = s;
         states_.push_back(st);
@@ -843,6 +862,7 @@ int64_t GroupedAccumulators::HostStates::bytes() const
 
 GroupedAccumulators::HostStates GroupedAccumulators::dump(int64_t groups)
 {
+    if (!vstates_.empty()) fail(TGPU_ERR_NOT_SUPPORTED, "min / max over VARCHAR cannot spill");
     HostStates h;
     h.groups = groups;
     if (groups <= 0) return h;
@@ -950,7 +970,7 @@ void GroupedAccumulators::merge(const int32_t *gids, const HostStates &run, int6
         State &st = states_[k];
         const HostStates::Agg &r = run.aggs[k];
         MergeArgs::A &a = args.a[k];
-        a.function = st.spec.function;
+        a.function = agg_kernel_function(st.spec.function);
         a.counts = st.counts->as<long long>();
         a.limbs = st.limbs ? st.limbs->as<long long>() : nullptr;
         a.special = st.special ? st.special->as<unsigned int>() : nullptr;
@@ -1006,6 +1026,7 @@ __global__ void __launch_bounds__(kBlock) agg_carry_kernel(CarryArgs args, int64
 
 void GroupedAccumulators::carry_last_group(int64_t groups)
 {
+    TG_CHECK_STATE(vstates_.empty(), "min / max over VARCHAR cannot carry a group");
     if (states_.empty() || groups <= 1) return;   // (one group: it is group 0 already)
     TG_CHECK_STATE(mode_ == Mode::ORDERED, "carrying a group needs row-order states");
     ensure(groups);
@@ -1025,7 +1046,7 @@ GroupedAccumulators::DeviceState GroupedAccumulators::device_state(int k) const
 {
     const State &st = states_[(size_t)k];
     DeviceState d;
-    d.function = st.spec.function;
+    d.function = agg_kernel_function(st.spec.function);
     d.counts = st.counts ? st.counts->as<long long>() : nullptr;
     d.limbs = st.limbs ? st.limbs->as<long long>() : nullptr;
     d.special = st.special ? st.special->as<unsigned int>() : nullptr;
@@ -1037,18 +1058,25 @@ GroupedAccumulators::DeviceState GroupedAccumulators::device_state(int k) const
 const std::vector<tgpu_agg_spec> GroupedAccumulators::specs() const
 {
     std::vector<tgpu_agg_spec> v;
+    for (const Slot &s : order_) v.push_back(s.varchar ? vstates_[(size_t)s.index].spec : states_[(size_t)s.index].spec);
+    return v;
+}
+
+std::vector<tgpu_agg_spec> GroupedAccumulators::state_specs() const
+{
+    std::vector<tgpu_agg_spec> v;
     for (auto &s : states_) v.push_back(s.spec);
     return v;
 }
 
 int GroupedAccumulators::output_channel_count() const
 {
-    return step_ == TGPU_STEP_PARTIAL ? intermediate_channel_count() : (int)states_.size();
+    return step_ == TGPU_STEP_PARTIAL ? intermediate_channel_count() : (int)order_.size();
 }
 
 int GroupedAccumulators::intermediate_channel_count() const
 {
-    int n = 0;
+    int n = 2 * (int)vstates_.size();
     for (auto &s : states_) n += is_count(s.spec.function) ? 1 : 2;
     return n;
 }
@@ -1056,6 +1084,7 @@ int GroupedAccumulators::intermediate_channel_count() const
 int64_t GroupedAccumulators::estimated_size() const
 {
     int64_t s = 0;
+    for (auto &v : vstates_) s += v.acc->estimated_size();
     for (auto &st : states_) {
         s += st.cap * 8;
         if (st.limbs) s += st.cap * (kLimbs * 8 + 4);
@@ -1116,7 +1145,7 @@ void GroupedAccumulators::decide_mode(int64_t groups, int64_t lowcard_max_groups
 
 void GroupedAccumulators::decide(int64_t groups_in_prefix, int64_t lowcard_max_groups)
 {
-    if (lowcard_max_groups <= 0) lowcard_max_groups = (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(specs()), 1);
+    if (lowcard_max_groups <= 0) lowcard_max_groups = (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(state_specs()), 1);
     decide_mode(groups_in_prefix > 0 ? groups_in_prefix : 1, lowcard_max_groups);
 }
 
@@ -1193,18 +1222,54 @@ void GroupedAccumulators::sort_rows_by_group(const int32_t *gids, int64_t n, int
 
 void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
 {
+    add_input_states(gids, n, page, group_count, gids_ascending);
+    add_varchar(gids, n, page, group_count, false);
+}
+
+void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
+{
+    add_intermediate_states(gids, n, page, group_count, gids_ascending);
+    add_varchar(gids, n, page, group_count, true);
+}
+
+// min / max over VARCHAR, each as launches of its own (minmax_varchar.h); FINAL reads the count channel and, for the rows whose count is
+// not 0, the value channel behind it exactly as raw input is read
+void GroupedAccumulators::add_varchar(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool intermediate)
+{
+    if (n <= 0) return;
+    for (VarcharState &v : vstates_) {
+        const int ch = v.spec.input_channel;
+        if (intermediate) {
+            check_channel(page, ch, TGPU_BIGINT, "intermediate count");
+            check_channel(page, ch + 1, TGPU_VARCHAR, "intermediate value");
+            v.acc->add(gids, n, page.cols[(size_t)ch + 1], nullptr, nullptr, (const long long *)page.cols[(size_t)ch].values, group_count);
+            continue;
+        }
+        check_channel(page, ch, TGPU_VARCHAR, "aggregate input");
+        const uint8_t *mask = nullptr, *mask_nulls = nullptr;
+        if (v.spec.mask_channel >= 0) {
+            check_channel(page, v.spec.mask_channel, TGPU_BOOLEAN, "aggregate mask");
+            mask = (const uint8_t *)page.cols[(size_t)v.spec.mask_channel].values;
+            mask_nulls = page.cols[(size_t)v.spec.mask_channel].nulls;
+        }
+        v.acc->add(gids, n, page.cols[(size_t)ch], mask, mask_nulls, nullptr, group_count);
+    }
+}
+
+void GroupedAccumulators::add_input_states(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
+{
     if (states_.empty() || n <= 0) return;
     BufferPtr zero_gids;
     if (!gids && force_ordered()) {   // a global aggregation in Java order: one group, id 0 for every row
         zero_gids = ctx_->alloc_zero((size_t)n * 4);
         gids = zero_gids->as<int32_t>();
     }
-    if (gids) decide_mode(group_count > 0 ? group_count : 1, (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(specs()), 1));
+    if (gids) decide_mode(group_count > 0 ? group_count : 1, (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(state_specs()), 1));
     else if (mode_ == Mode::UNDECIDED) mode_ = Mode::EXACT;
     {
         // a low-cardinality launch leaves folded partials for every group its LDS has room for (fold_scratch): reserve those states
         // now, before the argument block below takes their addresses
-        const int64_t lowcard_capacity = (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(specs()), 1);
+        const int64_t lowcard_capacity = (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(state_specs()), 1);
         const int64_t g = group_count > 0 ? group_count : 1;
         ensure(mode_ == Mode::EXACT && g <= lowcard_capacity ? lowcard_capacity : g);
     }
@@ -1213,12 +1278,14 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
     for (size_t k = 0; k < states_.size(); k++) {
         State &st = states_[k];
         AggView &a = args.a[k];
-        a.function = st.spec.function;
+        a.function = agg_kernel_function(st.spec.function);
+        a.narrow = agg_narrow_type(st.spec.function) ? 1 : 0;
         if (st.spec.function != TGPU_AGG_COUNT_ALL) {
             int32_t want = 0;
             if (bigint_valued(st.spec.function) || st.spec.function == TGPU_AGG_AVG_BIGINT) want = TGPU_BIGINT;
             if (st.spec.function == TGPU_AGG_MIN_DOUBLE || st.spec.function == TGPU_AGG_MAX_DOUBLE) want = TGPU_DOUBLE;
             if (st.spec.function == TGPU_AGG_SUM_DOUBLE || st.spec.function == TGPU_AGG_AVG_DOUBLE) want = TGPU_DOUBLE;
+            if (agg_narrow_type(st.spec.function)) want = agg_narrow_type(st.spec.function);
             check_channel(page, st.spec.input_channel, want, "aggregate input");
             a.input = page.cols[st.spec.input_channel].values;
             a.input_nulls = page.cols[st.spec.input_channel].nulls;
@@ -1344,7 +1411,7 @@ void GroupedAccumulators::add_input(const int32_t *gids, int64_t n, const Device
     check_launch("agg_accumulate");
 }
 
-void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
+void GroupedAccumulators::add_intermediate_states(const int32_t *gids, int64_t n, const DevicePage &page, int64_t group_count, bool gids_ascending)
 {
     if (states_.empty() || n <= 0) return;
     BufferPtr zero_gids;
@@ -1352,7 +1419,7 @@ void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const
         zero_gids = ctx_->alloc_zero((size_t)n * 4);
         gids = zero_gids->as<int32_t>();
     }
-    if (gids) decide_mode(group_count > 0 ? group_count : 1, (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(specs()), 1));
+    if (gids) decide_mode(group_count > 0 ? group_count : 1, (160 * 1024) / std::max<int64_t>(lowcard_bytes_per_group(state_specs()), 1));
     else if (mode_ == Mode::UNDECIDED) mode_ = Mode::EXACT;
     ensure(group_count > 0 ? group_count : 1);
     AggArgs args{};
@@ -1360,7 +1427,7 @@ void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const
     for (size_t k = 0; k < states_.size(); k++) {
         State &st = states_[k];
         AggView &a = args.a[k];
-        a.function = st.spec.function;
+        a.function = agg_kernel_function(st.spec.function);   // (the intermediate value is BIGINT: nothing narrow here)
         int ch = st.spec.input_channel;
         check_channel(page, ch, TGPU_BIGINT, "intermediate count");
         a.input = page.cols[ch].values;
@@ -1393,6 +1460,26 @@ void GroupedAccumulators::add_intermediate(const int32_t *gids, int64_t n, const
 
 void GroupedAccumulators::evaluate(int64_t groups, std::vector<DeviceColumn> &out)
 {
+    if (vstates_.empty()) {
+        evaluate_states(groups, out);
+        return;
+    }
+    std::vector<DeviceColumn> fixed;
+    evaluate_states(groups, fixed);
+    const bool partial = step_ == TGPU_STEP_PARTIAL;
+    size_t at = 0;
+    for (const Slot &s : order_) {   // the channels in the order of the caller's aggregate list
+        if (s.varchar) {
+            vstates_[(size_t)s.index].acc->evaluate(groups, partial, out);
+            continue;
+        }
+        const size_t take = (partial && !is_count(states_[(size_t)s.index].spec.function)) ? 2 : 1;
+        for (size_t i = 0; i < take; i++) out.push_back(fixed[at++]);
+    }
+}
+
+void GroupedAccumulators::evaluate_states(int64_t groups, std::vector<DeviceColumn> &out)
+{
     if (states_.empty()) return;
     ensure(groups > 0 ? groups : 1);
     flush_fold();
@@ -1403,8 +1490,9 @@ void GroupedAccumulators::evaluate(int64_t groups, std::vector<DeviceColumn> &ou
     for (size_t k = 0; k < states_.size(); k++) {
         State &st = states_[k];
         EvalView &a = args.a[k];
-        a.function = st.spec.function;
+        a.function = agg_kernel_function(st.spec.function);
         a.partial = partial ? 1 : 0;
+        a.narrow = (!partial && agg_narrow_type(st.spec.function)) ? 1 : 0;
         a.counts = st.counts->as<long long>();
         a.limbs = st.limbs ? st.limbs->as<long long>() : nullptr;
         a.special = st.special ? st.special->as<unsigned int>() : nullptr;
@@ -1429,7 +1517,7 @@ void GroupedAccumulators::evaluate(int64_t groups, std::vector<DeviceColumn> &ou
             }
         }
         else {
-            c0.type = bigint_valued(st.spec.function) ? TGPU_BIGINT : TGPU_DOUBLE;
+            c0.type = agg_narrow_type(st.spec.function) ? agg_narrow_type(st.spec.function) : (bigint_valued(st.spec.function) ? TGPU_BIGINT : TGPU_DOUBLE);
             c0.nulls_buf = ctx_->alloc((size_t)alloc_n);
             c0.nulls = c0.nulls_buf->as<uint8_t>();
             a.out0_nulls = c0.nulls_buf->as<uint8_t>();

@@ -872,7 +872,12 @@ int32_t tgpu_hash_aggregation_factory_set_spill_enabled(tgpu_operator_factory *f
 {
     return guard_on(ctx_of(factory), [&] {
         TG_CHECK_ARG(factory != nullptr && factory->f, "factory is null");
-        if (auto *f = dynamic_cast<HashAggregationOperatorFactory *>(factory->f.get())) f->config().spill_enabled = enabled != 0;
+        if (auto *f = dynamic_cast<HashAggregationOperatorFactory *>(factory->f.get())) {
+            // (the value store of a VARCHAR extreme has no spilled form: the factory stays as it was, usable unspilled)
+            for (const tgpu_agg_spec &a : f->config().aggs)
+                if (enabled != 0 && (a.function == TGPU_AGG_MIN_VARCHAR || a.function == TGPU_AGG_MAX_VARCHAR)) fail(TGPU_ERR_NOT_SUPPORTED, "min / max over VARCHAR cannot spill");
+            f->config().spill_enabled = enabled != 0;
+        }
         else if (auto *g = dynamic_cast<FusedFilterProjectAggregationOperatorFactory *>(factory->f.get())) g->config().spill_enabled = enabled != 0;
         else fail(TGPU_ERR_NOT_SUPPORTED, "only hash aggregation factories can spill");
     });

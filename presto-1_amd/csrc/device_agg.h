@@ -17,6 +17,15 @@
 #define TG_AGG_MAX_BIGINT 8
 #define TG_AGG_MIN_DOUBLE 9
 #define TG_AGG_MAX_DOUBLE 10
+// min / max over INTEGER and DATE never reach a kernel under their own codes: the host runs them as TG_AGG_MIN_BIGINT / TG_AGG_MAX_BIGINT
+// over the sign-extended value (agg.h agg_kernel_function), so the kernels below know a load width, not a function more
+#define TG_AGG_MIN_INTEGER 11
+#define TG_AGG_MAX_INTEGER 12
+#define TG_AGG_MIN_DATE 13
+#define TG_AGG_MAX_DATE 14
+// min / max over VARCHAR have kernels of their own (minmax_varchar.hip) and are in none of the switches below
+#define TG_AGG_MIN_VARCHAR 15
+#define TG_AGG_MAX_VARCHAR 16
 
 // per-aggregate state arrays in HBM, indexed by group id
 struct TgAggState {

@@ -3719,11 +3719,17 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
     supported_ = true;
     const int np = (int)prog_.proj_roots.size();
     for (auto &a : aggs_) {
-        TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
+        TG_CHECK_ARG(agg_function_known(a.function), "unknown aggregate function");
+        if (agg_is_varchar_extreme(a.function)) fail(TGPU_ERR_NOT_SUPPORTED, "min / max over VARCHAR is not supported by the fused filter / project aggregation");
         if (a.function != TGPU_AGG_COUNT_ALL) {
             TG_CHECK_ARG(a.input_channel >= 0 && a.input_channel < np, "aggregate input channel out of range");
             const int32_t t = prog_.proj_types[(size_t)a.input_channel];
-            const bool want_bigint = a.function == TGPU_AGG_SUM_BIGINT || a.function == TGPU_AGG_AVG_BIGINT || a.function == TGPU_AGG_MIN_BIGINT || a.function == TGPU_AGG_MAX_BIGINT;
+            // min / max over INTEGER / DATE: the projection's value is an int expression, `y = value` below widens it, and from here on the
+            // aggregate is the BIGINT function (the output's type is the accumulators' business: they keep the caller's code)
+            const int32_t narrow = agg_narrow_type(a.function);
+            TG_CHECK_ARG(!narrow || t == narrow, "aggregate input type mismatch");
+            a.function = agg_kernel_function(a.function);
+            const bool want_bigint = !narrow && (a.function == TGPU_AGG_SUM_BIGINT || a.function == TGPU_AGG_AVG_BIGINT || a.function == TGPU_AGG_MIN_BIGINT || a.function == TGPU_AGG_MAX_BIGINT);
             const bool want_double = a.function == TGPU_AGG_SUM_DOUBLE || a.function == TGPU_AGG_AVG_DOUBLE || a.function == TGPU_AGG_MIN_DOUBLE || a.function == TGPU_AGG_MAX_DOUBLE;
             TG_CHECK_ARG(!(want_bigint && t != TGPU_BIGINT) && !(want_double && t != TGPU_DOUBLE), "aggregate input type mismatch");
             if (a.function == TGPU_AGG_COUNT_COLUMN && t == TGPU_VARCHAR) supported_ = supported_ && prog_.nodes[(size_t)prog_.proj_roots[(size_t)a.input_channel]].kind == TGPU_EX_INPUT;

@@ -780,7 +780,7 @@ static void validate(Context *, const HashAggregationConfig &cfg)
     TG_CHECK_ARG((int)cfg.group_by_types.size() <= kMaxKeyChannels, "at most 8 group-by channels");
     TG_CHECK_ARG((int)cfg.aggs.size() <= kMaxAggs, "at most 16 aggregates");
     TG_CHECK_ARG(cfg.expected_groups > 0, "expectedGroups must be positive");
-    for (auto &a : cfg.aggs) TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
+    for (auto &a : cfg.aggs) TG_CHECK_ARG(agg_function_known(a.function), "unknown aggregate function");
 }
 
 // =====================================================================================================================
@@ -920,8 +920,12 @@ static void validate(Context *, const StreamingAggregationConfig &cfg)
     for (int32_t t : cfg.types) TG_CHECK_ARG(valid_type(t), "unknown channel type");
     for (int32_t ch : cfg.group_by_channels) TG_CHECK_ARG(ch >= 0 && ch < (int)cfg.types.size(), "group-by channel out of range");
     for (auto &a : cfg.aggs) {
-        TG_CHECK_ARG(a.function >= TGPU_AGG_COUNT_ALL && a.function <= TGPU_AGG_MAX_DOUBLE, "unknown aggregate function");
+        TG_CHECK_ARG(agg_function_known(a.function), "unknown aggregate function");
+        if (agg_is_varchar_extreme(a.function)) fail(TGPU_ERR_NOT_SUPPORTED, "min / max over VARCHAR is not supported by the streaming aggregation");
         TG_CHECK_ARG(a.function == TGPU_AGG_COUNT_ALL || (a.input_channel >= 0 && a.input_channel < (int)cfg.types.size()), "aggregate input channel out of range");
+        // (the source types are known here: min / max over INTEGER / DATE read a channel of that type -- FINAL reads the BIGINT count channel)
+        if (agg_narrow_type(a.function))
+            TG_CHECK_ARG(cfg.types[(size_t)a.input_channel] == (cfg.step == TGPU_STEP_FINAL ? TGPU_BIGINT : agg_narrow_type(a.function)), "aggregate input type mismatch");
         TG_CHECK_ARG(a.mask_channel < (int)cfg.types.size(), "aggregate mask channel out of range");
         if (a.mask_channel >= 0) TG_CHECK_ARG(cfg.types[(size_t)a.mask_channel] == TGPU_BOOLEAN, "aggregate mask channel is not BOOLEAN");
     }
@@ -1891,6 +1895,8 @@ FusedFilterProjectAggregationOperatorFactory::FusedFilterProjectAggregationOpera
     }
     TG_CHECK_ARG(cfg_.hash_channel < (int)pt.size(), "hash channel out of range");
     TG_CHECK_ARG(cfg_.expected_groups > 0, "expectedGroups must be positive");
+    for (const tgpu_agg_spec &a : cfg_.aggs)
+        if (agg_is_varchar_extreme(a.function)) fail(TGPU_ERR_NOT_SUPPORTED, "min / max over VARCHAR is not supported by the fused filter / project aggregation");
     fused_ = FusedAggGpu::shared(input_types, spec, cfg_.aggs, cfg_.group_by_channels);
 }
 
