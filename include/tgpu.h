@@ -284,7 +284,79 @@ typedef enum tgpu_expr_op {
     TGPU_OP_LAST_DAY_OF_MONTH = 29,
     TGPU_OP_DATE_TRUNC = 30,
     TGPU_OP_DATE_ADD = 31,
-    TGPU_OP_DATE_DIFF = 32
+    TGPU_OP_DATE_DIFF = 32,
+    /* Math functions (M/operator/scalar/MathFunctions.java) over BIGINT, INTEGER and DOUBLE.  The usual call convention: arguments left to
+     * right, the first NULL argument gives NULL and the arguments after it are not evaluated.  A wrong argument count, argument type or
+     * result type: TGPU_ERR_COMPILER when the factory is created.
+     *
+     * Exact group: the result is pinned bit for bit, except that a NaN result may be any NaN (JDK versions differ on the sign and payload
+     * Math.abs leaves).
+     *
+     *   TGPU_OP_ABS       (BIGINT) -> BIGINT, (INTEGER) -> INTEGER, (DOUBLE) -> DOUBLE   :127-148.  The integer minimum fails with
+     *                     TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE and the reference's message, "Value -9223372036854775808 is out of range for
+     *                     abs(bigint)" / "Value -2147483648 is out of range for abs(integer)".  DOUBLE: the sign bit cleared.
+     *   TGPU_OP_SIGN      (BIGINT) -> BIGINT, (INTEGER) -> INTEGER, (DOUBLE) -> DOUBLE   :1085-1125.  -1, 0 or 1; DOUBLE is Math.signum: NaN
+     *                     gives NaN, a zero keeps its sign.
+     *   TGPU_OP_FLOOR     BIGINT / INTEGER: the identity; (DOUBLE) -> DOUBLE             :390-409, Math.floor
+     *   TGPU_OP_CEILING   BIGINT / INTEGER: the identity; (DOUBLE) -> DOUBLE             :245-264, Math.ceil: ceiling(-0.5) is -0.0
+     *   TGPU_OP_TRUNCATE  (DOUBLE) -> DOUBLE   :315-320: signum(x) * floor(abs(x)).  -0.5 gives -0.0; NaN and the infinities pass through.
+     *   TGPU_OP_ROUND     one argument: BIGINT / INTEGER the identity (:724-735), (DOUBLE) -> DOUBLE = round(x, 0) (:805-808).
+     *                     Two arguments: (BIGINT | INTEGER | DOUBLE, INTEGER decimals) -> the first argument's type.  decimals must be a
+     *                     TGPU_EX_CONST INTEGER node: TGPU_ERR_NOT_SUPPORTED otherwise, "the number of decimals must be an INTEGER constant".
+     *                     A null constant gives NULL for every row and evaluates nothing.
+     *                     Integers (roundLong :787-800): d >= 0 is the identity.  -18 <= d < 0: q = num / 10^-d rounded half away from zero
+     *                     (RoundingMode.HALF_UP), then q * 10^-d with the overflow checked.  d <= -19 fails for every non-null row:
+     *                     checkedPow overflows before num is looked at.  Every failure is TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE,
+     *                     "numerical overflow: " + num.  Deviation: INTEGER fails in the same way when the rounded value leaves int32; the
+     *                     reference's toIntExact there throws an ArithmeticException that escapes its own catch (:770-776).
+     *                     DOUBLE (:821-833): NaN and the infinities as they are.  Otherwise, with factor = 10^d, jround(x * factor) / factor
+     *                     for x >= 0 and -(jround(-x * factor) / factor) for x < 0, where jround is Math.round: the exact floor(x + 1/2) as a
+     *                     long, saturated at the int64 ends, 0 for NaN, converted back to double before the division.  factor is the
+     *                     correctly rounded decimal 1e<d>: equal to Math.pow(10, d) for 0 <= d <= 22, where the power is exact; outside of
+     *                     that the correctly rounded power, JVM parity unpinned.  d > 308 (factor +inf) gives +-0.0 and d < -323 (factor 0)
+     *                     gives NaN for every finite x: what the formula gives.
+     *   TGPU_OP_SQRT      (DOUBLE) -> DOUBLE   :1141: the correctly rounded IEEE square root.  Negative gives NaN, -0.0 gives -0.0.
+     *   TGPU_OP_IS_NAN, TGPU_OP_IS_FINITE, TGPU_OP_IS_INFINITE   (DOUBLE) -> BOOLEAN   :1165-1184
+     *   TGPU_OP_DEGREES, TGPU_OP_RADIANS   (DOUBLE) -> DOUBLE   :350, :569: one multiplication by 57.29577951308232, resp.
+     *                     0.017453292519943295.  That is Math.toDegrees / toRadians since JDK 9 (JDK 8 multiplied by 180 and divided by pi);
+     *                     the reference needs Java 11.
+     *
+     * Bounded group: (DOUBLE) -> DOUBLE, never fails.  The JVM promises "within 1 ulp of the exact result" for these, so there is no bit
+     * parity to keep: a finite result lies within 1 ulp of the correctly rounded one for CBRT, EXP, LN, LOG10 and POWER, and within the
+     * interval bound of the quotient (tests/golden/math_function_ulp_corpus.json "bounds") for LOG2 and LOG.
+     *
+     *   TGPU_OP_CBRT :221, TGPU_OP_EXP :366, TGPU_OP_LN :465, TGPU_OP_LOG10 :489   Math.cbrt / exp / log / log10
+     *   TGPU_OP_LOG2      :481: ln(x) / ln(2)
+     *   TGPU_OP_LOG       (DOUBLE base, DOUBLE x) -> DOUBLE   :473: ln(x) / ln(base), the base first
+     *   TGPU_OP_POWER     (DOUBLE x, DOUBLE y) -> DOUBLE      :561, Math.pow
+     *
+     * Special cases are Java's: a negative argument of a logarithm gives NaN, ln(+-0) is -inf, exp overflows to +inf.  POWER follows
+     * Math.pow's list, which differs from C's pow twice: pow(1, NaN) is NaN and pow(+-1, +-inf) is NaN; pow(x, +-0) is 1 even for a NaN x.
+     * Where the mathematical value of x ^ y for an integral y with |y| <= 1024 is a double (power(2, 10), power(10, 22), power(-3, 3)), the
+     * result is that value.
+     *
+     * Out of the IR: the trigonometric and hyperbolic functions, width_bucket, random, to_base / from_base, the CDF functions,
+     * cosine_similarity, greatest / least, the bitwise functions, the TINYINT / SMALLINT / REAL / DECIMAL flavours and a decimals argument
+     * that is no constant.  mod(a, b) is TGPU_OP_MODULUS. */
+    TGPU_OP_ABS = 33,
+    TGPU_OP_SIGN = 34,
+    TGPU_OP_FLOOR = 35,
+    TGPU_OP_CEILING = 36,
+    TGPU_OP_TRUNCATE = 37,
+    TGPU_OP_ROUND = 38,
+    TGPU_OP_SQRT = 39,
+    TGPU_OP_CBRT = 40,
+    TGPU_OP_EXP = 41,
+    TGPU_OP_LN = 42,
+    TGPU_OP_LOG2 = 43,
+    TGPU_OP_LOG10 = 44,
+    TGPU_OP_LOG = 45,
+    TGPU_OP_POWER = 46,
+    TGPU_OP_IS_NAN = 47,
+    TGPU_OP_IS_FINITE = 48,
+    TGPU_OP_IS_INFINITE = 49,
+    TGPU_OP_DEGREES = 50,
+    TGPU_OP_RADIANS = 51
 } tgpu_expr_op;
 typedef enum tgpu_special_form { /* M/sql/relational/SpecialForm.java:137-152 */
     TGPU_SF_AND = 1, TGPU_SF_OR, TGPU_SF_IF, TGPU_SF_IS_NULL, TGPU_SF_COALESCE, TGPU_SF_BETWEEN,

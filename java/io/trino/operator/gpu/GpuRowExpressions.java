@@ -1,7 +1,10 @@
 package io.trino.operator.gpu;
 
 import io.airlift.slice.Slice;
+import io.trino.spi.type.BigintType;
 import io.trino.spi.type.DateType;
+import io.trino.spi.type.DoubleType;
+import io.trino.spi.type.IntegerType;
 import io.trino.spi.type.Type;
 import io.trino.spi.type.VarcharType;
 import io.trino.sql.relational.CallExpression;
@@ -39,6 +42,10 @@ public final class GpuRowExpressions
     // dayOfWeekFromDate :436 ... yearFromDate :517)
     private static final int OP_YEAR = 21, OP_QUARTER = 22, OP_MONTH = 23, OP_WEEK = 24, OP_DAY = 25, OP_DAY_OF_WEEK = 26, OP_DAY_OF_YEAR = 27, OP_YEAR_OF_WEEK = 28;
     private static final int OP_LAST_DAY_OF_MONTH = 29, OP_DATE_TRUNC = 30, OP_DATE_ADD = 31, OP_DATE_DIFF = 32;
+    // TGPU_OP_ABS .. TGPU_OP_RADIANS: operator/scalar/MathFunctions.java over BIGINT, INTEGER and DOUBLE (abs :127-148, ceiling :245-264, truncate :317,
+    // floor :390-409, log :473, power :561, round :724-833, sign :1085-1125)
+    private static final int OP_MODULUS = 5, OP_ABS = 33, OP_SIGN = 34, OP_FLOOR = 35, OP_CEILING = 36, OP_TRUNCATE = 37, OP_ROUND = 38, OP_SQRT = 39, OP_CBRT = 40, OP_EXP = 41;
+    private static final int OP_LN = 42, OP_LOG2 = 43, OP_LOG10 = 44, OP_LOG = 45, OP_POWER = 46, OP_IS_NAN = 47, OP_IS_FINITE = 48, OP_IS_INFINITE = 49, OP_DEGREES = 50, OP_RADIANS = 51;
 
     public static final class Program
     {
@@ -130,6 +137,17 @@ public final class GpuRowExpressions
             if (dateOp != 0 && overDates(dateOp, call.getArguments())) {
                 int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
                 return emit(p, CALL, type, dateOp, args, false, 0, 0, 0);
+            }
+            if (call.getArguments().isEmpty() && call.getType() instanceof DoubleType) {
+                Double constant = mathConstant(name);
+                if (constant != null) {
+                    return emit(p, CONST, type, 0, new int[0], false, 0, constant, 0);
+                }
+            }
+            int mathOp = mathFunction(name, call.getArguments().size());
+            if (mathOp != 0 && overNumbers(mathOp, call.getType(), call.getArguments())) {
+                int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
+                return emit(p, CALL, type, mathOp, args, false, 0, 0, 0);
             }
             for (int op = 1; op < OPERATORS.length; op++) {
                 if (OPERATORS[op].equalsIgnoreCase(name)) {
@@ -223,6 +241,75 @@ public final class GpuRowExpressions
         }
         boolean dates = arguments.get(arguments.size() - 1).getType() instanceof DateType;
         return op == OP_DATE_DIFF ? dates && arguments.get(1).getType() instanceof DateType : dates;
+    }
+
+    /**
+     * The names and aliases of MathFunctions.java -> TGPU_OP_ABS .. TGPU_OP_RADIANS.  mod(a, b) is the IR's MODULUS, with one difference: a zero
+     * integer divisor is DIVISION_BY_ZERO here, where the reference's function lets the raw ArithmeticException through (mod :513-524 has
+     * no check; the % operator's has).  The trigonometric and hyperbolic functions, width_bucket, random, the bases, the CDFs and the
+     * bitwise functions are outside the IR.
+     */
+    private static int mathFunction(String name, int arguments)
+    {
+        switch (name.toLowerCase(java.util.Locale.ENGLISH)) {
+            case "abs": return arguments == 1 ? OP_ABS : 0;
+            case "sign": return arguments == 1 ? OP_SIGN : 0;
+            case "floor": return arguments == 1 ? OP_FLOOR : 0;
+            case "ceil":
+            case "ceiling": return arguments == 1 ? OP_CEILING : 0;
+            case "truncate": return arguments == 1 ? OP_TRUNCATE : 0;   // truncate(x, n) exists over decimals only
+            case "round": return arguments == 1 || arguments == 2 ? OP_ROUND : 0;
+            case "sqrt": return arguments == 1 ? OP_SQRT : 0;
+            case "cbrt": return arguments == 1 ? OP_CBRT : 0;
+            case "exp": return arguments == 1 ? OP_EXP : 0;
+            case "ln": return arguments == 1 ? OP_LN : 0;
+            case "log2": return arguments == 1 ? OP_LOG2 : 0;
+            case "log10": return arguments == 1 ? OP_LOG10 : 0;
+            case "log": return arguments == 2 ? OP_LOG : 0;
+            case "pow":
+            case "power": return arguments == 2 ? OP_POWER : 0;
+            case "is_nan": return arguments == 1 ? OP_IS_NAN : 0;
+            case "is_finite": return arguments == 1 ? OP_IS_FINITE : 0;
+            case "is_infinite": return arguments == 1 ? OP_IS_INFINITE : 0;
+            case "degrees": return arguments == 1 ? OP_DEGREES : 0;
+            case "radians": return arguments == 1 ? OP_RADIANS : 0;
+            case "mod": return arguments == 2 ? OP_MODULUS : 0;
+            default: return 0;
+        }
+    }
+
+    /**
+     * The same names exist over tinyint, smallint, real and decimal: only the BIGINT / INTEGER / DOUBLE flavours are in the IR, every other one
+     * falls through to "function not in the GPU IR".  abs, sign, floor, ceiling, round and mod keep their argument's type; everything else
+     * is over double.  The number of decimals of round is an integer, which the library wants constant.
+     */
+    private static boolean overNumbers(int op, Type result, List<RowExpression> arguments)
+    {
+        Type first = arguments.get(0).getType();
+        boolean integer = first instanceof BigintType || first instanceof IntegerType;
+        boolean typed = op == OP_ABS || op == OP_SIGN || op == OP_FLOOR || op == OP_CEILING || op == OP_ROUND || op == OP_MODULUS;
+        if (!(first instanceof DoubleType) && !(typed && integer)) {
+            return false;
+        }
+        if (op == OP_ROUND) {
+            return result.equals(first) && (arguments.size() == 1 || arguments.get(1).getType() instanceof IntegerType);
+        }
+        if (op == OP_IS_NAN || op == OP_IS_FINITE || op == OP_IS_INFINITE) {
+            return true;
+        }
+        return result.equals(first) && arguments.stream().allMatch(a -> a.getType().equals(first));
+    }
+
+    /** pi(), e(), nan() and infinity() fold to DOUBLE constants (MathFunctions.java :358, :553, :1189, :1197) */
+    private static Double mathConstant(String name)
+    {
+        switch (name.toLowerCase(java.util.Locale.ENGLISH)) {
+            case "pi": return Math.PI;
+            case "e": return Math.E;
+            case "nan": return Double.NaN;
+            case "infinity": return Double.POSITIVE_INFINITY;
+            default: return null;
+        }
     }
 
     /**

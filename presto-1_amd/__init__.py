@@ -6,7 +6,9 @@ needs libtgpu.so (built by __graft_entry__.build()) and a HIP device.
 from . import _lib, expressions, operators, spi
 from ._lib import SO_PATH, TgpuError, build
 from .expressions import (and_, between, call, cast, coalesce, concat, constant, field, if_, in_, is_null, length, like, not_, or_, starts_with, strpos, substr,
-                          date_add, date_diff, date_trunc, day, day_of_week, day_of_year, last_day_of_month, month, quarter, week, year, year_of_week)
+                          date_add, date_diff, date_trunc, day, day_of_week, day_of_year, last_day_of_month, month, quarter, week, year, year_of_week,
+                          abs_, sign, floor, ceiling, ceil, truncate, round_, sqrt, cbrt, exp, ln, log2, log10, log, power, pow_, is_nan, is_finite, is_infinite,
+                          degrees, radians)
 from .operators import (ASC_NULLS_FIRST, ASC_NULLS_LAST, DESC_NULLS_FIRST, DESC_NULLS_LAST, DynamicFilterSourceOperatorFactory, MergePagesOperatorFactory, OrderByOperatorFactory, PartitionedOutputOperator, PartitionedOutputOperatorFactory, TopNOperatorFactory, AVG_BIGINT, AVG_DOUBLE, MIN_BIGINT, MAX_BIGINT, MIN_DOUBLE, MAX_DOUBLE, SUM_ORDER_EXACT, SUM_ORDER_JAVA, COUNT_ALL, COUNT_COLUMN, FINAL, FULL_OUTER, INNER, LOOKUP_OUTER, PARTIAL, PROBE_OUTER, SINGLE, SUM_BIGINT, SUM_DOUBLE,
                         Context, FilterAndProjectOperatorFactory, ScanFilterAndProjectOperatorFactory, PageSource, RecordCursor, FilterProjectHashAggregationOperatorFactory, FilterProjectLookupJoinOperatorFactory, GroupByHash, HashAggregationOperatorFactory, HashBuilderOperatorFactory,
                         LookupJoinOperatorFactory, LookupOuterOperatorFactory, Operator, OperatorFactory, page_processor_source, fused_probe_launch_counts, fused_probe_depth_counts, precompile_fused_aggregation, precompile_fused_probe, precompile_page_processor, to_pages,

@@ -263,12 +263,17 @@ struct ProfileScope {
 };
 
 // an expression-error word written by a generated kernel: ~0 = none, else (rank << 40) | (row << 8) | code (7 = division by zero, 9 = invalid
-// cast argument, 10 = concatenated string too large, else overflow).  rank orders the roots as the reference evaluates them (0 the filter,
+// cast argument, 10 = concatenated string too large, 11 / 12 = abs of the BIGINT / INTEGER minimum, 13 = round over integers, else overflow).  rank orders the roots as the reference evaluates them (0 the filter,
 // 1 + i projection i: jit.cpp "which error a page raises"); the minimum over the page is the failure the reference throws first.
-inline void raise_expression_error(unsigned long long e)
+constexpr int kErrorRoundOverflow = 13;   // its message carries the operand, which the caller fetches (PageProcessorGpu::process)
+inline void raise_expression_error(unsigned long long e, long long operand = 0)
 {
     if (e == ~0ull) return;
     const long long row = (long long)((e >> 8) & 0xffffffffull);
+    // M/operator/scalar/MathFunctions.java:127-140 and :787-800
+    if ((int)(e & 0xff) == 11) fail(TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "Value -9223372036854775808 is out of range for abs(bigint) (position " + std::to_string(row) + ")");
+    if ((int)(e & 0xff) == 12) fail(TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "Value -2147483648 is out of range for abs(integer) (position " + std::to_string(row) + ")");
+    if ((int)(e & 0xff) == kErrorRoundOverflow) fail(TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "numerical overflow: " + std::to_string(operand) + " (position " + std::to_string(row) + ")");
     if ((int)(e & 0xff) == 7) fail(TGPU_ERR_DIVISION_BY_ZERO, "Division by zero (position " + std::to_string(row) + ")");
     if ((int)(e & 0xff) == 10) fail(TGPU_ERR_INVALID_ARGUMENT, "Concatenated string is too large (position " + std::to_string(row) + ")");
     if ((int)(e & 0xff) == 9) fail(TGPU_ERR_INVALID_CAST_ARGUMENT, "Cannot cast double to an integer type: NaN or out of range (position " + std::to_string(row) + ")");

@@ -564,6 +564,20 @@ struct Gen {
         return std::string("TG_RAISE(") + code + ");";
     }
 
+    // A failure whose message carries an operand (round over integers: "numerical overflow: " + num).  The error word has no room for it: the
+    // host launches the kernel that raised once more with FpArgs.operand_key = the winning word, and the one lane that posts exactly that
+    // word stores its operand (PageProcessorGpu::process).  In every other launch FpArgs.operand is null.
+    std::string raise_operand(const char *code, const std::string &value)
+    {
+        raise(code);
+        if (!operand_raises)
+            consts << "#ifndef TG_RAISE_OPERAND\n#define TG_RAISE_OPERAND(code, value) do { if (!ef_) { if (A.operand && ((((unsigned long long)(er_ + row)) << 8) | "
+                      "(unsigned long long)(code)) == A.operand_key) *A.operand = (long long)(value); TG_RAISE(code); } } while (0)\n#endif\n";
+        operand_raises = true;
+        return std::string("TG_RAISE_OPERAND(") + code + ", " + value + ");";
+    }
+    bool operand_raises = false;
+
     // gen() for the root of the filter (rank 0) or of projection i (rank 1 + i): declares the root's flag and key when it can raise
     Val gen_root(int idx, int d, int rank)
     {
@@ -641,6 +655,7 @@ struct Gen {
             if (nd.op == TGPU_OP_LIKE) return gen_like(nd, idx, d);
             if ((nd.op >= TGPU_OP_LENGTH && nd.op <= TGPU_OP_STARTS_WITH) || (nd.op == TGPU_OP_CAST && nd.type == TGPU_VARCHAR)) return gen_string(nd, idx, d);
             if (nd.op >= TGPU_OP_YEAR && nd.op <= TGPU_OP_DATE_DIFF) return gen_date(nd, d);
+            if (nd.op >= TGPU_OP_ABS && nd.op <= TGPU_OP_RADIANS) return gen_math(nd, d);
             return gen_call(nd, d);
         case TGPU_EX_SPECIAL: return nd.op == TGPU_SF_IN ? gen_in(nd, idx, d) : gen_special(nd, idx, d);
         default: bad("unknown node kind");
@@ -879,6 +894,117 @@ struct Gen {
         default: os << ind(dd) << r.v << " = tg_date_" << kFields[nd.op - TGPU_OP_YEAR] << "(" << a[0].v << ");\n";
         }
         for (int k = first; k < nd.n_args; k++) os << ind(--dd) << "}\n";
+        os << ind(d) << "}\n";
+        return r;
+    }
+
+    // ---- math functions (M/operator/scalar/MathFunctions.java); what is more than one expression is csrc/device_math.h -------------------
+    bool math_helpers = false;
+
+    void need_math_helpers()
+    {
+        if (!math_helpers) consts << device_header("device_math.h");   // (guarded by its own #ifndef: several generators feed one module)
+        math_helpers = true;
+    }
+
+    // a finite double as a hex-float literal (exact), e.g. 100 = 0x1.9p+6
+    static std::string hex_float(double x)
+    {
+        char buf[64];
+        snprintf(buf, sizeof buf, "%a", x);
+        return buf;
+    }
+
+    Val gen_math(const tgpu_expr_node &nd, int d)
+    {
+        static const char *kNames[] = {"ABS", "SIGN", "FLOOR", "CEILING", "TRUNCATE", "ROUND", "SQRT", "CBRT", "EXP", "LN", "LOG2", "LOG10", "LOG", "POWER",
+                                       "IS_NAN", "IS_FINITE", "IS_INFINITE", "DEGREES", "RADIANS"};
+        const int op = nd.op;
+        const std::string name = kNames[op - TGPU_OP_ABS];
+        const bool two = op == TGPU_OP_LOG || op == TGPU_OP_POWER;
+        const bool decimals = op == TGPU_OP_ROUND && nd.n_args == 2;
+        if (!decimals && nd.n_args != (two ? 2 : 1)) bad(name + ": wrong number of arguments");
+        const int32_t at = node(nd.args[0]).type;
+        const bool integers_too = op == TGPU_OP_ABS || op == TGPU_OP_SIGN || op == TGPU_OP_FLOOR || op == TGPU_OP_CEILING || op == TGPU_OP_ROUND;
+        const bool integer = at == TGPU_BIGINT || at == TGPU_INTEGER;
+        if (at != TGPU_DOUBLE && !(integers_too && integer)) bad(name + ": wrong argument type");
+        if (two && node(nd.args[1]).type != TGPU_DOUBLE) bad(name + ": wrong argument type");
+        if (decimals && node(nd.args[1]).type != TGPU_INTEGER) bad(name + ": wrong argument type");
+        const bool predicate = op >= TGPU_OP_IS_NAN && op <= TGPU_OP_IS_INFINITE;
+        if (nd.type != (predicate ? TGPU_BOOLEAN : at)) bad(name + ": wrong result type");
+        long long dec = 0;
+        if (decimals) {
+            const tgpu_expr_node &dn = node(nd.args[1]);
+            if (dn.kind != TGPU_EX_CONST) fail(TGPU_ERR_NOT_SUPPORTED, name + ": the number of decimals must be an INTEGER constant");
+            dec = (long long)(int32_t)dn.ival;
+            if (dn.is_null) {   // a null argument: nothing is evaluated
+                Val r = declare(nd.type, d);
+                os << ind(d) << r.n << " = true;\n";
+                return r;
+            }
+        }
+        Val r = declare(nd.type, d);
+        // arguments left to right; the first null argument skips the rest and the call
+        os << ind(d) << "{\n";
+        std::vector<Val> a;
+        int dd = d + 1;
+        for (int k = 0; k < (decimals ? 1 : nd.n_args); k++) {
+            a.push_back(gen(nd.args[k], dd));
+            os << ind(dd) << "if (" << a.back().n << ") " << r.n << " = true; else {\n";
+            dd++;
+        }
+        const std::string &x = a[0].v;
+        auto set = [&](const std::string &e) { os << ind(dd) << r.v << " = " << e << ";\n"; };
+        const char *T = at == TGPU_BIGINT ? "long long" : "int";
+        switch (op) {
+        case TGPU_OP_ABS:
+            if (integer)   // :127-140: the minimum has no absolute value
+                os << ind(dd) << "if (" << x << " == " << (at == TGPU_BIGINT ? "(-9223372036854775807LL - 1)" : "(-2147483647 - 1)") << ") { "
+                   << raise(at == TGPU_BIGINT ? "TG_E_ABS_BIGINT" : "TG_E_ABS_INTEGER") << " " << r.n << " = true; } else " << r.v << " = " << x << " < 0 ? -" << x << " : " << x << ";\n";
+            else set("fabs(" + x + ")");
+            break;
+        case TGPU_OP_SIGN:
+            if (integer) set("(" + std::string(T) + ")((" + x + " > 0) - (" + x + " < 0))");
+            else { need_math_helpers(); set("tg_signum(" + x + ")"); }
+            break;
+        case TGPU_OP_FLOOR: set(integer ? x : "floor(" + x + ")"); break;
+        case TGPU_OP_CEILING: set(integer ? x : "ceil(" + x + ")"); break;
+        case TGPU_OP_TRUNCATE: need_math_helpers(); set("tg_truncate(" + x + ")"); break;
+        case TGPU_OP_ROUND:
+            if (integer && dec >= 0) set(x);   // roundLong :789-791
+            else if (integer && dec < -18)     // checkedPow(10, -decimals) overflows before num is looked at
+                os << ind(dd) << raise_operand("TG_E_ROUND", x) << " " << r.n << " = true;\n";
+            else if (integer) {
+                need_math_helpers();
+                long long factor = 1;
+                for (long long k = 0; k < -dec; k++) factor *= 10;
+                os << ind(dd) << "int o_ = 0; const long long t_ = tg_round_long((long long)" << x << ", " << factor << "LL, &o_);\n";
+                if (at == TGPU_INTEGER) os << ind(dd) << "if (t_ > 2147483647LL || t_ < -2147483648LL) o_ = 1;\n";
+                os << ind(dd) << "if (o_) { " << raise_operand("TG_E_ROUND", x) << " " << r.n << " = true; } else " << r.v << " = (" << T << ")t_;\n";
+            }
+            else {
+                // factor = the correctly rounded decimal 1e<d> (strtod): 10^d exactly for 0 <= d <= 22; +inf above 308 and 0 below -323
+                need_math_helpers();
+                const double factor = strtod(("1e" + std::to_string(dec)).c_str(), nullptr);
+                set("tg_round_double(" + x + ", " + (std::isinf(factor) ? fmt_double(factor) : hex_float(factor)) + ")");
+            }
+            break;
+        case TGPU_OP_SQRT: set("sqrt(" + x + ")"); break;
+        case TGPU_OP_CBRT: set("cbrt(" + x + ")"); break;
+        case TGPU_OP_EXP: set("exp(" + x + ")"); break;
+        case TGPU_OP_LN: set("log(" + x + ")"); break;
+        case TGPU_OP_LOG2: set("log(" + x + ") / " + hex_float(0.6931471805599453)); break;   // :481: Math.log(num) / Math.log(2), the double nearest ln 2
+        case TGPU_OP_LOG10: set("log10(" + x + ")"); break;
+        case TGPU_OP_LOG: set("log(" + a[1].v + ") / log(" + x + ")"); break;   // :473: log(base, number)
+        case TGPU_OP_POWER: need_math_helpers(); set("tg_pow(" + x + ", " + a[1].v + ")"); break;
+        case TGPU_OP_IS_NAN: set(x + " != " + x); break;
+        case TGPU_OP_IS_FINITE: set(x + " - " + x + " == 0.0"); break;
+        case TGPU_OP_IS_INFINITE: set(x + " == " + x + " && " + x + " - " + x + " != 0.0"); break;
+        case TGPU_OP_DEGREES: set(x + " * " + hex_float(57.29577951308232)); break;      // Math.toDegrees since JDK 9: one multiplication
+        case TGPU_OP_RADIANS: set(x + " * " + hex_float(0.017453292519943295)); break;   // Math.toRadians since JDK 9
+        default: bad("unknown math op");
+        }
+        for (size_t k = 0; k < a.size(); k++) os << ind(--dd) << "}\n";
         os << ind(d) << "}\n";
         return r;
     }
@@ -1447,6 +1573,9 @@ const char *kPrelude = R"SRC(
 #define TG_E_DIV0 7
 #define TG_E_CAST 9
 #define TG_E_CONCAT 10
+#define TG_E_ABS_BIGINT 11
+#define TG_E_ABS_INTEGER 12
+#define TG_E_ROUND 13
 #define TG_MAXC 24
 #define TG_MAXP 16
 struct FpArgs {
@@ -1461,6 +1590,8 @@ struct FpArgs {
   unsigned long long* error;
   long long n;
   unsigned long long* sel_mask;   // filter verdicts of pass 1, one 64-bit ballot per (tile, stripe, wave)
+  long long* operand;             // null, or where the lane that posts operand_key stores the operand of its failure
+  unsigned long long operand_key;
 };
 // first failing row wins (the reference throws at the first failing position)
 __device__ inline void tg_error(unsigned long long* e, long long row, int code) {
@@ -1574,10 +1705,40 @@ bool ExprProgram::can_raise(int root) const
             const int32_t from = nodes[(size_t)nd.args[0]].type;
             if (from == TGPU_DOUBLE || (from == TGPU_BIGINT && nd.type == TGPU_INTEGER)) return true;
         }
+        if (int_result && nd.op == TGPU_OP_ABS) return true;   // abs of the minimum
+        if (raises_with_operand_here(nd)) return true;
     }
     if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
         for (int k = 0; k < nd.n_args; k++)
             if (can_raise(nd.args[k])) return true;
+    return false;
+}
+
+// round(integer, d) with a constant d < 0: the rounded value can leave the type
+bool ExprProgram::raises_with_operand_here(const tgpu_expr_node &nd) const
+{
+    if (nd.kind != TGPU_EX_CALL || nd.op != TGPU_OP_ROUND || nd.n_args != 2 || (nd.type != TGPU_BIGINT && nd.type != TGPU_INTEGER)) return false;
+    if (nd.args[1] < 0 || nd.args[1] >= (int)nodes.size()) return false;
+    const tgpu_expr_node &dn = nodes[(size_t)nd.args[1]];
+    return dn.kind == TGPU_EX_CONST && !dn.is_null && (int32_t)dn.ival < 0;
+}
+
+bool ExprProgram::raises_with_operand(int root) const
+{
+    if (root < 0 || root >= (int)nodes.size()) return false;
+    const tgpu_expr_node &nd = nodes[(size_t)root];
+    if (raises_with_operand_here(nd)) return true;
+    if (nd.kind == TGPU_EX_CALL || nd.kind == TGPU_EX_SPECIAL)
+        for (int k = 0; k < nd.n_args && k < 3; k++)
+            if (raises_with_operand(nd.args[k])) return true;
+    return false;
+}
+
+bool ExprProgram::any_raises_with_operand() const
+{
+    if (raises_with_operand(filter_root)) return true;
+    for (int32_t r : proj_roots)
+        if (raises_with_operand(r)) return true;
     return false;
 }
 
@@ -1952,7 +2113,20 @@ bool PageProcessorGpu::process(Context *ctx, const DevicePage &in, DevicePage &o
     HIP_CHECK(hipMemsetAsync(err->ptr(), 0xff, 8, ctx->stream()));
     args.error = err->as<unsigned long long>();
 
-    auto raise_error = [&](unsigned long long e) { raise_expression_error(e); };
+    // A failure whose message names its operand (TG_E_ROUND): the kernel that raised runs once more over the same arguments -- it writes what
+    // it wrote before -- and the lane that posts the winning word stores its operand.
+    auto raise_error = [&](unsigned long long e) {
+        if (e != ~0ull && (int)(e & 0xff) == kErrorRoundOverflow) {
+            BufferPtr operand = ctx->alloc(8);
+            HIP_CHECK(hipMemsetAsync(operand->ptr(), 0, 8, ctx->stream()));
+            FpArgs again = args;
+            again.operand = operand->as<long long>();
+            again.operand_key = e;
+            launch((e >> 40) == 0 ? fn_count_ : fn_emit_, (int)tiles, again, ctx->stream());
+            raise_expression_error(e, ctx->read_scalar(operand->as<long long>()));
+        }
+        raise_expression_error(e);
+    };
     auto check_error = [&]() { raise_error(ctx->read_scalar(err->as<unsigned long long>())); };
 
     int64_t n_sel = n;
@@ -2722,6 +2896,7 @@ FusedProbeGpu::FusedProbeGpu(std::vector<int32_t> input_types, const tgpu_page_p
     for (size_t ch = 0; ch < prog_.proj_roots.size(); ch++)
         if ((int)ch != join_channel_ && prog_.can_raise(prog_.proj_roots[ch])) supported_ = false;
     key_can_raise_ = prog_.can_raise(prog_.proj_roots[(size_t)join_channel_]);
+    if (prog_.any_raises_with_operand()) supported_ = false;   // the message's operand is fetched by the page processor alone
     if (supported_) generate();
 }
 
@@ -3746,6 +3921,7 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
     }
     // nothing the accumulate kernels evaluate can raise (TPCH Q1: double arithmetic only): their error word is never written and
     // the per-page read-back of it is skipped
+    if (prog_.any_raises_with_operand()) supported_ = false;   // the message's operand is fetched by the page processor alone
     accumulate_can_raise_ = false;
     for (int ch : used) accumulate_can_raise_ = accumulate_can_raise_ || prog_.can_raise(prog_.proj_roots[(size_t)ch]);
     for (int ch = 0; ch < np; ch++)

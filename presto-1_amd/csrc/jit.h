@@ -26,6 +26,8 @@ struct FpArgs {  // must match the struct declared in the generated source
     unsigned long long *error;
     long long n;
     unsigned long long *sel_mask;
+    long long *operand;   // null, or where the lane that posts operand_key stores the operand of its failure (jit.cpp raise_operand)
+    unsigned long long operand_key;
 };
 
 // fp_vwrite, the write pass of the computed VARCHAR projections: fp_emit left each row's byte length in out_values[slot] (an int32 array), the
@@ -57,6 +59,11 @@ struct ExprProgram {
     // FilterAndProjectOperator evaluates every one on every selected row: that is only equivalent for projections that cannot raise, so the
     // fused generators keep the unfused composition for the others.
     bool can_raise(int root) const;
+    // ... with a message that carries an operand (round over integers with negative decimals).  Only the page processor fetches it: the
+    // fused generators keep the unfused composition for a program that has one.
+    bool raises_with_operand(int root) const;
+    bool any_raises_with_operand() const;
+    bool raises_with_operand_here(const tgpu_expr_node &nd) const;
     void inputs_of(int root, std::set<int> &out) const;   // the input channels the expression reads
     int identity_channel(int projection) const;            // the input channel a projection passes through, -1 when it is computed
     // the expression is null only if one of its input columns is (no null literal, no IF / COALESCE subtleties)

@@ -14,7 +14,9 @@ OPS = {"ADD": 1, "SUBTRACT": 2, "MULTIPLY": 3, "DIVIDE": 4, "MODULUS": 5, "NEGAT
        "LESS_THAN": 9, "LESS_THAN_OR_EQUAL": 10, "GREATER_THAN": 11, "GREATER_THAN_OR_EQUAL": 12, "NOT": 13, "CAST": 14, "LIKE": 15,
        "LENGTH": 16, "SUBSTR": 17, "CONCAT": 18, "STRPOS": 19, "STARTS_WITH": 20,
        "YEAR": 21, "QUARTER": 22, "MONTH": 23, "WEEK": 24, "DAY": 25, "DAY_OF_WEEK": 26, "DAY_OF_YEAR": 27, "YEAR_OF_WEEK": 28,
-       "LAST_DAY_OF_MONTH": 29, "DATE_TRUNC": 30, "DATE_ADD": 31, "DATE_DIFF": 32}
+       "LAST_DAY_OF_MONTH": 29, "DATE_TRUNC": 30, "DATE_ADD": 31, "DATE_DIFF": 32,
+       "ABS": 33, "SIGN": 34, "FLOOR": 35, "CEILING": 36, "TRUNCATE": 37, "ROUND": 38, "SQRT": 39, "CBRT": 40, "EXP": 41, "LN": 42, "LOG2": 43,
+       "LOG10": 44, "LOG": 45, "POWER": 46, "IS_NAN": 47, "IS_FINITE": 48, "IS_INFINITE": 49, "DEGREES": 50, "RADIANS": 51}
 FORMS = {"AND": 1, "OR": 2, "IF": 3, "IS_NULL": 4, "COALESCE": 5, "BETWEEN": 6, "IN": 7}
 _CMP = {"EQUAL", "NOT_EQUAL", "LESS_THAN", "LESS_THAN_OR_EQUAL", "GREATER_THAN", "GREATER_THAN_OR_EQUAL"}
 
@@ -156,6 +158,61 @@ def date_add(unit, value, d):
 def date_diff(unit, d1, d2):
     """date_diff(unit, d1, d2): the whole units from d1 to d2, negative when d2 < d1"""
     return call("DATE_DIFF", BIGINT, _wrap(unit, VARCHAR), _wrap(d1, DATE), _wrap(d2, DATE))
+
+
+# Math functions.  abs_ / sign / floor / ceiling / round_ keep the argument's type (BIGINT, INTEGER or DOUBLE); a Python float stands for a DOUBLE
+# constant, a Python int for a BIGINT one; every other function is over DOUBLE, where Python ints and floats both become DOUBLE constants.
+def _numeric(x):
+    if isinstance(x, RowExpression):
+        return x
+    return ConstantExpression(x, BIGINT if isinstance(x, int) and not isinstance(x, bool) else DOUBLE)
+
+
+def _same(name, x):
+    x = _numeric(x)
+    return call(name, x.type, x)
+
+
+def _double(name, *args):
+    return call(name, DOUBLE, *[_wrap(a, DOUBLE) for a in args])
+
+
+def abs_(x): return _same("ABS", x)
+def sign(x): return _same("SIGN", x)
+def floor(x): return _same("FLOOR", x)
+def ceiling(x): return _same("CEILING", x)
+def truncate(x): return _double("TRUNCATE", x)
+
+
+def round_(x, decimals=None):
+    """round(x) or round(x, decimals); decimals: a Python int or an INTEGER constant (the null literal: constant(None, INTEGER))"""
+    x = _numeric(x)
+    return call("ROUND", x.type, x) if decimals is None else call("ROUND", x.type, x, _wrap(decimals, INTEGER))
+
+
+def sqrt(x): return _double("SQRT", x)
+def cbrt(x): return _double("CBRT", x)
+def exp(x): return _double("EXP", x)
+def ln(x): return _double("LN", x)
+def log2(x): return _double("LOG2", x)
+def log10(x): return _double("LOG10", x)
+
+
+def log(b, x):
+    """log(b, x): the logarithm of x to the base b, ln(x) / ln(b)"""
+    return _double("LOG", b, x)
+
+
+def power(x, y): return _double("POWER", x, y)
+def is_nan(x): return call("IS_NAN", BOOLEAN, _wrap(x, DOUBLE))
+def is_finite(x): return call("IS_FINITE", BOOLEAN, _wrap(x, DOUBLE))
+def is_infinite(x): return call("IS_INFINITE", BOOLEAN, _wrap(x, DOUBLE))
+def degrees(x): return _double("DEGREES", x)
+def radians(x): return _double("RADIANS", x)
+
+
+ceil = ceiling
+pow_ = power
 
 
 class FlatProgram:
