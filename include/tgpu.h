@@ -80,7 +80,16 @@ typedef enum tgpu_type {
     TGPU_DATE = 3,     /* int32   IntArrayBlock (days) */
     TGPU_DOUBLE = 4,   /* IEEE double, LongArrayBlock bits */
     TGPU_BOOLEAN = 5,  /* 1 byte  ByteArrayBlock */
-    TGPU_VARCHAR = 6   /* VariableWidthBlock: byte pool + int32 offsets[n+1] */
+    TGPU_VARCHAR = 6,  /* VariableWidthBlock: byte pool + int32 offsets[n+1] */
+    /* timestamp(p), 0 <= p <= 6, without time zone: int64 microseconds since 1970-01-01 00:00:00 UTC in a LongArrayBlock
+     * (S/type/ShortTimestampType.java:48-75).  The precision is not part of the type code: a timestamp(p) value is a multiple of 10^(6-p) by
+     * construction, the library neither checks nor needs that, and the two functions whose result depends on p receive it on their node.
+     * BIGINT's twin wherever a value is carried, compared, hashed or ordered: ShortTimestampType.java:128-161 declares EQUAL (left == right),
+     * HASH_CODE (AbstractLongType.hash), XX_HASH_64 (XxHash64.hash), COMPARISON (Long.compare), LESS_THAN and LESS_THAN_OR_EQUAL, each with
+     * the body AbstractLongType.java:126-166 gives BIGINT (BigintType extends AbstractLongType and declares none of its own); neither declares
+     * IS_DISTINCT_FROM, which TypeOperators derives from EQUAL for both.  timestamp(p > 6) (LongTimestampType, a 12-byte Fixed12Block) and
+     * timestamp with time zone are not this type. */
+    TGPU_TIMESTAMP = 7
 } tgpu_type;
 
 typedef enum tgpu_encoding {
@@ -270,7 +279,8 @@ typedef enum tgpu_expr_op {
      * source is not part of the reference tree: beyond the reference's test literals Joda parity unpinned; the rule above is what the library
      * guarantees.
      *
-     * Out of the IR: CAST between DATE and any other type (TGPU_ERR_COMPILER), the TIMESTAMP / TIME / INTERVAL variants of these functions,
+     * Out of the IR: CAST between DATE and any other type but TIMESTAMP (TGPU_ERR_COMPILER), the TIME / INTERVAL variants of these functions
+     * (the TIMESTAMP variants: below, at TGPU_OP_HOUR),
      * date_format / date_parse / to_iso8601 / current_date and the date + interval operators (a planner folds constant intervals into
      * date_add). */
     TGPU_OP_YEAR = 21,
@@ -356,7 +366,60 @@ typedef enum tgpu_expr_op {
     TGPU_OP_IS_FINITE = 48,
     TGPU_OP_IS_INFINITE = 49,
     TGPU_OP_DEGREES = 50,
-    TGPU_OP_RADIANS = 51
+    TGPU_OP_RADIANS = 51,
+    /* TIMESTAMP functions (M/operator/scalar/timestamp/), over TGPU_TIMESTAMP = int64 microseconds since 1970-01-01 00:00:00 UTC, precision
+     * p <= 6.  INPUT and CONST nodes of type TIMESTAMP carry microseconds (CONST: ival).  The six comparisons, BETWEEN, IN, IS_NULL, IF and
+     * COALESCE take TIMESTAMP exactly as they take BIGINT.
+     *
+     * Throughout: ms = floordiv(us, 1000) (DateTimes.scaleEpochMicrosToMillis), day = floordiv(ms, 86 400 000), tod = ms - day * 86 400 000.
+     * day always fits int32 (|day| <= 106 751 992); the calendar is the DATE functions' (csrc/device_date.h), the arithmetic around it is
+     * csrc/device_timestamp.h.
+     *
+     *   TGPU_OP_YEAR .. TGPU_OP_YEAR_OF_WEEK  (TIMESTAMP) -> BIGINT   the DATE function of `day` (ExtractYear.java etc.: the Joda field of
+     *                             scaleEpochMicrosToMillis)
+     *   TGPU_OP_LAST_DAY_OF_MONTH (TIMESTAMP) -> DATE       the DATE function of `day` (LastDayOfMonth.java); cannot leave int32 here
+     *   TGPU_OP_HOUR, TGPU_OP_MINUTE, TGPU_OP_SECOND, TGPU_OP_MILLISECOND   (TIMESTAMP) -> BIGINT   tod / 3 600 000, tod / 60 000 % 60,
+     *                             tod / 1000 % 60, tod % 1000 (ExtractHour.java ...)
+     *   TGPU_OP_TO_UNIXTIME       (TIMESTAMP) -> DOUBLE     (double) us / 1000000.0: one int64 -> double conversion and one IEEE division,
+     *                             bit for bit (ToUnixTime.java)
+     *   TGPU_OP_DATE_TRUNC        (VARCHAR unit, TIMESTAMP) -> TIMESTAMP   DateTrunc.java: ms floored to the unit (week: Monday 00:00), then
+     *                             x 1000; the sub-millisecond part is dropped
+     *   TGPU_OP_DATE_ADD          (VARCHAR unit, BIGINT value, TIMESTAMP) -> TIMESTAMP   DateAdd.java:41-57.  The node's ival is the argument's
+     *                             precision p (0..6).  value must fit int32 (toIntExact).  The precise units add value * unit_ms to ms; month /
+     *                             quarter / year move the (year, month) of `day` with the day of the month clamped and keep tod.  For p <= 3
+     *                             the millisecond result is rounded with DateTimes.round(ms, 3 - p).  Result ms' * 1000 + floormod(us, 1000)
+     *   TGPU_OP_DATE_DIFF         (VARCHAR unit, TIMESTAMP t1, TIMESTAMP t2) -> BIGINT   DateDiff.java, on ms1 and ms2.  Precise units:
+     *                             (ms2 - ms1) / unit_ms truncated toward zero.  month: for t2 >= t1 the largest n >= 0 with
+     *                             add_months(ms1, n) <= ms2, else the negated count the other way; quarter = months / 3, year = months / 12
+     *   TGPU_OP_CAST              (DATE) -> TIMESTAMP       TimeUnit.DAYS.toMicros (DateToTimestampCast.java), which SATURATES at the int64 ends
+     *                             for days beyond +-106 751 991.  No error
+     *                             (TIMESTAMP) -> DATE       floordiv(us, 86 400 000 000) (TimestampToDateCast.java)
+     *                             (TIMESTAMP) -> TIMESTAMP  the node's ival is the target precision q (0..6): roundDiv(us, 10^(6-q)) * 10^(6-q)
+     *                             with roundDiv as M/type/DateTimes.java:104-117 writes it -- (v + f/2) / f for v >= 0, (v + 1 - f/2) / f for v < 0,
+     *                             Java's truncating division: to the nearest, a positive tie up and a negative tie toward zero -- in 64-bit
+     *                             two's-complement arithmetic, wraparound included.  q = 6 is the identity
+     *
+     * Units.  'millisecond', 'second', 'minute', 'hour', 'day', 'week', 'month', 'quarter' or 'year' (getTimestampField,
+     * DateTimeFunctions.java:323-347), a TGPU_EX_CONST VARCHAR node matched after ASCII lower-casing; TGPU_ERR_NOT_SUPPORTED when it is no
+     * constant.  Any other string fails when the factory is created with TGPU_ERR_INVALID_ARGUMENT and the reference's message
+     * "'<lower-cased unit>' is not a valid Timestamp field".  Nulls: the usual first-null-argument rule, the unit included.
+     *
+     * Errors.  A row fails with TGPU_ERR_NUMERIC_VALUE_OUT_OF_RANGE when date_add's value lies outside int32 or when a date_trunc / date_add
+     * result is not an int64 count of microseconds (where the reference's toIntExact / multiplyExact throw; the library also fails where the
+     * reference's last addition of the microseconds of the millisecond would wrap).  The rule for which error of a page wins is the checked
+     * arithmetic's.  No intermediate value overflows silently; the months index is kept in 64 bits.  Wrong argument types, counts, result
+     * types or a precision outside 0..6: TGPU_ERR_COMPILER.
+     *
+     * date_diff in months, quarters and years: as for DATE, Joda's source is not part of the reference tree; beyond the reference's test
+     * literals Joda parity is unpinned and the rule above is what the library guarantees.
+     *
+     * Out of the IR: CAST between TIMESTAMP and VARCHAR (and any type but DATE), date_format / date_parse / to_iso8601, from_unixtime (its
+     * result carries a zone), the timestamp +- interval operators, TIME, timestamp(p > 6) and timestamp with time zone. */
+    TGPU_OP_HOUR = 52,
+    TGPU_OP_MINUTE = 53,
+    TGPU_OP_SECOND = 54,
+    TGPU_OP_MILLISECOND = 55,
+    TGPU_OP_TO_UNIXTIME = 56
 } tgpu_expr_op;
 typedef enum tgpu_special_form { /* M/sql/relational/SpecialForm.java:137-152 */
     TGPU_SF_AND = 1, TGPU_SF_OR, TGPU_SF_IF, TGPU_SF_IS_NULL, TGPU_SF_COALESCE, TGPU_SF_BETWEEN,
@@ -377,7 +440,7 @@ typedef struct tgpu_expr_node {
     int32_t n_args;
     int32_t args[3];   /* indices into the node array */
     int32_t is_null;   /* CONST: null literal */
-    int64_t ival;      /* CONST BIGINT/INTEGER/DATE/BOOLEAN value; VARCHAR: offset into string_pool */
+    int64_t ival;      /* CONST BIGINT/INTEGER/DATE/BOOLEAN/TIMESTAMP value; VARCHAR: offset into string_pool; DATE_ADD / CAST over TIMESTAMP: precision */
     double dval;       /* CONST DOUBLE */
     int32_t slen;      /* CONST VARCHAR length */
     int32_t pad;
@@ -429,7 +492,13 @@ typedef enum tgpu_agg_function {
      * TGPU_ERR_NOT_SUPPORTED at creation.  A result channel of more than 2^31 - 1 bytes fails with TGPU_ERR_INSUFFICIENT_RESOURCES,
      * "variable width block cannot exceed 2GB". */
     TGPU_AGG_MIN_VARCHAR = 15,  /* min(varchar)    one VARCHAR channel; output VARCHAR */
-    TGPU_AGG_MAX_VARCHAR = 16   /* max(varchar) */
+    TGPU_AGG_MAX_VARCHAR = 16,  /* max(varchar) */
+    /* ShortTimestampType is a long.class type as well: NullableLongState and LONG_INPUT / LONG_COMBINE over the int64 microseconds, which is
+     * min / max(bigint) on the same values (nothing is narrowed).  PARTIAL gives min(bigint)'s layout (count BIGINT, extreme BIGINT), SINGLE /
+     * FINAL one TIMESTAMP channel.  Hash aggregation (spilled or not), the fused filter / project aggregation and the streaming aggregation
+     * take them; window aggregates do not.  sum / avg over a TIMESTAMP channel: TGPU_ERR_INVALID_ARGUMENT like any wrong input type. */
+    TGPU_AGG_MIN_TIMESTAMP = 17, /* min(timestamp(p)), p <= 6   one TIMESTAMP channel; output TIMESTAMP */
+    TGPU_AGG_MAX_TIMESTAMP = 18  /* max(timestamp(p)) */
 } tgpu_agg_function;
 
 typedef struct tgpu_agg_spec {

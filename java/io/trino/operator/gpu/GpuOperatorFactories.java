@@ -123,7 +123,7 @@ public final class GpuOperatorFactories
 
     /**
      * HashAggregationOperatorFactory (operator/HashAggregationOperator.java:54-262).  aggregates: {tgpu_agg_function, input channel, mask channel} triples
-     * resolved by the caller from the AccumulatorFactories' bound signatures (count / sum / avg over BIGINT and DOUBLE, min / max over BIGINT, DOUBLE, INTEGER, DATE and VARCHAR; anything else -> Optional.empty()).
+     * resolved by the caller from the AccumulatorFactories' bound signatures (count / sum / avg over BIGINT and DOUBLE, min / max over BIGINT, DOUBLE, INTEGER, DATE, VARCHAR and short timestamps (TGPU_AGG_MIN_TIMESTAMP = 17 / TGPU_AGG_MAX_TIMESTAMP = 18); anything else -> Optional.empty()).
      * min / max over VARCHAR cannot spill: with spillEnabled such a plan keeps the Java operator.
      */
     public Optional<OperatorFactory> hashAggregation(int operatorId, PlanNodeId planNodeId, List<Type> inputTypes, List<Type> groupByTypes, List<Integer> groupByChannels, Step step,
@@ -608,7 +608,7 @@ public final class GpuOperatorFactories
     {
         int[] codes;
         try {
-            codes = GpuPages.typeCodes(sourceTypes);
+            codes = windowTypeCodes(sourceTypes);
         }
         catch (IllegalArgumentException unsupportedType) {
             return Optional.empty();
@@ -620,6 +620,21 @@ public final class GpuOperatorFactories
         long factory = GpuNative.createWindowFactory(context, operatorId, codes, ints(outputChannels), flat, ints(partitionChannels), ints(sortChannels),
                 sortOrders.stream().mapToInt(SortOrder::ordinal).toArray(), expectedPositions);
         return Optional.of(new GpuOperatorFactory(operatorId, planNodeId, "GpuWindowOperator", sourceTypes, poller, factory));
+    }
+
+    /**
+     * the type codes of a window node's source channels.  The native window entry points take the codes 1..6: a node with a timestamp channel keeps the
+     * Java operator (the library's own window factories take TGPU_TIMESTAMP channels, include/tgpu.h)
+     */
+    private static int[] windowTypeCodes(List<Type> sourceTypes)
+    {
+        int[] codes = GpuPages.typeCodes(sourceTypes);
+        for (int code : codes) {
+            if (code == GpuPages.T_TIMESTAMP) {
+                throw new IllegalArgumentException("timestamp channels are not handed to the native window factories");
+            }
+        }
+        return codes;
     }
 
     /** one frame as the five ints of tgpu_window_frame_spec, from the fields of a FrameInfo (operator/window/FrameInfo.java); the channels are read for PRECEDING / FOLLOWING bounds only */
@@ -647,7 +662,7 @@ public final class GpuOperatorFactories
         }
         int[] codes;
         try {
-            codes = GpuPages.typeCodes(sourceTypes);
+            codes = windowTypeCodes(sourceTypes);
         }
         catch (IllegalArgumentException unsupportedType) {
             return Optional.empty();
@@ -691,7 +706,7 @@ public final class GpuOperatorFactories
         }
         int[] codes;
         try {
-            codes = GpuPages.typeCodes(sourceTypes);
+            codes = windowTypeCodes(sourceTypes);
         }
         catch (IllegalArgumentException unsupportedType) {
             return Optional.empty();

@@ -37,7 +37,7 @@ import static io.trino.spi.type.IntegerType.INTEGER;
 public final class GpuPages
 {
     // tgpu_type / tgpu_encoding (include/tgpu.h)
-    public static final int T_BIGINT = 1, T_INTEGER = 2, T_DATE = 3, T_DOUBLE = 4, T_BOOLEAN = 5, T_VARCHAR = 6;
+    public static final int T_BIGINT = 1, T_INTEGER = 2, T_DATE = 3, T_DOUBLE = 4, T_BOOLEAN = 5, T_VARCHAR = 6, T_TIMESTAMP = 7;
     public static final int FLAT = 0, DICTIONARY = 1, RLE = 2;
 
     private static final Cleaner CLEANER = Cleaner.create();
@@ -52,6 +52,9 @@ public final class GpuPages
         if (type.equals(DOUBLE)) return T_DOUBLE;
         if (type.equals(BOOLEAN)) return T_BOOLEAN;
         if (type instanceof io.trino.spi.type.VarcharType) return T_VARCHAR;
+        // timestamp(p), p <= 6: epoch microseconds in a LongArrayBlock (ShortTimestampType.java:48-75).  timestamp(p > 6) is a LongTimestampType over a
+        // 12-byte block and timestamp with time zone is another type altogether: both fall through, and the plan node keeps the Java operator
+        if (type instanceof io.trino.spi.type.TimestampType && ((io.trino.spi.type.TimestampType) type).isShort()) return T_TIMESTAMP;
         throw new IllegalArgumentException("type not supported by the GPU operators: " + type);   // the planner keeps the Java operator for such plan nodes
     }
 
@@ -172,7 +175,7 @@ public final class GpuPages
             GpuNative.blockInfo(page, ch, info);
             types[ch] = (int) info[0];
             switch (types[ch]) {
-                case T_BIGINT: case T_DOUBLE: values[ch] = new long[positions]; break;
+                case T_BIGINT: case T_DOUBLE: case T_TIMESTAMP: values[ch] = new long[positions]; break;
                 case T_INTEGER: case T_DATE: values[ch] = new int[positions]; break;
                 case T_BOOLEAN: values[ch] = new byte[positions]; break;
                 default: values[ch] = new byte[(int) info[1]]; offsets[ch] = new int[positions + 1];
@@ -184,7 +187,7 @@ public final class GpuPages
         for (int ch = 0; ch < channels; ch++) {
             Optional<boolean[]> isNull = Optional.ofNullable((boolean[]) nulls[ch]);
             switch (types[ch]) {
-                case T_BIGINT: case T_DOUBLE: blocks[ch] = new LongArrayBlock(positions, isNull, (long[]) values[ch]); break;
+                case T_BIGINT: case T_DOUBLE: case T_TIMESTAMP: blocks[ch] = new LongArrayBlock(positions, isNull, (long[]) values[ch]); break;
                 case T_INTEGER: case T_DATE: blocks[ch] = new IntArrayBlock(positions, isNull, (int[]) values[ch]); break;
                 case T_BOOLEAN: blocks[ch] = new ByteArrayBlock(positions, isNull, (byte[]) values[ch]); break;
                 default: blocks[ch] = new VariableWidthBlock(positions, Slices.wrappedBuffer((byte[]) values[ch]), (int[]) offsets[ch], isNull);
@@ -253,7 +256,7 @@ public final class GpuPages
         Object[] dValues = new Object[n], dNulls = new Object[n], dOffsets = new Object[n];
         for (int ch = 0; ch < n; ch++) {
             BlockArrays a = arraysOf(page.getBlock(ch), channelTypes.get(ch));
-            types[ch] = typeCode(channelTypes.get(ch));     // LongArrayBlock holds BIGINT or DOUBLE, IntArrayBlock INTEGER or DATE: the operator's input types decide
+            types[ch] = typeCode(channelTypes.get(ch));     // LongArrayBlock holds BIGINT, DOUBLE or TIMESTAMP, IntArrayBlock INTEGER or DATE: the operator's input types decide
             encodings[ch] = a.encoding;
             arrayOffsets[ch] = a.arrayOffset;
             dictionaryPositions[ch] = a.dictionaryPositions;

@@ -5,6 +5,7 @@ import io.trino.spi.type.BigintType;
 import io.trino.spi.type.DateType;
 import io.trino.spi.type.DoubleType;
 import io.trino.spi.type.IntegerType;
+import io.trino.spi.type.TimestampType;
 import io.trino.spi.type.Type;
 import io.trino.spi.type.VarcharType;
 import io.trino.sql.relational.CallExpression;
@@ -46,6 +47,10 @@ public final class GpuRowExpressions
     // floor :390-409, log :473, power :561, round :724-833, sign :1085-1125)
     private static final int OP_MODULUS = 5, OP_ABS = 33, OP_SIGN = 34, OP_FLOOR = 35, OP_CEILING = 36, OP_TRUNCATE = 37, OP_ROUND = 38, OP_SQRT = 39, OP_CBRT = 40, OP_EXP = 41;
     private static final int OP_LN = 42, OP_LOG2 = 43, OP_LOG10 = 44, OP_LOG = 45, OP_POWER = 46, OP_IS_NAN = 47, OP_IS_FINITE = 48, OP_IS_INFINITE = 49, OP_DEGREES = 50, OP_RADIANS = 51;
+    // TGPU_OP_HOUR .. TGPU_OP_TO_UNIXTIME and the timestamp flavours of TGPU_OP_YEAR .. TGPU_OP_DATE_DIFF: operator/scalar/timestamp/ (ExtractHour.java,
+    // ExtractMinute.java, ExtractSecond.java, ExtractMillisecond.java, ToUnixTime.java; DateTrunc.java, DateAdd.java, DateDiff.java ...), over a short timestamp(p)
+    private static final int OP_HOUR = 52, OP_MINUTE = 53, OP_SECOND = 54, OP_MILLISECOND = 55, OP_TO_UNIXTIME = 56;
+    private static final int T_TIMESTAMP = GpuPages.T_TIMESTAMP;
 
     public static final class Program
     {
@@ -138,6 +143,16 @@ public final class GpuRowExpressions
                 int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
                 return emit(p, CALL, type, dateOp, args, false, 0, 0, 0);
             }
+            int timestampOp = dateOp != 0 ? dateOp : timestampFunction(name, call.getArguments().size());
+            if (timestampOp != 0 && overTimestamps(timestampOp, call.getArguments())) {
+                int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
+                // date_add rounds its millisecond result to the argument's precision when that is 3 or less (DateAdd.java:50-52): the node carries p
+                long precision = timestampOp == OP_DATE_ADD ? ((TimestampType) call.getArguments().get(2).getType()).getPrecision() : 0;
+                return emit(p, CALL, type, timestampOp, args, false, precision, 0, 0);
+            }
+            if (isTimestampCast(name, call)) {
+                return addTimestampCast(p, type, call);
+            }
             if (call.getArguments().isEmpty() && call.getType() instanceof DoubleType) {
                 Double constant = mathConstant(name);
                 if (constant != null) {
@@ -151,6 +166,9 @@ public final class GpuRowExpressions
             }
             for (int op = 1; op < OPERATORS.length; op++) {
                 if (OPERATORS[op].equalsIgnoreCase(name)) {
+                    if (op == OP_CAST && (type == T_TIMESTAMP || call.getArguments().stream().anyMatch(a -> isShortTimestamp(a.getType())))) {
+                        throw new IllegalArgumentException("CAST between timestamp and " + call.getType() + " is not in the GPU IR");   // (date and timestamp(p): above)
+                    }
                     int[] args = call.getArguments().stream().mapToInt(a -> add(p, a)).toArray();
                     return emit(p, CALL, type, op, args, false, 0, 0, 0);
                 }
@@ -228,8 +246,8 @@ public final class GpuRowExpressions
     }
 
     /**
-     * The same names exist over timestamps, times and intervals: only the DATE flavour is in the IR, every other one falls through to
-     * "function not in the GPU IR".  The unit of date_trunc / date_add / date_diff is a varchar, which the library wants constant.
+     * The same names exist over timestamps, times and intervals: the DATE flavour is decided here, the short-timestamp flavour by
+     * overTimestamps, every other one falls through to "function not in the GPU IR".  The unit of date_trunc / date_add / date_diff is a varchar, which the library wants constant.
      */
     private static boolean overDates(int op, List<RowExpression> arguments)
     {
@@ -241,6 +259,74 @@ public final class GpuRowExpressions
         }
         boolean dates = arguments.get(arguments.size() - 1).getType() instanceof DateType;
         return op == OP_DATE_DIFF ? dates && arguments.get(1).getType() instanceof DateType : dates;
+    }
+
+    /** the functions that exist over timestamps only (operator/scalar/timestamp/ExtractHour.java ... ToUnixTime.java) */
+    private static int timestampFunction(String name, int arguments)
+    {
+        switch (name.toLowerCase(java.util.Locale.ENGLISH)) {
+            case "hour": return arguments == 1 ? OP_HOUR : 0;
+            case "minute": return arguments == 1 ? OP_MINUTE : 0;
+            case "second": return arguments == 1 ? OP_SECOND : 0;
+            case "millisecond": return arguments == 1 ? OP_MILLISECOND : 0;
+            case "to_unixtime": return arguments == 1 ? OP_TO_UNIXTIME : 0;
+            default: return 0;
+        }
+    }
+
+    /** timestamp(p) with p <= 6: epoch microseconds in a long.  timestamp(p > 6) and timestamp with time zone are outside the IR */
+    private static boolean isShortTimestamp(io.trino.spi.type.Type type)
+    {
+        return type instanceof TimestampType && ((TimestampType) type).isShort();
+    }
+
+    /** the timestamp flavour of a date / time function: its last argument (date_diff: its last two) is a short timestamp; the unit is a varchar */
+    private static boolean overTimestamps(int op, List<RowExpression> arguments)
+    {
+        if (op < OP_DATE_TRUNC || op >= OP_HOUR) {
+            return isShortTimestamp(arguments.get(0).getType());
+        }
+        if (!(arguments.get(0).getType() instanceof VarcharType)) {
+            return false;
+        }
+        boolean timestamps = isShortTimestamp(arguments.get(arguments.size() - 1).getType());
+        return op == OP_DATE_DIFF ? timestamps && isShortTimestamp(arguments.get(1).getType()) : timestamps;
+    }
+
+    /**
+     * CAST(date AS timestamp(p)) (DateToTimestampCast.java), CAST(timestamp(p) AS date) and its function name date(t) (TimestampToDateCast.java) and
+     * CAST(timestamp(p) AS timestamp(q)) (TimestampToTimestampCast.java), short timestamps only
+     */
+    private static boolean isTimestampCast(String name, CallExpression call)
+    {
+        if (call.getArguments().size() != 1) {
+            return false;
+        }
+        io.trino.spi.type.Type from = call.getArguments().get(0).getType();
+        io.trino.spi.type.Type to = call.getType();
+        if ("date".equalsIgnoreCase(name)) {
+            return isShortTimestamp(from) && to instanceof DateType;
+        }
+        if (!CAST_OPERATOR.equalsIgnoreCase(name)) {
+            return false;
+        }
+        return (isShortTimestamp(from) && (to instanceof DateType || isShortTimestamp(to))) || (from instanceof DateType && isShortTimestamp(to));
+    }
+
+    /**
+     * The CAST node's long is the target precision of a timestamp -> timestamp cast that narrows: the library rounds to it as shortToShort does
+     * (TimestampToTimestampCast.java:37-49).  A widening cast returns its argument there, which is the node's 6
+     */
+    private static int addTimestampCast(Program p, int type, CallExpression call)
+    {
+        RowExpression argument = call.getArguments().get(0);
+        long precision = 0;
+        if (isShortTimestamp(argument.getType()) && isShortTimestamp(call.getType())) {
+            int source = ((TimestampType) argument.getType()).getPrecision();
+            int target = ((TimestampType) call.getType()).getPrecision();
+            precision = source <= target ? 6 : target;
+        }
+        return emit(p, CALL, type, OP_CAST, new int[] {add(p, argument)}, false, precision, 0, 0);
     }
 
     /**

@@ -190,7 +190,7 @@ typedef struct {
 
 static void *pin(JNIEnv *env, jarray a) { return a ? (*env)->GetPrimitiveArrayCritical(env, a, NULL) : NULL; }
 static void unpin(JNIEnv *env, jarray a, void *p, jint mode) { if (a && p) (*env)->ReleasePrimitiveArrayCritical(env, a, p, mode); }
-static int width_of(jint t) { return t == TGPU_BIGINT || t == TGPU_DOUBLE ? 8 : (t == TGPU_INTEGER || t == TGPU_DATE ? 4 : 1); }
+static int width_of(jint t) { return t == TGPU_BIGINT || t == TGPU_DOUBLE || t == TGPU_TIMESTAMP ? 8 : (t == TGPU_INTEGER || t == TGPU_DATE ? 4 : 1); }
 
 /* GpuPages hands every channel as parallel arrays: per channel i
  *   types[i], encodings[i] (TGPU_FLAT / TGPU_DICTIONARY / TGPU_RLE), arrayOffsets[i], dictionaryPositions[i],

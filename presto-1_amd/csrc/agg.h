@@ -34,8 +34,8 @@ constexpr int64_t kOrdHandoffRows = 4096;
 // the sign-extended value -- 4-byte signed load of raw input, 8-byte intermediates, 4-byte store of the output -- and never see these codes
 inline int32_t agg_kernel_function(int32_t f)
 {
-    if (f == TGPU_AGG_MIN_INTEGER || f == TGPU_AGG_MIN_DATE) return TGPU_AGG_MIN_BIGINT;
-    if (f == TGPU_AGG_MAX_INTEGER || f == TGPU_AGG_MAX_DATE) return TGPU_AGG_MAX_BIGINT;
+    if (f == TGPU_AGG_MIN_INTEGER || f == TGPU_AGG_MIN_DATE || f == TGPU_AGG_MIN_TIMESTAMP) return TGPU_AGG_MIN_BIGINT;
+    if (f == TGPU_AGG_MAX_INTEGER || f == TGPU_AGG_MAX_DATE || f == TGPU_AGG_MAX_TIMESTAMP) return TGPU_AGG_MAX_BIGINT;
     return f;
 }
 // the int32-stored type of such an aggregate's input and output channel, 0 for every other function
@@ -45,9 +45,16 @@ inline int32_t agg_narrow_type(int32_t f)
     if (f == TGPU_AGG_MIN_DATE || f == TGPU_AGG_MAX_DATE) return TGPU_DATE;
     return 0;
 }
+// the type of the input and output channel of an aggregate that runs as another type's function: the int32-stored types above and
+// TIMESTAMP, whose int64 microseconds are min / max(bigint)'s input as they stand (nothing narrow); 0 for every other function
+inline int32_t agg_own_type(int32_t f)
+{
+    if (f == TGPU_AGG_MIN_TIMESTAMP || f == TGPU_AGG_MAX_TIMESTAMP) return TGPU_TIMESTAMP;
+    return agg_narrow_type(f);
+}
 // min / max over VARCHAR: state of variable width, kept beside the fixed-width states and run as launches of their own (minmax_varchar.h)
 inline bool agg_is_varchar_extreme(int32_t f) { return f == TGPU_AGG_MIN_VARCHAR || f == TGPU_AGG_MAX_VARCHAR; }
-inline bool agg_function_known(int32_t f) { return f >= TGPU_AGG_COUNT_ALL && f <= TGPU_AGG_MAX_VARCHAR; }
+inline bool agg_function_known(int32_t f) { return f >= TGPU_AGG_COUNT_ALL && f <= TGPU_AGG_MAX_TIMESTAMP; }
 inline int64_t ord_chain_max_groups() { const char *e = getenv("TGPU_ORD_CHAIN_MAX_GROUPS"); return e ? atoll(e) : kOrdChainMaxGroups; }   // (the variable: kernel study)
 
 class GroupedAccumulators {

@@ -734,8 +734,8 @@ __global__ void __launch_bounds__(kBlock) agg_evaluate_kernel(EvalArgs args, int
 
 bool is_double_state(int32_t f) { return f == TGPU_AGG_SUM_DOUBLE || f == TGPU_AGG_AVG_DOUBLE || f == TGPU_AGG_AVG_BIGINT; }
 bool is_count(int32_t f) { return f == TGPU_AGG_COUNT_ALL || f == TGPU_AGG_COUNT_COLUMN; }
-// (these take a tgpu_agg_function as the caller gave it: INTEGER / DATE extremes answer as the BIGINT function they run as)
-bool is_minmax(int32_t f) { return f >= TGPU_AGG_MIN_BIGINT && f <= TGPU_AGG_MAX_DATE; }
+// (these take a tgpu_agg_function as the caller gave it: INTEGER / DATE / TIMESTAMP extremes answer as the BIGINT function they run as)
+bool is_minmax(int32_t f) { return (f >= TGPU_AGG_MIN_BIGINT && f <= TGPU_AGG_MAX_DATE) || f == TGPU_AGG_MIN_TIMESTAMP || f == TGPU_AGG_MAX_TIMESTAMP; }
 bool is_bigint_state(int32_t f) { return f == TGPU_AGG_SUM_BIGINT || is_minmax(f); }   // two 64-bit words per group (128-bit sum / extreme code)
 // the type of the aggregate's value channel (PARTIAL's second channel; input and output unless agg_narrow_type names an int32 type)
 bool bigint_valued(int32_t f) { f = agg_kernel_function(f); return f == TGPU_AGG_SUM_BIGINT || f == TGPU_AGG_MIN_BIGINT || f == TGPU_AGG_MAX_BIGINT; }
@@ -1285,7 +1285,7 @@ void GroupedAccumulators::add_input_states(const int32_t *gids, int64_t n, const
             if (bigint_valued(st.spec.function) || st.spec.function == TGPU_AGG_AVG_BIGINT) want = TGPU_BIGINT;
             if (st.spec.function == TGPU_AGG_MIN_DOUBLE || st.spec.function == TGPU_AGG_MAX_DOUBLE) want = TGPU_DOUBLE;
             if (st.spec.function == TGPU_AGG_SUM_DOUBLE || st.spec.function == TGPU_AGG_AVG_DOUBLE) want = TGPU_DOUBLE;
-            if (agg_narrow_type(st.spec.function)) want = agg_narrow_type(st.spec.function);
+            if (agg_own_type(st.spec.function)) want = agg_own_type(st.spec.function);
             check_channel(page, st.spec.input_channel, want, "aggregate input");
             a.input = page.cols[st.spec.input_channel].values;
             a.input_nulls = page.cols[st.spec.input_channel].nulls;
@@ -1517,7 +1517,7 @@ void GroupedAccumulators::evaluate_states(int64_t groups, std::vector<DeviceColu
             }
         }
         else {
-            c0.type = agg_narrow_type(st.spec.function) ? agg_narrow_type(st.spec.function) : (bigint_valued(st.spec.function) ? TGPU_BIGINT : TGPU_DOUBLE);
+            c0.type = agg_own_type(st.spec.function) ? agg_own_type(st.spec.function) : (bigint_valued(st.spec.function) ? TGPU_BIGINT : TGPU_DOUBLE);
             c0.nulls_buf = ctx_->alloc((size_t)alloc_n);
             c0.nulls = c0.nulls_buf->as<uint8_t>();
             a.out0_nulls = c0.nulls_buf->as<uint8_t>();

@@ -54,13 +54,13 @@ void set_last_error(const std::string &msg);
 inline int type_width(int32_t t)
 {
     switch (t) {
-    case TGPU_BIGINT: case TGPU_DOUBLE: return 8;
+    case TGPU_BIGINT: case TGPU_DOUBLE: case TGPU_TIMESTAMP: return 8;
     case TGPU_INTEGER: case TGPU_DATE: return 4;
     case TGPU_BOOLEAN: return 1;
     default: return 0;
     }
 }
-inline bool valid_type(int32_t t) { return t >= TGPU_BIGINT && t <= TGPU_VARCHAR; }
+inline bool valid_type(int32_t t) { return t >= TGPU_BIGINT && t <= TGPU_TIMESTAMP; }
 const char *type_name(int32_t t);
 
 class Context;

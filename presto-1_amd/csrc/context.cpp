@@ -20,6 +20,7 @@ const char *type_name(int32_t t)
     case TGPU_DOUBLE: return "double";
     case TGPU_BOOLEAN: return "boolean";
     case TGPU_VARCHAR: return "varchar";
+    case TGPU_TIMESTAMP: return "timestamp";
     default: return "?";
     }
 }

@@ -26,6 +26,9 @@
 // min / max over VARCHAR have kernels of their own (minmax_varchar.hip) and are in none of the switches below
 #define TG_AGG_MIN_VARCHAR 15
 #define TG_AGG_MAX_VARCHAR 16
+// min / max over TIMESTAMP arrive as TG_AGG_MIN_BIGINT / TG_AGG_MAX_BIGINT as well (int64 microseconds: the same load width)
+#define TG_AGG_MIN_TIMESTAMP 17
+#define TG_AGG_MAX_TIMESTAMP 18
 
 // per-aggregate state arrays in HBM, indexed by group id
 struct TgAggState {

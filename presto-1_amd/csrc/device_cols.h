@@ -23,7 +23,8 @@ __device__ inline tg_i64 tg_hash_cell(const TgColView &c, long long r)
 {
     if (c.nulls && c.nulls[r]) return 0;
     switch (c.type) {
-    case 1: return tg_hash_long(((const tg_i64 *)c.values)[r]);
+    case 1:
+    case 7: return tg_hash_long(((const tg_i64 *)c.values)[r]);
     case 2:
     case 3: return tg_hash_int(((const int *)c.values)[r]);
     case 4: return tg_hash_double_bits(((const tg_u64 *)c.values)[r]);
@@ -60,6 +61,7 @@ __device__ inline bool tg_rows_not_distinct(const TgKeyCols &a, long long ra, co
         }
         switch (x.type) {
         case 1:
+        case 7:
             if (((const tg_i64 *)x.values)[ra] != ((const tg_i64 *)y.values)[rb]) return false;
             break;
         case 2:
@@ -115,6 +117,7 @@ __device__ inline bool tg_rows_not_distinct_u(const TgKeyCols &a, long long ra, 
         }
         switch (x.type) {
         case 1:
+        case 7:
             if (((const tg_i64 *)x.values)[ra] != ((const tg_i64 *)y.values)[rb]) return false;
             break;
         case 2:

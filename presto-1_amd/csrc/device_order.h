@@ -28,7 +28,7 @@ __device__ __forceinline__ unsigned long long double_order_bits(unsigned long lo
 __device__ __forceinline__ unsigned long long cell_order_bits(const TgColView &c, long long r)
 {
     switch (c.type) {
-    case TGPU_BIGINT: return (unsigned long long)((const long long *)c.values)[r] ^ 0x8000000000000000ULL;
+    case TGPU_BIGINT: case TGPU_TIMESTAMP: return (unsigned long long)((const long long *)c.values)[r] ^ 0x8000000000000000ULL;
     case TGPU_INTEGER:
     case TGPU_DATE: return (unsigned long long)(long long)((const int *)c.values)[r] ^ 0x8000000000000000ULL;
     case TGPU_DOUBLE: return double_order_bits(((const unsigned long long *)c.values)[r]);

@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(kBlock) gbh_finalize_kernel(const KeyCols *bat
             const bool isnull = s.nulls && s.nulls[r];
             ((uint8_t *)d.nulls)[gid] = isnull ? 1 : 0;
             switch (s.type) {
-            case TGPU_BIGINT:
+            case TGPU_BIGINT: case TGPU_TIMESTAMP:
             case TGPU_DOUBLE: ((int64_t *)d.values)[gid] = isnull ? 0 : ((const int64_t *)s.values)[r]; break;
             case TGPU_INTEGER:
             case TGPU_DATE: ((int32_t *)d.values)[gid] = isnull ? 0 : ((const int32_t *)s.values)[r]; break;
@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(kBlock) gbh_rehash_kernel(const int64_t *__res
 //             A null key cell is a violation, too (the route is for the ordered integer keys of scans; nulls take the table).
 //   scan    : exclusive scan of the tiles' head counts; its total is the number of new groups
 //   publish : gid = groups + (heads at or before the row) - 1; heads store key cells and raw hash at their id.  A no-op after a violation.
-// Eligible: fixed-width integer-like channels (BIGINT, INTEGER, DATE, BOOLEAN), no row mask, no external probe kernel.
+// Eligible: fixed-width integer-like channels (BIGINT, INTEGER, DATE, BOOLEAN, TIMESTAMP), no row mask, no external probe kernel.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kRunIters = 8;
 constexpr int kRunTile = kBlock * kRunIters;   // rows per tile (2^20 rows = 512 tiles: their scan is one launch)
@@ -213,7 +213,7 @@ __device__ __forceinline__ int run_compare(const KeyCols &a, long long ra, const
         if (x.nulls && x.nulls[ra]) return 2;
         if (res != 0) continue;   // decided by an earlier channel (the later ones are still looked at for nulls)
         switch (x.type) {
-        case TGPU_BIGINT: {
+        case TGPU_BIGINT: case TGPU_TIMESTAMP: {
             const int64_t u = ((const int64_t *)x.values)[ra], v = ((const int64_t *)y.values)[rb];
             res = u < v ? -1 : (u > v ? 1 : 0);
             break;
@@ -311,7 +311,7 @@ __device__ __forceinline__ void run_tile_states(const KeyCols &batch, const KeyC
             }
         }
         switch (x.type) {
-        case TGPU_BIGINT: run_compare_channel<int64_t, false>((const int64_t *)x.values, base, n, res); break;
+        case TGPU_BIGINT: case TGPU_TIMESTAMP: run_compare_channel<int64_t, false>((const int64_t *)x.values, base, n, res); break;
         case TGPU_INTEGER:
         case TGPU_DATE: run_compare_channel<int32_t, false>((const int32_t *)x.values, base, n, res); break;
         default: run_compare_channel<uint8_t, true>((const uint8_t *)x.values, base, n, res); break;   // TGPU_BOOLEAN (any non-zero byte is true)
@@ -415,7 +415,7 @@ __global__ void __launch_bounds__(kBlock) gbh_run_publish_kernel(const KeyCols *
             const ColView &s = batch.c[c];
             const ColView &d = store.c[c];
             switch (s.type) {
-            case TGPU_BIGINT: run_publish_channel<int64_t>((const int64_t *)s.values, (int64_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
+            case TGPU_BIGINT: case TGPU_TIMESTAMP: run_publish_channel<int64_t>((const int64_t *)s.values, (int64_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
             case TGPU_INTEGER:
             case TGPU_DATE: run_publish_channel<int32_t>((const int32_t *)s.values, (int32_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
             default: run_publish_channel<uint8_t>((const uint8_t *)s.values, (uint8_t *)d.values, (uint8_t *)d.nulls, base, n, gid, head, h); break;
@@ -486,11 +486,11 @@ GroupByHashGpu::GroupByHashGpu(Context *ctx, std::vector<int32_t> types, bool ha
     next_sub_ = std::min<int64_t>(sub_batch_, std::max<int64_t>(first ? atoll(first) : (1ll << 14), (int64_t)expected_size * 16));
     counters_ = ctx_->alloc_zero((size_t)GroupByHashGpu::kCounterSets * 8 * 8);
     // GroupByHash.createGroupByHash (M/operator/GroupByHash.java:45-59): one BIGINT key -> BigintGroupByHash, whose output hash is
-    // recomputed from the value (BigintGroupByHash.java:150-157) -- a precomputed hash channel is not even read.  INTEGER / DATE keys
+    // recomputed from the value (BigintGroupByHash.java:150-157) -- a precomputed hash channel is not even read.  INTEGER / DATE / TIMESTAMP keys
     // take the same table when no hash channel is given (their raw hash is then a function of the value, too).
     const char *off = getenv("TGPU_GBH_INTEGER_TABLE");
     if (allow_integer_table && types_.size() == 1 && !(off && off[0] == '0') &&
-        (types_[0] == TGPU_BIGINT || ((types_[0] == TGPU_INTEGER || types_[0] == TGPU_DATE) && !has_input_hash_)))
+        (types_[0] == TGPU_BIGINT || ((types_[0] == TGPU_INTEGER || types_[0] == TGPU_DATE || types_[0] == TGPU_TIMESTAMP) && !has_input_hash_)))
         integer_ = std::make_unique<BigintGroupTable>(ctx_, types_[0]);
     run_mode_ = !integer_;   // until the first page that does not take the run route
 }
@@ -796,7 +796,7 @@ void GroupByHashGpu::rebuild_table(int64_t min_capacity)
     capacity_ = want;
 }
 
-static bool run_key_type(int32_t t) { return t == TGPU_BIGINT || t == TGPU_INTEGER || t == TGPU_DATE || t == TGPU_BOOLEAN; }
+static bool run_key_type(int32_t t) { return t == TGPU_BIGINT || t == TGPU_INTEGER || t == TGPU_DATE || t == TGPU_BOOLEAN || t == TGPU_TIMESTAMP; }
 
 bool GroupByHashGpu::get_group_ids(const std::vector<const DeviceColumn *> &keys, const int64_t *hashes, int64_t n, int32_t *out_gids,
                                    const uint8_t *row_mask, bool inline_hash, const GbhProbeFn *probe, uint8_t *out_gids8, const GbhSpeculateFn *speculate,

@@ -298,7 +298,7 @@ namespace {
 const char *ctype(int32_t t)
 {
     switch (t) {
-    case TGPU_BIGINT: return "long long";
+    case TGPU_BIGINT: case TGPU_TIMESTAMP: return "long long";
     case TGPU_INTEGER: case TGPU_DATE: return "int";
     case TGPU_DOUBLE: return "double";
     case TGPU_BOOLEAN: return "bool";
@@ -628,7 +628,7 @@ struct Gen {
                 return r;
             }
             switch (nd.type) {
-            case TGPU_BIGINT: os << ind(d) << r.v << " = (long long)" << (long long)nd.ival << "LL;\n"; break;
+            case TGPU_BIGINT: case TGPU_TIMESTAMP: os << ind(d) << r.v << " = (long long)" << (long long)nd.ival << "LL;\n"; break;
             case TGPU_INTEGER: case TGPU_DATE: os << ind(d) << r.v << " = (int)" << (long long)nd.ival << "LL;\n"; break;
             case TGPU_BOOLEAN: os << ind(d) << r.v << " = " << (nd.ival ? "true" : "false") << ";\n"; break;
             case TGPU_DOUBLE: os << ind(d) << r.v << " = " << fmt_double(nd.dval) << ";\n"; break;
@@ -653,6 +653,7 @@ struct Gen {
         }
         case TGPU_EX_CALL:
             if (nd.op == TGPU_OP_LIKE) return gen_like(nd, idx, d);
+            if (is_timestamp_call(nd)) return gen_timestamp(nd, d);
             if ((nd.op >= TGPU_OP_LENGTH && nd.op <= TGPU_OP_STARTS_WITH) || (nd.op == TGPU_OP_CAST && nd.type == TGPU_VARCHAR)) return gen_string(nd, idx, d);
             if (nd.op >= TGPU_OP_YEAR && nd.op <= TGPU_OP_DATE_DIFF) return gen_date(nd, d);
             if (nd.op >= TGPU_OP_ABS && nd.op <= TGPU_OP_RADIANS) return gen_math(nd, d);
@@ -892,6 +893,120 @@ struct Gen {
         case TGPU_OP_DATE_ADD: checked("tg_date_add(" + u + ", " + a[0].v + ", " + a[1].v + ", &o_)"); break;
         case TGPU_OP_DATE_DIFF: os << ind(dd) << r.v << " = tg_date_diff(" << u << ", " << a[0].v << ", " << a[1].v << ");\n"; break;
         default: os << ind(dd) << r.v << " = tg_date_" << kFields[nd.op - TGPU_OP_YEAR] << "(" << a[0].v << ");\n";
+        }
+        for (int k = first; k < nd.n_args; k++) os << ind(--dd) << "}\n";
+        os << ind(d) << "}\n";
+        return r;
+    }
+
+    // ---- TIMESTAMP functions (M/operator/scalar/timestamp/); the arithmetic is csrc/device_timestamp.h over csrc/device_date.h -------------
+    bool timestamp_helpers = false;
+
+    void need_timestamp_helpers()
+    {
+        need_date_helpers();
+        if (!timestamp_helpers) consts << device_header("device_timestamp.h");   // (guarded by its own #ifndef, and behind the calendar's text)
+        timestamp_helpers = true;
+    }
+
+    // the calls that gen_timestamp generates: the five TIMESTAMP-only functions, a DATE function whose date argument is a TIMESTAMP, and a
+    // CAST that has a TIMESTAMP on either side
+    bool is_timestamp_call(const tgpu_expr_node &nd)
+    {
+        if (nd.op >= TGPU_OP_HOUR && nd.op <= TGPU_OP_TO_UNIXTIME) return true;
+        if (nd.op >= TGPU_OP_YEAR && nd.op <= TGPU_OP_DATE_DIFF) return nd.n_args >= 1 && nd.n_args <= 3 && node(nd.args[nd.n_args - 1]).type == TGPU_TIMESTAMP;
+        if (nd.op == TGPU_OP_CAST && nd.n_args == 1) return nd.type == TGPU_TIMESTAMP || node(nd.args[0]).type == TGPU_TIMESTAMP;
+        return false;
+    }
+
+    // getTimestampField (DateTimeFunctions.java:323-347): the unit after ASCII lower-casing -> TG_TS_UNIT_*
+    static int timestamp_unit(const std::string &text)
+    {
+        std::string u = text;
+        for (char &c : u)
+            if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+        static const char *kUnits[] = {"millisecond", "second", "minute", "hour", "day", "week", "month", "quarter", "year"};
+        for (int i = 0; i < 9; i++)
+            if (u == kUnits[i]) return i;
+        fail(TGPU_ERR_INVALID_ARGUMENT, "'" + u + "' is not a valid Timestamp field");
+    }
+
+    Val gen_timestamp(const tgpu_expr_node &nd, int d)
+    {
+        static const char *kDateNames[] = {"YEAR", "QUARTER", "MONTH", "WEEK", "DAY", "DAY_OF_WEEK", "DAY_OF_YEAR", "YEAR_OF_WEEK", "LAST_DAY_OF_MONTH", "DATE_TRUNC", "DATE_ADD", "DATE_DIFF"};
+        static const char *kDateFields[] = {"year", "quarter", "month", "week", "day", "day_of_week", "day_of_year", "year_of_week"};
+        static const char *kOwnNames[] = {"HOUR", "MINUTE", "SECOND", "MILLISECOND", "TO_UNIXTIME"};
+        static const char *kOwnFields[] = {"hour", "minute", "second", "millisecond"};
+        const bool cast = nd.op == TGPU_OP_CAST, own = nd.op >= TGPU_OP_HOUR;
+        const std::string name = cast ? "CAST" : (own ? kOwnNames[nd.op - TGPU_OP_HOUR] : kDateNames[nd.op - TGPU_OP_YEAR]) + std::string(" (TIMESTAMP)");
+        const bool has_unit = !cast && !own && nd.op >= TGPU_OP_DATE_TRUNC;
+        const int arity = nd.op == TGPU_OP_DATE_TRUNC ? 2 : has_unit ? 3 : 1;
+        if (nd.n_args != arity) bad(name + ": wrong number of arguments");
+        const int first = has_unit ? 1 : 0;
+        if (cast) {
+            const int32_t from = node(nd.args[0]).type;
+            if (!((nd.type == TGPU_TIMESTAMP && (from == TGPU_DATE || from == TGPU_TIMESTAMP)) || (nd.type == TGPU_DATE && from == TGPU_TIMESTAMP))) bad("unsupported cast");
+            if (nd.type == TGPU_TIMESTAMP && from == TGPU_TIMESTAMP && (nd.ival < 0 || nd.ival > 6)) bad("CAST: the target precision of a TIMESTAMP must be 0..6");
+        }
+        else {
+            const int32_t want_result = nd.op == TGPU_OP_TO_UNIXTIME ? TGPU_DOUBLE : nd.op == TGPU_OP_LAST_DAY_OF_MONTH ? TGPU_DATE
+                                        : (nd.op == TGPU_OP_DATE_TRUNC || nd.op == TGPU_OP_DATE_ADD) ? TGPU_TIMESTAMP : TGPU_BIGINT;
+            if (nd.type != want_result) bad(name + ": wrong result type");
+            for (int k = 0; k < nd.n_args; k++) {
+                const int32_t want = k < first ? TGPU_VARCHAR : (nd.op == TGPU_OP_DATE_ADD && k == 1) ? TGPU_BIGINT : TGPU_TIMESTAMP;
+                if (node(nd.args[k]).type != want) bad(name + ": wrong argument type");
+            }
+            if (nd.op == TGPU_OP_DATE_ADD && (nd.ival < 0 || nd.ival > 6)) bad(name + ": the precision of the TIMESTAMP argument must be 0..6");
+        }
+        int unit = -1;
+        bool null_unit = false;
+        if (has_unit) {
+            const tgpu_expr_node &un = node(nd.args[0]);
+            if (un.kind != TGPU_EX_CONST) fail(TGPU_ERR_NOT_SUPPORTED, name + ": the unit must be a VARCHAR constant");
+            null_unit = un.is_null != 0;
+            if (!null_unit) unit = timestamp_unit(const_text(un));
+        }
+        Val r = declare(nd.type, d);
+        if (null_unit) {   // the first argument is null: the others are not evaluated
+            os << ind(d) << r.n << " = true;\n";
+            return r;
+        }
+        const bool identity = cast && nd.type == TGPU_TIMESTAMP && node(nd.args[0]).type == TGPU_TIMESTAMP && nd.ival == 6;
+        if (!identity && nd.op != TGPU_OP_TO_UNIXTIME) need_timestamp_helpers();
+        os << ind(d) << "{\n";
+        std::vector<Val> a;
+        int dd = d + 1;
+        for (int k = first; k < nd.n_args; k++) {
+            a.push_back(gen(nd.args[k], dd));
+            os << ind(dd) << "if (" << a.back().n << ") " << r.n << " = true; else {\n";
+            dd++;
+        }
+        const std::string u = std::to_string(unit);
+        // a result that is no int64 count of microseconds (and date_add's amount outside int32) raises like the checked arithmetic does
+        auto checked = [&](const std::string &call) {
+            os << ind(dd) << "int o_ = 0; const long long t_ = " << call << ";\n";
+            os << ind(dd) << "if (o_) { " << raise("TG_E_RANGE") << " " << r.n << " = true; } else " << r.v << " = t_;\n";
+        };
+        switch (nd.op) {
+        case TGPU_OP_CAST:
+            if (identity) os << ind(dd) << r.v << " = " << a[0].v << ";\n";
+            else if (nd.type == TGPU_DATE) os << ind(dd) << r.v << " = tg_ts_to_date(" << a[0].v << ");\n";
+            else if (a[0].type == TGPU_DATE) os << ind(dd) << r.v << " = tg_ts_from_date(" << a[0].v << ");\n";
+            else os << ind(dd) << r.v << " = tg_ts_cast_precision(" << a[0].v << ", " << (int)nd.ival << ");\n";
+            break;
+        // one int64 -> double conversion and one IEEE division by the exact 10^6, as ToUnixTime.java's timestamp * 1.0 / 1000000 (no
+        // fast-math option is given to the compiler, so the division is not replaced by a multiplication with a reciprocal)
+        case TGPU_OP_TO_UNIXTIME: os << ind(dd) << r.v << " = (double)" << a[0].v << " / 1000000.0;\n"; break;
+        case TGPU_OP_HOUR: case TGPU_OP_MINUTE: case TGPU_OP_SECOND: case TGPU_OP_MILLISECOND:
+            os << ind(dd) << r.v << " = tg_ts_" << kOwnFields[nd.op - TGPU_OP_HOUR] << "(" << a[0].v << ");\n";
+            break;
+        case TGPU_OP_LAST_DAY_OF_MONTH:   // (cannot leave int32 here: |day| <= 106 751 992)
+            os << ind(dd) << "int o_ = 0; " << r.v << " = tg_date_last_day_of_month(tg_ts_date(" << a[0].v << "), &o_);\n";
+            break;
+        case TGPU_OP_DATE_TRUNC: checked("tg_ts_trunc(" + u + ", " + a[0].v + ", &o_)"); break;
+        case TGPU_OP_DATE_ADD: checked("tg_ts_add(" + u + ", " + a[0].v + ", " + a[1].v + ", " + std::to_string((int)nd.ival) + ", &o_)"); break;
+        case TGPU_OP_DATE_DIFF: os << ind(dd) << r.v << " = tg_ts_diff(" << u << ", " << a[0].v << ", " << a[1].v << ");\n"; break;
+        default: os << ind(dd) << r.v << " = tg_date_" << kDateFields[nd.op - TGPU_OP_YEAR] << "(tg_ts_date(" << a[0].v << "));\n";
         }
         for (int k = first; k < nd.n_args; k++) os << ind(--dd) << "}\n";
         os << ind(d) << "}\n";
@@ -1472,7 +1587,7 @@ struct Gen {
                 if (x == 0.0) x = 0.0;       // -0.0 == +0.0
                 memcpy(&w, &x, 8);
             }
-            else if (t == TGPU_BIGINT) w = (unsigned long long)it.ival;
+            else if (t == TGPU_BIGINT || t == TGPU_TIMESTAMP) w = (unsigned long long)it.ival;
             else if (t == TGPU_INTEGER || t == TGPU_DATE) w = (unsigned long long)(long long)(int32_t)it.ival;
             else if (t == TGPU_BOOLEAN) w = it.ival != 0;
             else bad("IN on an unsupported type");
@@ -1503,7 +1618,7 @@ struct Gen {
                     std::string c;
                     if (t == TGPU_DOUBLE) { double x; memcpy(&x, &w, 8); c = fmt_double(x); }
                     else if (t == TGPU_BOOLEAN) c = w ? "true" : "false";
-                    else c = std::string(t == TGPU_BIGINT ? "(long long)" : "(int)(long long)") + hex64(w);
+                    else c = std::string(t == TGPU_BIGINT || t == TGPU_TIMESTAMP ? "(long long)" : "(int)(long long)") + hex64(w);
                     found += (found.empty() ? "" : " || ") + (v.v + " == " + c);
                 }
         }
@@ -2889,7 +3004,7 @@ FusedProbeGpu::FusedProbeGpu(std::vector<int32_t> input_types, const tgpu_page_p
     for (int32_t ch : output_channels_) TG_CHECK_ARG(ch >= 0 && ch < (int)prog_.proj_roots.size(), "probe output channel out of range");
     prog_.resolve_projection_types();
     const int32_t kt = prog_.proj_types[(size_t)join_channel_];
-    supported_ = (kt == TGPU_BIGINT || kt == TGPU_INTEGER || kt == TGPU_DATE) && (int)output_channels_.size() <= kFpMaxProj;
+    supported_ = (kt == TGPU_BIGINT || kt == TGPU_INTEGER || kt == TGPU_DATE || kt == TGPU_TIMESTAMP) && (int)output_channels_.size() <= kFpMaxProj;
     for (int32_t ch : output_channels_) supported_ = supported_ && prog_.proj_types[(size_t)ch] != TGPU_VARCHAR;
     // the fused kernel evaluates the non-key projections lazily (for matching rows only) or not at all (channels the join drops):
     // one that can raise keeps the unfused composition (ExprProgram::can_raise)
@@ -3901,7 +4016,8 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
             const int32_t t = prog_.proj_types[(size_t)a.input_channel];
             // min / max over INTEGER / DATE: the projection's value is an int expression, `y = value` below widens it, and from here on the
             // aggregate is the BIGINT function (the output's type is the accumulators' business: they keep the caller's code)
-            const int32_t narrow = agg_narrow_type(a.function);
+            // (min / max over TIMESTAMP: a long long expression already, the BIGINT function from here on as well)
+            const int32_t narrow = agg_own_type(a.function);
             TG_CHECK_ARG(!narrow || t == narrow, "aggregate input type mismatch");
             a.function = agg_kernel_function(a.function);
             const bool want_bigint = !narrow && (a.function == TGPU_AGG_SUM_BIGINT || a.function == TGPU_AGG_AVG_BIGINT || a.function == TGPU_AGG_MIN_BIGINT || a.function == TGPU_AGG_MAX_BIGINT);
@@ -4172,7 +4288,7 @@ void FusedAggGpu::generate()
             const int32_t t = prog_.input_types[(size_t)key_inputs_[i]];
             src << "   {\n" << cell((int)i, "row", "x") << "    tg_i64 c = 0;\n    if (!xn) c = ";
             switch (t) {
-            case TGPU_BIGINT: src << "tg_hash_long(xv)"; break;
+            case TGPU_BIGINT: case TGPU_TIMESTAMP: src << "tg_hash_long(xv)"; break;
             case TGPU_INTEGER: case TGPU_DATE: src << "tg_hash_int(xv)"; break;
             case TGPU_DOUBLE: src << "tg_hash_double_bits(xv)"; break;
             case TGPU_BOOLEAN: src << "tg_hash_boolean(xv)"; break;
@@ -4212,7 +4328,7 @@ void FusedAggGpu::generate()
                "    for (int j = 0; j < 16; j++) r[j] = 0;\n    if (nl) continue;\n"
                "    if (c.type == 6) {\n      const int a = c.offsets[g], l = c.offsets[g + 1] - a;\n      *(int*)(r + 16) = l;\n      if (l > 16) r[21] = 1;\n"
                "      else for (int j = 0; j < l; j++) r[j] = ((const unsigned char*)c.values)[a + j];\n    }\n"
-               "    else if (c.type == 1 || c.type == 4) *(unsigned long long*)r = ((const unsigned long long*)c.values)[g];\n"
+               "    else if (c.type == 1 || c.type == 4 || c.type == 7) *(unsigned long long*)r = ((const unsigned long long*)c.values)[g];\n"
                "    else if (c.type == 2 || c.type == 3) *(long long*)r = (long long)((const int*)c.values)[g];\n"
                "    else *(unsigned long long*)r = ((const unsigned char*)c.values)[g] != 0 ? 1ULL : 0ULL;\n  }\n  __syncthreads();\n}\n";
         // pre-loaded key cells of one row (phase A: null flags, fixed-width values, varchar offset/length; phase B: the first
@@ -4275,7 +4391,7 @@ void FusedAggGpu::generate()
         }
         src << "  (void)A;\n  return 1;\n}\n";
         // The first FG_REG_GROUPS records additionally live in registers as SIGNATURES: bit fields [null mask | 32 bits per
-        // INTEGER / DATE key | 1 per BOOLEAN | 64 per BIGINT / DOUBLE key (DOUBLE canonicalised: one NaN, -0 -> +0) | 10 per VARCHAR
+        // INTEGER / DATE key | 1 per BOOLEAN | 64 per BIGINT / TIMESTAMP / DOUBLE key (DOUBLE canonicalised: one NaN, -0 -> +0) | 10 per VARCHAR
         // key = min(length, 2) << 8 | first byte] packed into as few words as they need (one 32-bit word for two varchar keys).
         // Equal signatures decide the row unless it has a varchar key longer than one byte ("open": the byte-wise LDS comparison
         // decides -- which is also why lengths above one need not be told apart here).  A record that cannot be summarised
@@ -4319,7 +4435,7 @@ void FusedAggGpu::generate()
                     fr.push_back({"w" + I, 10});
                     fg.push_back({"w" + I, 10});
                 }
-                else if (t == TGPU_BIGINT || t == TGPU_DOUBLE) {
+                else if (t == TGPU_BIGINT || t == TGPU_DOUBLE || t == TGPU_TIMESTAMP) {
                     row_sig << "  const unsigned long long q" << I << " = n" << I << " ? 0ULL : "
                             << (t == TGPU_DOUBLE ? "fg_canon_double((unsigned long long)K.v" + I + ")" : "(unsigned long long)K.v" + I) << ";\n";
                     rec_sig << "  const unsigned long long q" << I << " = n" << I << " ? 0ULL : "

@@ -36,7 +36,7 @@ __device__ __forceinline__ bool rows_equal_nonnull(const KeyCols &a, int64_t ra,
         if (c >= a.n) break;
         const ColView &x = a.c[c], &y = b.c[c];
         switch (x.type) {
-        case TGPU_BIGINT:
+        case TGPU_BIGINT: case TGPU_TIMESTAMP:
             if (((const int64_t *)x.values)[ra] != ((const int64_t *)y.values)[rb]) return false;
             break;
         case TGPU_INTEGER:
@@ -76,7 +76,7 @@ __device__ __forceinline__ bool row_has_null(const KeyCols &k, int64_t r)
 
 __device__ __forceinline__ long long int_key_at(const ColView &c, int64_t r)
 {
-    return c.type == TGPU_BIGINT ? ((const long long *)c.values)[r] : (long long)((const int *)c.values)[r];
+    return c.type == TGPU_BIGINT || c.type == TGPU_TIMESTAMP ? ((const long long *)c.values)[r] : (long long)((const int *)c.values)[r];
 }
 
 // PagesIndex.addPage / MergePages' appendPage as ONE launch: every buffer of the page (values and null vectors of all channels, VARCHAR
@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(kBlock) key_range_kernel(ColView key, int64_t 
     bool descent = false;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     const int lane = threadIdx.x & 63;
-    const bool wide = key.type == TGPU_BIGINT && key.nulls == nullptr && (reinterpret_cast<uintptr_t>(key.values) & 15) == 0;
+    const bool wide = (key.type == TGPU_BIGINT || key.type == TGPU_TIMESTAMP) && key.nulls == nullptr && (reinterpret_cast<uintptr_t>(key.values) & 15) == 0;
     const int64_t pairs = wide ? n / 2 : 0;
     if (wide) {
         const longlong2 *__restrict__ kv = (const longlong2 *)key.values;
@@ -815,7 +815,7 @@ void LookupSourceGpu::build()
     n_ = index_->position_count();
     key_cols_.clear();
     for (int32_t ch : key_channels_) key_cols_.push_back(index_->column(ch));
-    int_key_fast_ = key_cols_.size() == 1 && (key_cols_[0].type == TGPU_BIGINT || key_cols_[0].type == TGPU_INTEGER || key_cols_[0].type == TGPU_DATE);
+    int_key_fast_ = key_cols_.size() == 1 && (key_cols_[0].type == TGPU_BIGINT || key_cols_[0].type == TGPU_INTEGER || key_cols_[0].type == TGPU_DATE || key_cols_[0].type == TGPU_TIMESTAMP);
     // table size: the reference uses arraySize(n, 0.75) (PagesHash.java:63); the layout is unobservable, so the int-key fast
     // path runs at load <= 0.5 (HBM is plentiful and almost every probe then resolves in its first slot)
     const double max_load = int_key_fast_ ? 0.5 : 0.75;
@@ -1061,7 +1061,7 @@ void LookupSourceGpu::probe(const std::vector<const DeviceColumn *> &probe_keys,
     TG_CHECK_ARG(probe_keys.size() == key_channels_.size(), "probe key channel count differs from the build side's");
     for (size_t i = 0; i < probe_keys.size(); i++) {
         const int32_t bt = index_->types()[key_channels_[i]];
-        const bool int_like = (bt == TGPU_BIGINT || bt == TGPU_INTEGER || bt == TGPU_DATE);
+        const bool int_like = (bt == TGPU_BIGINT || bt == TGPU_INTEGER || bt == TGPU_DATE || bt == TGPU_TIMESTAMP);
         TG_CHECK_ARG(probe_keys[i]->type == bt || (int_key_fast_ && int_like && probe_keys[i]->type == bt), "probe key type differs from the build key type");
     }
     out_count = 0;

@@ -923,9 +923,9 @@ static void validate(Context *, const StreamingAggregationConfig &cfg)
         TG_CHECK_ARG(agg_function_known(a.function), "unknown aggregate function");
         if (agg_is_varchar_extreme(a.function)) fail(TGPU_ERR_NOT_SUPPORTED, "min / max over VARCHAR is not supported by the streaming aggregation");
         TG_CHECK_ARG(a.function == TGPU_AGG_COUNT_ALL || (a.input_channel >= 0 && a.input_channel < (int)cfg.types.size()), "aggregate input channel out of range");
-        // (the source types are known here: min / max over INTEGER / DATE read a channel of that type -- FINAL reads the BIGINT count channel)
-        if (agg_narrow_type(a.function))
-            TG_CHECK_ARG(cfg.types[(size_t)a.input_channel] == (cfg.step == TGPU_STEP_FINAL ? TGPU_BIGINT : agg_narrow_type(a.function)), "aggregate input type mismatch");
+        // (the source types are known here: min / max over INTEGER / DATE / TIMESTAMP read a channel of that type -- FINAL reads the BIGINT count channel)
+        if (agg_own_type(a.function))
+            TG_CHECK_ARG(cfg.types[(size_t)a.input_channel] == (cfg.step == TGPU_STEP_FINAL ? TGPU_BIGINT : agg_own_type(a.function)), "aggregate input type mismatch");
         TG_CHECK_ARG(a.mask_channel < (int)cfg.types.size(), "aggregate mask channel out of range");
         if (a.mask_channel >= 0) TG_CHECK_ARG(cfg.types[(size_t)a.mask_channel] == TGPU_BOOLEAN, "aggregate mask channel is not BOOLEAN");
     }
@@ -2261,7 +2261,7 @@ __global__ void __launch_bounds__(256) df_minmax_kernel(ColView col, int64_t n, 
     long long lo = 0x7fffffffffffffffLL, hi = -0x7fffffffffffffffLL - 1;
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
         if (col.nulls && col.nulls[r]) continue;
-        const long long v = col.type == TGPU_BIGINT ? ((const long long *)col.values)[r]
+        const long long v = col.type == TGPU_BIGINT || col.type == TGPU_TIMESTAMP ? ((const long long *)col.values)[r]
                             : (col.type == TGPU_BOOLEAN ? (long long)(((const unsigned char *)col.values)[r] != 0) : (long long)((const int *)col.values)[r]);
         lo = v < lo ? v : lo;
         hi = v > hi ? v : hi;

@@ -25,7 +25,7 @@ constexpr unsigned long long kEmptyKey = 0x8000000000000000ull;   // INT64_MIN: 
 
 __device__ __forceinline__ long long key_at(const ColView &c, int64_t r)
 {
-    return c.type == TGPU_BIGINT ? ((const long long *)c.values)[r] : (long long)((const int *)c.values)[r];
+    return c.type == TGPU_BIGINT || c.type == TGPU_TIMESTAMP ? ((const long long *)c.values)[r] : (long long)((const int *)c.values)[r];
 }
 
 // HashSemiJoinOperator.java:191-215 for one row
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(kBlock) semi_probe_generic(const int32_t *__re
 SemiSetGpu::SemiSetGpu(Context *ctx, int32_t type) : ctx_(ctx), type_(type)
 {
     TG_CHECK_ARG(valid_type(type), "unknown type");
-    integer_ = type == TGPU_BIGINT || type == TGPU_INTEGER || type == TGPU_DATE;
+    integer_ = type == TGPU_BIGINT || type == TGPU_INTEGER || type == TGPU_DATE || type == TGPU_TIMESTAMP;
     if (integer_) keys_ = std::make_unique<PagesIndexGpu>(ctx, std::vector<int32_t>{type});
     else groups_ = std::make_unique<GroupByHashGpu>(ctx, std::vector<int32_t>{type}, false, 1024);
     null_seen_ = ctx->alloc_zero(8);

@@ -273,7 +273,7 @@ DeviceColumn read_block(Context *ctx, Reader &r, int32_t type, int depth)
 const char *encoding_name(int32_t type)
 {
     switch (type) {
-    case TGPU_BIGINT:
+    case TGPU_BIGINT: case TGPU_TIMESTAMP:
     case TGPU_DOUBLE: return "LONG_ARRAY";
     case TGPU_INTEGER:
     case TGPU_DATE: return "INT_ARRAY";

@@ -95,7 +95,7 @@ __device__ __forceinline__ void sagg_tile_starts(const KeyCols &batch, int64_t b
     for (int c = 0; c < batch.n; c++) {
         const ColView &x = batch.c[c];
         switch (x.type) {
-        case TGPU_BIGINT: sagg_fixed_channel<int64_t, 0>((const int64_t *)x.values, x.nulls, base, n, diff); break;
+        case TGPU_BIGINT: case TGPU_TIMESTAMP: sagg_fixed_channel<int64_t, 0>((const int64_t *)x.values, x.nulls, base, n, diff); break;
         case TGPU_INTEGER:
         case TGPU_DATE: sagg_fixed_channel<int32_t, 0>((const int32_t *)x.values, x.nulls, base, n, diff); break;
         case TGPU_DOUBLE: sagg_fixed_channel<double, 1>((const double *)x.values, x.nulls, base, n, diff); break;

@@ -7,7 +7,7 @@ translator rewrites it to `b < a` (SqlToRowExpressionTranslator.java:317-320), w
 import ctypes as C
 
 from . import _lib
-from .spi import BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, VARCHAR
+from .spi import BIGINT, BOOLEAN, DATE, DOUBLE, INTEGER, TIMESTAMP, VARCHAR
 
 EX_INPUT, EX_CONST, EX_CALL, EX_SPECIAL = 0, 1, 2, 3
 OPS = {"ADD": 1, "SUBTRACT": 2, "MULTIPLY": 3, "DIVIDE": 4, "MODULUS": 5, "NEGATE": 6, "EQUAL": 7, "NOT_EQUAL": 8,
@@ -16,7 +16,8 @@ OPS = {"ADD": 1, "SUBTRACT": 2, "MULTIPLY": 3, "DIVIDE": 4, "MODULUS": 5, "NEGAT
        "YEAR": 21, "QUARTER": 22, "MONTH": 23, "WEEK": 24, "DAY": 25, "DAY_OF_WEEK": 26, "DAY_OF_YEAR": 27, "YEAR_OF_WEEK": 28,
        "LAST_DAY_OF_MONTH": 29, "DATE_TRUNC": 30, "DATE_ADD": 31, "DATE_DIFF": 32,
        "ABS": 33, "SIGN": 34, "FLOOR": 35, "CEILING": 36, "TRUNCATE": 37, "ROUND": 38, "SQRT": 39, "CBRT": 40, "EXP": 41, "LN": 42, "LOG2": 43,
-       "LOG10": 44, "LOG": 45, "POWER": 46, "IS_NAN": 47, "IS_FINITE": 48, "IS_INFINITE": 49, "DEGREES": 50, "RADIANS": 51}
+       "LOG10": 44, "LOG": 45, "POWER": 46, "IS_NAN": 47, "IS_FINITE": 48, "IS_INFINITE": 49, "DEGREES": 50, "RADIANS": 51,
+       "HOUR": 52, "MINUTE": 53, "SECOND": 54, "MILLISECOND": 55, "TO_UNIXTIME": 56}
 FORMS = {"AND": 1, "OR": 2, "IF": 3, "IS_NULL": 4, "COALESCE": 5, "BETWEEN": 6, "IN": 7}
 _CMP = {"EQUAL", "NOT_EQUAL", "LESS_THAN", "LESS_THAN_OR_EQUAL", "GREATER_THAN", "GREATER_THAN_OR_EQUAL"}
 
@@ -50,9 +51,10 @@ class ConstantExpression(RowExpression):
 
 
 class CallExpression(RowExpression):
-    def __init__(self, name, type_id, arguments):
+    def __init__(self, name, type_id, arguments, ival=0):
         assert name in OPS, name
         self.name, self.type, self.arguments = name, type_id, list(arguments)
+        self.ival = ival   # the node's ival: the precision of a TIMESTAMP date_add / cast, unused otherwise
 
 
 class SpecialForm(RowExpression):
@@ -85,7 +87,11 @@ def is_null(a): return SpecialForm("IS_NULL", BOOLEAN, [a])
 def if_(c, t, f): return SpecialForm("IF", t.type, [c, t, f])
 def coalesce(*args): return SpecialForm("COALESCE", args[0].type, [_wrap(a, args[0].type) for a in args])
 def between(v, lo, hi): return SpecialForm("BETWEEN", BOOLEAN, [v, _wrap(lo, v.type), _wrap(hi, v.type)])
-def cast(a, type_id): return call("CAST", type_id, a)
+
+
+def cast(a, type_id, precision=6):
+    """CAST(a AS type); precision: the target's p of a CAST(timestamp AS timestamp(p)), 0..6 (the value is rounded to it)"""
+    return CallExpression("CAST", type_id, [a], ival=precision if type_id == TIMESTAMP and a.type == TIMESTAMP else 0)
 
 
 def like(value, pattern, escape=None):
@@ -133,31 +139,51 @@ def starts_with(x, prefix):
     return call("STARTS_WITH", BOOLEAN, _wrap(x, VARCHAR), _wrap(prefix, VARCHAR))
 
 
-# DATE functions: extraction gives BIGINT; a Python int stands for a DATE constant (days since 1970-01-01), None for the null literal
-def year(d): return call("YEAR", BIGINT, _wrap(d, DATE))
-def quarter(d): return call("QUARTER", BIGINT, _wrap(d, DATE))
-def month(d): return call("MONTH", BIGINT, _wrap(d, DATE))
-def week(d): return call("WEEK", BIGINT, _wrap(d, DATE))
-def day(d): return call("DAY", BIGINT, _wrap(d, DATE))
-def day_of_week(d): return call("DAY_OF_WEEK", BIGINT, _wrap(d, DATE))
-def day_of_year(d): return call("DAY_OF_YEAR", BIGINT, _wrap(d, DATE))
-def year_of_week(d): return call("YEAR_OF_WEEK", BIGINT, _wrap(d, DATE))
-def last_day_of_month(d): return call("LAST_DAY_OF_MONTH", DATE, _wrap(d, DATE))
+# DATE functions: extraction gives BIGINT; a Python int stands for a DATE constant (days since 1970-01-01), None for the null literal.
+# Every one of them takes a TIMESTAMP expression (field(ch, TIMESTAMP), constant(us, TIMESTAMP)) in the DATE argument's place as well.
+def _date_like(d):
+    """the DATE / TIMESTAMP argument, and its type"""
+    d = _wrap(d, DATE)
+    return d, (TIMESTAMP if d.type == TIMESTAMP else DATE)
+
+
+def year(d): return call("YEAR", BIGINT, _date_like(d)[0])
+def quarter(d): return call("QUARTER", BIGINT, _date_like(d)[0])
+def month(d): return call("MONTH", BIGINT, _date_like(d)[0])
+def week(d): return call("WEEK", BIGINT, _date_like(d)[0])
+def day(d): return call("DAY", BIGINT, _date_like(d)[0])
+def day_of_week(d): return call("DAY_OF_WEEK", BIGINT, _date_like(d)[0])
+def day_of_year(d): return call("DAY_OF_YEAR", BIGINT, _date_like(d)[0])
+def year_of_week(d): return call("YEAR_OF_WEEK", BIGINT, _date_like(d)[0])
+def last_day_of_month(d): return call("LAST_DAY_OF_MONTH", DATE, _date_like(d)[0])
 
 
 def date_trunc(unit, d):
-    """date_trunc(unit, d); unit: 'day', 'week', 'month', 'quarter' or 'year' in any case (a str, None = the null literal), a constant"""
-    return call("DATE_TRUNC", DATE, _wrap(unit, VARCHAR), _wrap(d, DATE))
+    """date_trunc(unit, d); unit: 'day', 'week', 'month', 'quarter' or 'year' -- for a TIMESTAMP also 'millisecond', 'second', 'minute' and
+    'hour' -- in any case (a str, None = the null literal), a constant.  The result has d's type"""
+    d, t = _date_like(d)
+    return call("DATE_TRUNC", t, _wrap(unit, VARCHAR), d)
 
 
-def date_add(unit, value, d):
-    """date_add(unit, value, d): value a BIGINT expression or a Python int; months clamp the day of the month to the target month"""
-    return call("DATE_ADD", DATE, _wrap(unit, VARCHAR), _wrap(value, BIGINT), _wrap(d, DATE))
+def date_add(unit, value, d, precision=6):
+    """date_add(unit, value, d): value a BIGINT expression or a Python int; months clamp the day of the month to the target month.
+    precision: the p of a timestamp(p) argument, 0..6 (for p <= 3 the reference rounds the millisecond result to it)"""
+    d, t = _date_like(d)
+    return CallExpression("DATE_ADD", t, [_wrap(unit, VARCHAR), _wrap(value, BIGINT), d], ival=precision if t == TIMESTAMP else 0)
 
 
 def date_diff(unit, d1, d2):
-    """date_diff(unit, d1, d2): the whole units from d1 to d2, negative when d2 < d1"""
-    return call("DATE_DIFF", BIGINT, _wrap(unit, VARCHAR), _wrap(d1, DATE), _wrap(d2, DATE))
+    """date_diff(unit, d1, d2): the whole units from d1 to d2, negative when d2 < d1; two DATEs or two TIMESTAMPs"""
+    d1, t = _date_like(d1)
+    return call("DATE_DIFF", BIGINT, _wrap(unit, VARCHAR), d1, _wrap(d2, t))
+
+
+# TIMESTAMP functions: int64 microseconds since 1970-01-01 00:00:00 UTC; a Python int stands for a TIMESTAMP constant
+def hour(t): return call("HOUR", BIGINT, _wrap(t, TIMESTAMP))
+def minute(t): return call("MINUTE", BIGINT, _wrap(t, TIMESTAMP))
+def second(t): return call("SECOND", BIGINT, _wrap(t, TIMESTAMP))
+def millisecond(t): return call("MILLISECOND", BIGINT, _wrap(t, TIMESTAMP))
+def to_unixtime(t): return call("TO_UNIXTIME", DOUBLE, _wrap(t, TIMESTAMP))
 
 
 # Math functions.  abs_ / sign / floor / ceiling / round_ keep the argument's type (BIGINT, INTEGER or DOUBLE); a Python float stands for a DOUBLE
@@ -240,7 +266,7 @@ class FlatProgram:
                     nd["ival"] = int(e.value)
         elif isinstance(e, CallExpression):
             args = [self._add(a) for a in e.arguments]
-            nd = dict(kind=EX_CALL, type=e.type, op=OPS[e.name], args=args)
+            nd = dict(kind=EX_CALL, type=e.type, op=OPS[e.name], args=args, ival=e.ival)
         elif isinstance(e, SpecialForm):
             args = [self._add(a) for a in e.arguments]
             assert len(args) <= 3, "special forms take at most 3 arguments here"

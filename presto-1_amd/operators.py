@@ -17,6 +17,7 @@ from .spi import OutputPage, Page
 
 COUNT_ALL, COUNT_COLUMN, SUM_BIGINT, SUM_DOUBLE, AVG_BIGINT, AVG_DOUBLE, MIN_BIGINT, MAX_BIGINT, MIN_DOUBLE, MAX_DOUBLE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 MIN_INTEGER, MAX_INTEGER, MIN_DATE, MAX_DATE = 11, 12, 13, 14   # min / max over int32-stored types: output of the input's type, BIGINT intermediate
+MIN_TIMESTAMP, MAX_TIMESTAMP = 17, 18                           # min / max over int64 microseconds: output TIMESTAMP, BIGINT intermediate
 MIN_VARCHAR, MAX_VARCHAR = 15, 16                               # plain hash aggregation only; PARTIAL: count BIGINT, value VARCHAR
 SINGLE, PARTIAL, FINAL = 0, 1, 2
 # S/connector/SortOrder.java:18-21

@@ -12,8 +12,9 @@ import numpy as np
 from . import _lib
 
 BIGINT, INTEGER, DATE, DOUBLE, BOOLEAN, VARCHAR = 1, 2, 3, 4, 5, 6
-TYPE_NAMES = {BIGINT: "bigint", INTEGER: "integer", DATE: "date", DOUBLE: "double", BOOLEAN: "boolean", VARCHAR: "varchar"}
-NP_DTYPE = {BIGINT: np.int64, INTEGER: np.int32, DATE: np.int32, DOUBLE: np.float64, BOOLEAN: np.uint8}
+TIMESTAMP = 7   # timestamp(p), p <= 6: int64 microseconds since 1970-01-01 00:00:00 UTC (LongArrayBlock)
+TYPE_NAMES = {BIGINT: "bigint", INTEGER: "integer", DATE: "date", DOUBLE: "double", BOOLEAN: "boolean", VARCHAR: "varchar", TIMESTAMP: "timestamp"}
+NP_DTYPE = {BIGINT: np.int64, INTEGER: np.int32, DATE: np.int32, DOUBLE: np.float64, BOOLEAN: np.uint8, TIMESTAMP: np.int64}
 FLAT, DICTIONARY, RLE = 0, 1, 2
 HOST, DEVICE = 0, 1
 
