@@ -1684,30 +1684,6 @@ struct Gen {
 
 const char *kPrelude = R"SRC(
 // generated by libtgpu (jit.cpp): fused filter + project kernels for gfx950
-#define TG_E_RANGE 2
-#define TG_E_DIV0 7
-#define TG_E_CAST 9
-#define TG_E_CONCAT 10
-#define TG_E_ABS_BIGINT 11
-#define TG_E_ABS_INTEGER 12
-#define TG_E_ROUND 13
-#define TG_MAXC 24
-#define TG_MAXP 16
-struct FpArgs {
-  const void* col_values[TG_MAXC];
-  const unsigned char* col_nulls[TG_MAXC];
-  const int* col_offsets[TG_MAXC];
-  void* out_values[TG_MAXP];
-  unsigned char* out_nulls[TG_MAXP];
-  int* positions;
-  const int* tile_offsets;
-  int* tile_counts;
-  unsigned long long* error;
-  long long n;
-  unsigned long long* sel_mask;   // filter verdicts of pass 1, one 64-bit ballot per (tile, stripe, wave)
-  long long* operand;             // null, or where the lane that posts operand_key stores the operand of its failure
-  unsigned long long operand_key;
-};
 // first failing row wins (the reference throws at the first failing position)
 __device__ inline void tg_error(unsigned long long* e, long long row, int code) {
   atomicMin(e, ((unsigned long long)row << 8) | (unsigned long long)code);
@@ -1739,6 +1715,9 @@ __device__ inline double tg_round_half_away(double x) {
 #define TG_TILE 1024
 #define TG_STRIPES 4
 )SRC";
+
+// what every generated source starts with: the FpArgs block and the helpers above
+std::string prelude() { return device_header("device_fp_args.h") + kPrelude; }
 
 // The column pointers a generated function of the fused kernels declares for the channels its expressions read from memory.  `no_nulls` names
 // the macro of the specialisation for pages without null vectors (FJ_NO_NULLS / FA_NO_NULLS).
@@ -2011,7 +1990,7 @@ void PageProcessorGpu::generate()
     }
 
     std::ostringstream src;
-    src << kPrelude << g.consts.str();
+    src << prelude() << g.consts.str();
     const bool has_filter = prog_.filter_root >= 0;
     if (has_filter) {
         src << "__device__ inline bool tg_filter(const FpArgs& A, long long row) {\n" << cols.str() << filter_body.str() << "}\n";
@@ -2087,7 +2066,7 @@ extern "C" __global__ void __launch_bounds__(256) fp_emit(FpArgs A) {
     if (varchar_count_ > 0) {
         // pass 3: one lane per OUTPUT row.  Lanes past the last row evaluate the last row too (and write nothing), so that every lane of a
         // wave reaches the cooperative copies of tg_vw_piece.
-        src << "struct FvArgs { FpArgs fp; const int* offsets[" << kFpMaxVarchar << "]; unsigned char* pool[" << kFpMaxVarchar << "]; long long n_out; };\n";
+        src << device_header("device_fv_args.h");
         src << "__device__ inline void tg_vwrite(const FvArgs& V, long long row, long long o, bool act) {\n  const FpArgs& A = V.fp;\n" << cols.str() << vwrite_body.str() << "  (void)row;\n}\n";
         src << R"SRC(
 extern "C" __global__ void __launch_bounds__(256) fp_vwrite(FvArgs V) {
@@ -2347,38 +2326,8 @@ static int fj_stripes()
 }
 
 const char *kFjKernels = R"SRC(
-struct FjArgs {
-  FpArgs fp;
-  const TgSlot16* slots;
-  unsigned long long mask;
-  TgPrefilter pf;
-  int* tile_cnt;            // pairs produced by each CHUNK of tiles (see fj_probe)
-  int* tile_src;            // where the chunk's pairs start inside its block's private region
-  const int* tile_dst;      // pass 2: exclusive scan of tile_cnt = final output offset of the chunk
-  int* pair_probe;          // block-private regions, capacity = rows the block owns
-  int* pair_build;
-  int* out_build;           // pass 2: build positions in final order
-  unsigned long long* counters;
-  long long tiles;
-  long long grid1;          // grid size of pass 1 (defines the region layout)
-  int outer;                // bit 0: PROBE_OUTER / FULL_OUTER rows; bit 1: nobody reads the build positions (no build output channels,
-                            // no outer tracking): the DIRECT layout then skips the rank and position lookups
-  int chunk_shift;          // a workgroup takes 2^chunk_shift consecutive tiles at a time
-  struct { const void* values; const unsigned char* nulls; void* out_values; unsigned char* out_nulls; int width; int pad; } bcol[4];   // build-side
-  int n_bcol;               // output channels pass 2 gathers itself (fixed width)
-  int pad2;
-  void* carry[4];           // FJ_CARRY: block-private regions of the probe-side output VALUES (pass 1 evaluates them from its row
-  unsigned char* carry_nulls; // registers for every emitted pair; pass 2 moves them instead of re-reading the input columns sparsely)
-  unsigned long long* host_out; // epilogue (small pages): host-visible result words, written by the LAST workgroup of pass 1 (null: none)
-  unsigned int* done;           //                         workgroups that have finished (rests at 0)
-  const FpArgs* pages;          // FJ_EPILOGUE == 2 (a launch over a LIST of pages): one FpArgs per page, in device memory
-  const int* page_tile0;        //   first tile of each page in the launch's tile sequence, [n_pages] = all tiles
-  int n_pages;
-  int pad3;
-};
 #define FJ_STRIPES @FJ_STRIPES@
 #define FJ_TILE (FJ_STRIPES * 256)
-#define FJ_COUNT_SLOTS 64
 #ifndef FJ_EPILOGUE
 #define FJ_EPILOGUE 0   // the variant for pages (few, one-tile chunks): pass 1 ends with the scan and hands its totals to the host itself
 #endif
@@ -2987,7 +2936,6 @@ extern "C" __global__ void __launch_bounds__(256) fj_emit(FjArgs J) { fj_emit_bo
 // One launch for two pages of a page-at-a-time probe: pass 2 of an EARLIER page (its totals have reached the host) next to pass 1 of the NEW
 // page.  Both are chains of dependent memory round trips that one page cannot fill the chip with (17.7 and 9.6 us for a 2^20-row page);
 // side by side in one grid they overlap.  The probe's workgroups come first (they run longer).
-struct FjPairArgs { FjArgs probe; FjArgs emit; unsigned int probe_blocks; unsigned int pad; };
 extern "C" __global__ void __launch_bounds__(256) fj_pair(FjPairArgs P) {
   if (blockIdx.x < P.probe_blocks) fj_probe_body(P.probe, blockIdx.x, P.probe_blocks);
   else fj_emit_body(P.emit, blockIdx.x - P.probe_blocks, gridDim.x - P.probe_blocks);
@@ -3110,7 +3058,7 @@ void FusedProbeGpu::generate()
         carry_bodies.push_back(f.str());
         carry_bytes += type_width(prog_.proj_types[(size_t)ch]);
     }
-    carry_supported_ = !output_channels_.empty() && output_channels_.size() <= 4 && carry_bytes <= 24 && gc.used_cols.empty();   // (used_cols: columns read from memory = VARCHAR inputs)
+    carry_supported_ = !output_channels_.empty() && output_channels_.size() <= (size_t)kFjMaxCarry && carry_bytes <= 24 && gc.used_cols.empty();   // (used_cols: columns read from memory = VARCHAR inputs)
     std::vector<int> carry_only_cols;   // columns only the carried outputs read
     for (int ch : gc.reg_cols)
         if (!gr.reg_cols.count(ch)) carry_only_cols.push_back(ch);
@@ -3123,7 +3071,7 @@ void FusedProbeGpu::generate()
     {
         const char *rule_env = getenv("TGPU_FJ_CARRY_RULE");   // kernel studies: 0 = every free channel, 1 = not the join key's channel
         const int free_rule = rule_env ? atoi(rule_env) : kFjFreeRule;
-        for (size_t i = 0; i < output_channels_.size() && i < 4; i++) {
+        for (size_t i = 0; i < output_channels_.size() && i < (size_t)kFjMaxCarry; i++) {
             const int ch = output_channels_[i];
             if (ch == join_channel_ && (key_can_raise_ || free_rule == 1)) continue;
             Gen ga(prog_);
@@ -3140,7 +3088,7 @@ void FusedProbeGpu::generate()
 
     std::ostringstream src;
     src << "#ifndef FJ_CARRY\n#define FJ_CARRY 0\n#endif\n";
-    src << kPrelude << device_header("device_hash.h") << device_header("device_join.h") << gr.consts.str() << gm.consts.str() << gc.consts.str();
+    src << prelude() << device_header("device_hash.h") << device_header("device_join.h") << device_header("device_fj_args.h") << gr.consts.str() << gm.consts.str() << gc.consts.str();
     // the pre-loaded row: one field pair per fixed-width column the filter / key (and, in the carry variant, the outputs) read
     src << row_decl(prog_.input_types, "TgRow", "row", gr.reg_cols, false, "FJ_NO_NULLS", &carry_only_cols);
     // load instructions tg_load_row issues per row (FJ_DEPTH 2 sizes its wait with it): a value per column, a null byte where the page may have
@@ -3150,7 +3098,7 @@ void FusedProbeGpu::generate()
     for (auto &b : reg_bodies) src << splice(b, rc);
     for (auto &b : mem_bodies) src << splice(b, mc);
     // the carried outputs of one row (register form), their evaluation, and the two stores
-    src << "struct FjArgs;\nstruct TgOut {\n";
+    src << "struct TgOut {\n";
     for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  " << ctype(prog_.proj_types[(size_t)output_channels_[i]]) << " v" << i << ";\n#endif\n";
     src << "#if !FJ_NO_NULLS\n  unsigned char nulls;\n#endif\n};\n__device__ inline void tg_zero_out(TgOut& O) {\n";
     for (size_t i = 0; i < output_channels_.size(); i++) src << all_or_free(i) << "  O.v" << i << " = 0;\n#endif\n";
@@ -3167,7 +3115,7 @@ void FusedProbeGpu::generate()
         src << "#if !FJ_NO_NULLS\n  O.nulls = nl;\n#else\n  (void)nl;\n#endif\n}\n";
     }
     src << "#endif\n";
-    std::ostringstream carry_funcs;   // need FjArgs: spliced in behind its definition (@CARRY_FUNCS@ in kFjKernels)
+    std::ostringstream carry_funcs;   // spliced in at @CARRY_FUNCS@ in kFjKernels
     carry_funcs << "#if FJ_CARRY\n__device__ inline void tg_carry_store(const FjArgs& J, long long at, const TgOut& O) {\n";
     for (size_t i = 0; i < output_channels_.size(); i++) {
         const int32_t t = prog_.proj_types[(size_t)output_channels_[i]];
@@ -3374,15 +3322,9 @@ std::shared_ptr<FusedProbeGpu::Pending> FusedProbeGpu::begin(Context *ctx, const
     pend->carry = carry;
     FjArgs &J = pend->J;
     fill_fp_cols(J.fp, in);   // (several pages: the first one's; the kernel reads the descriptors below)
-    J.slots = tv.slots;
+    J.slots = static_cast<const TgSlot16 *>(tv.slots);
     J.mask = tv.mask;
-    J.bitmap = tv.bitmap;
-    J.key_min = tv.key_min;
-    J.key_max = tv.key_max;
-    J.bloom = tv.bloom;
-    J.bloom_word_mask = tv.bloom_word_mask;
-    J.direct = tv.direct;
-    J.rank_base = tv.rank_base;
+    J.pf = TgPrefilter{tv.bitmap, tv.key_min, tv.key_max, tv.bloom, tv.bloom_word_mask, tv.direct, tv.rank_base};
     J.outer = (outer ? 1 : 0) | (need_build_positions ? 0 : 2);
     J.tiles = ceil_div(n, tile_rows);
     TG_CHECK_ARG(n <= 0x7fffffffLL && J.tiles <= 0x7fffffffLL, "page too large");
@@ -3507,10 +3449,7 @@ void FusedProbeGpu::launch_pair(Context *ctx, const std::shared_ptr<Pending> &em
 {
     static const char *pair_names[4] = {"fj_pair_plain", "fj_pair_bitmap", "fj_pair_bloom", "fj_pair_direct"};
     TG_CHECK_STATE(can_pair(emit_side, probe_side), "these two pages cannot share a launch");
-    struct FjPairArgs {
-        FjArgs probe, emit;
-        unsigned int probe_blocks, pad;
-    } P{probe_side->J, emit_side->J, (unsigned int)probe_side->grid1, 0u};
+    FjPairArgs P{probe_side->J, emit_side->J, (unsigned int)probe_side->grid1, 0u};
     {
         ProfileScope ps(ctx, "fused_probe_pair");
         launch_args(probe_side->module->fn(pair_names[probe_side->pf_kind]), (int)(probe_side->grid1 + emit_side->emit_blocks), P, ctx->stream());
@@ -3609,7 +3548,7 @@ void FusedProbeGpu::finish(Context *ctx, const std::shared_ptr<Pending> &pend, c
                 c.nulls_buf = ctx->alloc((size_t)count);
                 c.nulls = c.nulls_buf->as<uint8_t>();
             }
-            FjArgs::BuildCol &b = J.bcol[J.n_bcol++];
+            FjBuildCol &b = J.bcol[J.n_bcol++];
             b.values = src.values;
             b.nulls = src.nulls;
             b.out_values = c.values_buf->ptr();
@@ -3640,28 +3579,6 @@ static int fa_stripes()
 }
 
 const char *kFaKernels = R"SRC(
-struct FaArgs {
-  FpArgs fp;
-  const int* gids;
-  unsigned char* mask_out;
-  TgAggState st[TG_MAX_AGGS];
-  TgLowCardPlan plan;
-  long long tiles;
-  int lowcard;
-  int pad;
-  const unsigned int* ord_keys;   // ORDERED mode: (group id + 1) of the page's rows in (group, row) order, 0 = filtered row
-  const int* ord_rows;            //               and their row numbers
-  const unsigned char* gids8;     // compact group ids (id + 1, 0 = filtered row) instead of gids
-  TgFoldScratch fold;             // low-cardinality launches: the workgroups' folded partials
-  const unsigned long long* gate; // speculative launch behind a group-by probe: its counters; anything but clean = do nothing
-  const int* ord_stretch;         // ORDERED mode, chained kernel over all groups: {first, end} of every group's stretch of ord_keys; or
-  long long* ord_list;            // the groups the lane-per-group kernel handed over after ord_handoff rows: {group, next index} pairs,
-  unsigned int* ord_list_count;   // their number (starts at 0); ord_handoff 0 = lanes walk their groups to the end
-  int ord_handoff;
-  int pad4;
-  unsigned long long* spill_dirty; // one-pass launches (totals pending): a residue of the lane-private pairs counts here and makes the page
-                                   // dirty; null = the residues go straight to the limbs (device_agg.h TgSpill)
-};
 // what a lane's double-double pair of aggregate k cannot hold exactly (device_agg.h tg_dd_add1)
 __device__ inline void tg_lc_spill(const FaArgs& F, int k, int g, double r) {
   if (F.spill_dirty) atomicAdd(F.spill_dirty, 1ULL);
@@ -3795,19 +3712,6 @@ static const char *kFqKernel = R"SRC(
 // signatures / LDS records of the groups the table holds (at most FG_LDS_GROUPS); a row that matches none only COUNTS (counters[0]) -- the
 // page is then "dirty": its totals stay pending and are dropped, the host re-runs it through the insert protocol.  A clean page's totals are
 // made final by the NEXT one-pass launch (stream order), or by the host for the last one.
-struct FqArgs {
-  FaArgs fa;
-  TgKeyCols store;
-  int store_groups;
-  int pad;
-  unsigned long long* counters;        // this page: [0] rows of unknown groups, [7] expression error word (~0 = none)
-  const unsigned long long* prev;      // the previous one-pass page's counters (its totals are in fold.pending), or null
-  unsigned long long* host_out;        // host-visible words for the counters ({[0], [2], [7]}, then a flag in word 7), written by the
-  unsigned int* done;                  // workgroup that finishes last (`done` = finished workgroups, rests at 0); null: the host copies
-  const FpArgs* pages;                 // fq_onepass_multi: the launch's pages in order (device memory; error words all = fa.fp.error)
-  int n_pages;
-  int pad3;
-};
 #define FQ_STRIPES 8
 #define FQ_TILE (FQ_STRIPES * 256)
 // the raw loads of one row: filter inputs, key cells (phase A: null flags, fixed-width values, varchar offsets) and the aggregates' inputs
@@ -3941,63 +3845,6 @@ extern "C" __global__ void __launch_bounds__(256) fq_onepass(FqArgs Q) { fq_body
 extern "C" __global__ void __launch_bounds__(256) fq_onepass_multi(FqArgs Q) { fq_body<true>(Q); }
 )SRC";
 
-// host mirror of the generated FaArgs
-struct FaArgsHost {
-    FpArgs fp;
-    const int32_t *gids;
-    unsigned char *mask_out;
-    struct St {
-        int32_t function;
-        int32_t pad;
-        long long *counts;
-        long long *limbs;
-        unsigned int *special;
-        unsigned long long *i128;
-        double *dsum;
-    } st[16];
-    struct Plan {
-        int32_t n_aggs, n_wide;
-        int32_t wide_slot[16];
-        int32_t n_cnt;
-        int32_t cnt_slot[16];
-        int32_t count_from_rows[16];
-        int32_t rows_slot;
-        int32_t per_group_bytes, n_groups;
-    } plan;
-    long long tiles;
-    int32_t lowcard;
-    int32_t pad;
-    const unsigned int *ord_keys;
-    const int *ord_rows;
-    const unsigned char *gids8;
-    struct {
-        unsigned long long *partials;
-        int32_t stride;
-        unsigned long long *pending;
-    } fold;
-    const unsigned long long *gate;
-    const int *ord_stretch;
-    long long *ord_list;
-    unsigned int *ord_list_count;
-    int32_t ord_handoff;
-    int32_t pad4;
-    unsigned long long *spill_dirty;
-};
-// host mirror of the generated FqArgs (fq_onepass)
-struct FqArgsHost {
-    FaArgsHost fa;
-    KeyCols store;
-    int32_t store_groups;
-    int32_t pad;
-    unsigned long long *counters;
-    const unsigned long long *prev;
-    unsigned long long *host_out;
-    unsigned int *done;
-    const FpArgs *pages;
-    int32_t n_pages;
-    int32_t pad3;
-};
-
 }  // namespace
 
 FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_processor_spec *spec, std::vector<tgpu_agg_spec> aggs,
@@ -4005,7 +3852,7 @@ FusedAggGpu::FusedAggGpu(std::vector<int32_t> input_types, const tgpu_page_proce
     : prog_(std::move(input_types), spec), aggs_(std::move(aggs))
 {
     prog_.resolve_projection_types();
-    TG_CHECK_ARG((int)aggs_.size() <= 16, "at most 16 aggregates");
+    TG_CHECK_ARG((int)aggs_.size() <= TG_MAX_AGGS, "at most 16 aggregates");
     supported_ = true;
     const int np = (int)prog_.proj_roots.size();
     for (auto &a : aggs_) {
@@ -4240,11 +4087,11 @@ void FusedAggGpu::generate()
     if (!nf_any.str().empty()) eval_all += "  if (" + nf_any.str() + ") {\n" + nf_slow.str() + "  }\n" + nf_clear.str();
 
     std::ostringstream src;
-    src << kPrelude;
+    src << prelude();
     if (const char *exp = getenv("TGPU_FG_EXP")) src << "#define FG_EXP_" << exp << " 1\n";  // kernel-study switch, never set in production
     if (const char *st = getenv("TGPU_FG_STRIPES")) src << "#define FG_STRIPES " << std::max(1, std::min(16, atoi(st))) << "\n";  // rows per lane per tile of fg_probe
     if (getenv("TGPU_FA_DEBUG_SKIP")) src << "#define FA_DEBUG_SKIP " << atoi(getenv("TGPU_FA_DEBUG_SKIP")) << "\n";   // kernel study only
-    src << device_header("device_hash.h") << device_header("device_agg.h") << gm.consts.str() << gr.consts.str();
+    src << device_header("device_hash.h") << device_header("device_agg.h") << device_header("device_fa_args.h") << gm.consts.str() << gr.consts.str();
     src << "#define FA_LDS_BYTES " << std::max(2048, max_groups_ * per_group_bytes_) << "\n";   // >= the fold's exchange area (device_agg.h)
     // FA_NO_NULLS 1: the specialisation for pages without null vectors (null loads and per-aggregate count slots fold away)
     src << "#ifndef FA_NO_NULLS\n#define FA_NO_NULLS 0\n#endif\n";
@@ -4253,8 +4100,7 @@ void FusedAggGpu::generate()
     if (!key_inputs_.empty()) {
         // key accessor generated for this key schema (the GPU counterpart of JoinCompiler's hashRow / positionNotDistinctFromRow)
         src << device_header("device_cols.h") << device_header("device_groupby.h");
-        src << "struct FgArgs {\n  FpArgs fp;\n  TgKeyCols store;\n  unsigned long long* words;\n  unsigned long long mask;\n  int* out;\n  unsigned long long* counters;\n"
-               "  long long row0;\n  long long n;\n  int store_groups;\n  int pad;\n  const FgArgs* self;\n  unsigned char* out8;\n};\n";
+        src << device_header("device_fg_args.h");
         auto cell = [&](int i, const std::string &row, const std::string &pfx) {
             // declares <pfx>n (null flag) and the cell's value variables for key column i of the raw input at `row`
             const int ch = key_inputs_[(size_t)i];
@@ -4594,8 +4440,6 @@ extern "C" __global__ void __launch_bounds__(256) fg_probe(FgArgs G) {
 }
 )SRC";
     }
-    src << "struct FaArgs;\n";
-    // forward declare FaArgs fields used by the generated accumulate function: emit the struct first
     std::string kernels = kFaKernels;
     const size_t split = kernels.find("#define FA_STRIPES");
     src << kernels.substr(0, split);
@@ -4647,7 +4491,7 @@ extern "C" __global__ void __launch_bounds__(256) fg_probe(FgArgs G) {
     const std::string tag = "@FA_STRIPES@";
     tail.replace(tail.find(tag), tag.size(), std::to_string(fa_stripes()));
     src << tail;
-    if (!key_inputs_.empty()) src << "#define FQ_LDS_BYTES " << std::max(2048, onepass_groups() * per_group_bytes_) << "\n" << kFqKernel;
+    if (!key_inputs_.empty()) src << "#define FQ_LDS_BYTES " << std::max(2048, onepass_groups() * per_group_bytes_) << "\n" << device_header("device_fq_args.h") << kFqKernel;
     source_ = src.str();
 }
 
@@ -4702,7 +4546,7 @@ void FusedAggGpu::filter_mask(Context *ctx, const DevicePage &in, uint8_t *mask_
     TG_CHECK_STATE(supported_, "fused aggregation not supported for this configuration");
     JitModule *module = module_for(in);
     if (in.n == 0) return;
-    FaArgsHost F{};
+    FaArgs F{};
     fill_fp_cols(F.fp, in);
     BufferPtr err = ctx->alloc(8);
     HIP_CHECK(hipMemsetAsync(err->ptr(), 0xff, 8, ctx->stream()));
@@ -4715,23 +4559,6 @@ void FusedAggGpu::filter_mask(Context *ctx, const DevicePage &in, uint8_t *mask_
     }
     raise_if_error(ctx, err);
 }
-
-namespace {
-struct FgArgsHost {
-    FpArgs fp;
-    KeyCols store;
-    unsigned long long *words;
-    unsigned long long mask;
-    int32_t *out;
-    unsigned long long *counters;
-    long long row0;
-    long long n;
-    int32_t store_groups;
-    int32_t pad;
-    const void *self;   // device copy of this block (read by the out-of-line table path)
-    unsigned char *out8;   // compact mode: one byte per row instead of `out` (GbhProbeLaunch)
-};
-}  // namespace
 
 // What accumulate() (one page) and onepass() (a list of pages) both put into the kernels' argument blocks.
 struct FusedAggGpu::HostFill {
@@ -4748,20 +4575,15 @@ struct FusedAggGpu::HostFill {
                 fp.col_values[ch] = dummy->ptr();
             }
     }
-    static void states(const FusedAggGpu &a, FaArgsHost &F, GroupedAccumulators &accs)
+    static void states(const FusedAggGpu &a, FaArgs &F, GroupedAccumulators &accs)
     {
         for (size_t k = 0; k < a.aggs_.size(); k++) {
             GroupedAccumulators::DeviceState d = accs.device_state((int)k);
-            F.st[k].function = d.function;
-            F.st[k].counts = d.counts;
-            F.st[k].limbs = d.limbs;
-            F.st[k].special = d.special;
-            F.st[k].i128 = d.i128;
-            F.st[k].dsum = d.dsum;
+            F.st[k] = TgAggState{d.function, 0, d.counts, d.limbs, d.special, d.i128, d.dsum};
         }
     }
     // the slot plan of the lane-private states (n_groups is the launch's own)
-    static void plan(const FusedAggGpu &a, FaArgsHost &F, const std::vector<const DevicePage *> &pages)
+    static void plan(const FusedAggGpu &a, FaArgs &F, const std::vector<const DevicePage *> &pages)
     {
         F.plan.n_aggs = (int32_t)a.aggs_.size();
         F.plan.n_wide = a.n_wide_;
@@ -4786,7 +4608,7 @@ void FusedAggGpu::probe_groups(Context *ctx, const DevicePage &in, const GbhProb
 {
     TG_CHECK_STATE(supported_ && !key_inputs_.empty(), "fused group lookup not available for this configuration");
     JitModule *module = module_for(in);
-    FgArgsHost G{};
+    FgArgs G{};
     fill_fp_cols(G.fp, in);
     G.fp.error = l.counters + 7;   // the group-by table reads it back together with its own counters (GbhProbeLaunch)
     BufferPtr dummy;
@@ -4822,8 +4644,8 @@ void FusedAggGpu::onepass(Context *ctx, const std::vector<const DevicePage *> &p
         for (const DeviceColumn &c : pg->cols) any_nulls = any_nulls || c.nulls != nullptr;
     JitModule *module = module_variant(any_nulls, false);   // (the variant without null handling only when no page of the launch carries a null vector)
     accs.reserve(max_groups_);
-    FqArgsHost Q{};
-    FaArgsHost &F = Q.fa;
+    FqArgs Q{};
+    FaArgs &F = Q.fa;
     BufferPtr dummy;
     auto fill = [&](FpArgs &fp, const DevicePage &pg) {
         fill_fp_cols(fp, pg);
@@ -4837,9 +4659,7 @@ void FusedAggGpu::onepass(Context *ctx, const std::vector<const DevicePage *> &p
     F.plan.n_groups = (int32_t)groups;
     F.tiles = ceil_div(in.n, 8 * 256);
     const GroupedAccumulators::FoldScratch fs = accs.fold_scratch(blocks, max_groups_);
-    F.fold.partials = fs.partials;
-    F.fold.stride = fs.stride;
-    F.fold.pending = fs.pending;
+    F.fold = TgFoldScratch{fs.partials, fs.stride, fs.pending};
     Q.store = store;
     Q.store_groups = (int32_t)groups;
     Q.counters = counters;
@@ -4898,7 +4718,7 @@ void FusedAggGpu::accumulate(Context *ctx, const DevicePage &in, const int32_t *
     const bool ordered = accs.begin_ordered(gids, in.n, groups, max_groups_, ord_keys, ord_rows);
     // (low-cardinality launches: the states of every group the folded partials have room for, see GroupedAccumulators::fold_scratch)
     if (!ordered) accs.reserve(groups <= max_groups_ ? max_groups_ : groups);
-    FaArgsHost F{};
+    FaArgs F{};
     fill_fp_cols(F.fp, in);
     BufferPtr err = ctx->alloc(8);
     if (accumulate_can_raise_) HIP_CHECK(hipMemsetAsync(err->ptr(), 0xff, 8, ctx->stream()));   // (never written, never read otherwise)
@@ -4954,8 +4774,7 @@ void FusedAggGpu::accumulate(Context *ctx, const DevicePage &in, const int32_t *
     const int64_t blocks = std::min<int64_t>(F.tiles, (int64_t)ctx->cu_count() * (F.lowcard ? 1 : 4));
     if (F.lowcard) {
         const GroupedAccumulators::FoldScratch fs = accs.fold_scratch(blocks, max_groups_);
-        F.fold.partials = fs.partials;
-        F.fold.stride = fs.stride;
+        F.fold = TgFoldScratch{fs.partials, fs.stride, nullptr};
     }
     {
         ProfileScope ps(ctx, F.lowcard ? "fused_project_accumulate_lowcard" : "fused_project_accumulate");
@@ -4969,17 +4788,6 @@ void FusedAggGpu::accumulate(Context *ctx, const DevicePage &in, const int32_t *
 // =====================================================================================================================
 namespace {
 const char *kNlKernels = R"SRC(
-#define NL_STRIP 32
-struct NlArgs {
-  FpArgs fp;
-  unsigned long long* masks;
-  int* counts;
-  const int* offsets;
-  int* pair_probe;
-  int* pair_build;
-  long long s0, S, l0, Ln, W;
-  int build_large, pad;
-};
 // One wave = 64 rows of the large side x NL_STRIP rows of the small side.  The lane loads its large row's values ONCE, in front of the loop;
 // the small row is wave-uniform, so its values are scalar loads; the predicate itself touches registers only (NlRow).  Nothing is stored
 // inside the loop: lane i keeps the ballot of small row i and stores it at the end.
@@ -5140,9 +4948,9 @@ void NestedLoopFilterGpu::generate()
         row << "  (void)A; (void)row; (void)R;\n}\n";
     }
     std::ostringstream src;
-    src << kPrelude << g.consts.str() << row.str();
+    src << prelude() << g.consts.str() << row.str();
     src << "__device__ inline bool tg_pair_filter(const FpArgs& A, const NlRow& R) {\n" << g.os.str() << "  (void)A;\n}\n";
-    src << kNlKernels;
+    src << device_header("device_nl_args.h") << kNlKernels;
     source_ = src.str();
     supported_ = true;
 }

@@ -7,38 +7,23 @@
 #include <set>
 
 #include "common.h"
+// the argument blocks of the generated kernels and the device structs they embed: the files the generated sources embed verbatim (jit.cpp
+// device_header)
+#include "device_fp_args.h"
+#include "device_fv_args.h"
+#include "device_join.h"
+#include "device_fj_args.h"
+#include "device_agg.h"
+#include "device_fa_args.h"
+#include "device_fq_args.h"
+#include "device_fg_args.h"
+#include "device_nl_args.h"
 
 namespace tgpu {
 
-constexpr int kFpMaxCols = 24;
-constexpr int kFpMaxProj = 16;
-constexpr int kFpMaxVarchar = 8;   // computed VARCHAR projections of one page processor
-
-struct FpArgs {  // must match the struct declared in the generated source
-    const void *col_values[kFpMaxCols];
-    const uint8_t *col_nulls[kFpMaxCols];
-    const int32_t *col_offsets[kFpMaxCols];
-    void *out_values[kFpMaxProj];
-    uint8_t *out_nulls[kFpMaxProj];
-    int32_t *positions;
-    const int32_t *tile_offsets;
-    int32_t *tile_counts;
-    unsigned long long *error;
-    long long n;
-    unsigned long long *sel_mask;
-    long long *operand;   // null, or where the lane that posts operand_key stores the operand of its failure (jit.cpp raise_operand)
-    unsigned long long operand_key;
-};
-
-// fp_vwrite, the write pass of the computed VARCHAR projections: fp_emit left each row's byte length in out_values[slot] (an int32 array), the
-// scan of it is offsets[v], and the kernel evaluates the projection again to copy its bytes to pool[v] + offsets[v][o].  The block is this
-// kernel's own: FpArgs, which every fused kernel embeds, keeps its layout.
-struct FvArgs {  // must match the struct declared in the generated source
-    FpArgs fp;
-    const int32_t *offsets[kFpMaxVarchar];
-    uint8_t *pool[kFpMaxVarchar];
-    long long n_out;
-};
+constexpr int kFpMaxCols = TG_MAXC;
+constexpr int kFpMaxProj = TG_MAXP;
+constexpr int kFpMaxVarchar = TG_MAXV;
 
 struct JitModule;
 
@@ -137,49 +122,8 @@ private:
 // private regions, then a scan over the per-tile counts); the probe-side output projections are then evaluated for the
 // matching rows only.  Results are identical to running the two
 // reference operators back to back (M/operator/FilterAndProjectOperator.java + LookupJoinOperator.java).
-constexpr int kFjCountSlots = 64, kFjMiscWords = 16 + kFjCountSlots * 16;   // misc words of a probe launch: [0] error, [2] pairs, [16 + 16 i] selected rows
-struct FjArgs {  // must match the generated struct
-    FpArgs fp;
-    const void *slots;
-    unsigned long long mask;
-    const unsigned long long *bitmap;
-    long long key_min, key_max;
-    const unsigned long long *bloom;
-    unsigned long long bloom_word_mask;
-    const int32_t *direct;
-    const int32_t *rank_base;
-    int32_t *tile_cnt;
-    int32_t *tile_src;
-    const int32_t *tile_dst;
-    int32_t *pair_probe;
-    int32_t *pair_build;
-    int32_t *out_build;
-    unsigned long long *counters;   // [0] rows selected by the filter
-    long long tiles;
-    long long grid1;
-    int32_t outer;
-    int32_t chunk_shift;
-    // build-side output channels gathered by pass 2 itself (fixed-width columns; one launch instead of one more per channel)
-    struct BuildCol {
-        const void *values;
-        const uint8_t *nulls;
-        void *out_values;
-        uint8_t *out_nulls;
-        int32_t width;
-        int32_t pad;
-    } bcol[4];
-    int32_t n_bcol;
-    int32_t pad2;
-    void *carry[4];         // carry variant: block-private regions of the probe-side output values, one per output channel
-    uint8_t *carry_nulls;   //                and of their null bits (nullptr: no output can be null)
-    unsigned long long *host_out;   // small pages: pass 1's last workgroup scans the chunk counts and writes {error, pairs, selected} here
-    unsigned int *done;             //              (host-visible signal slot); `done` counts finished workgroups
-    const FpArgs *pages;            // multi-page launches (kernel variant FJ_EPILOGUE == 2): the pages' column pointers, device memory
-    const int32_t *page_tile0;      //   first tile of each page, [n_pages] = all tiles
-    int32_t n_pages;
-    int32_t pad3;
-};
-constexpr int kFjMaxBuildCols = 4;
+constexpr int kFjCountSlots = FJ_COUNT_SLOTS, kFjMiscWords = 16 + kFjCountSlots * 16;   // misc words of a probe launch: [0] error, [2] pairs, [16 + 16 i] selected rows
+constexpr int kFjMaxBuildCols = FJ_MAX_BUILD_COLS, kFjMaxCarry = FJ_MAX_CARRY;
 constexpr int64_t kFjMultiMaxTiles = 32768;      // tiles of one launch over a list of pages
 constexpr int64_t kFjEpilogueMaxChunks = 2048;   // probe launches of up to 2048 tiles (1.5 M rows at 768-row tiles; always one-tile chunks) end pass 1 with the epilogue
 
@@ -309,8 +253,8 @@ private:
     // kOrdChainMaxDoubles chains (one lane of wave 0 each, LDS for two tiles of them), one workgroup per group, >= kOrdChainMinRows rows per
     // group on average (below that the lane-per-group kernel has more lanes at work)
     int ord_doubles_ = 0;
-    static constexpr int kOrdChainMaxDoubles = 8, kOrdChainWaves = 16;   // = TG_ORD_MAX_DOUBLES, TG_ORD_WAVES (device_agg.h)
-    int wide_slot_[16], cnt_slot_[16];
+    static constexpr int kOrdChainMaxDoubles = TG_ORD_MAX_DOUBLES, kOrdChainWaves = TG_ORD_WAVES;
+    int wide_slot_[TG_MAX_AGGS], cnt_slot_[TG_MAX_AGGS];
     std::vector<std::vector<int>> cnt_inputs_;   // per count slot: the raw input channels its (mask, input) expressions read
     std::vector<bool> cnt_masked_;
     std::string source_;
@@ -323,18 +267,7 @@ private:
 // every row of the large side (a lane keeps its large row, the small row is wave-uniform) and keeps one 64-bit ballot and its popcount per
 // (small row, wave of the large side); after the scan of the counts nlj_pair_emit writes the surviving (probe row, build row) pairs in the
 // order of the reference's output pages: small row major, large row minor.
-struct NlArgs {  // must match the struct declared in the generated source
-    FpArgs fp;
-    unsigned long long *masks;
-    int32_t *counts;
-    const int32_t *offsets;
-    int32_t *pair_probe, *pair_build;
-    long long s0, S;     // rows [s0, s0 + S) of the small side ...
-    long long l0, Ln;    // ... against rows [l0, l0 + Ln) of the large side
-    long long W;         // waves over the large rows: ceil(Ln / 64)
-    int32_t build_large, pad;
-};
-constexpr int kNlStrip = 32;   // small rows one wave evaluates for its 64 large rows (= NL_STRIP of the generated source)
+constexpr int kNlStrip = NL_STRIP;
 
 class NestedLoopFilterGpu {
 public:
